@@ -8,7 +8,7 @@ LR (B,4,32,32,128) -> HR (B,3,128,128,128), full-size G (16 RRDB, nf 128) and th
 128^3 D, bf16 compute with fp32 loss, dropout / instance noise / Adam all on.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3p|C1|C1b|C1c|C2|C3lit|C4|C5b|C5c|C5lit|C6]
-                    [--dtype bf16|fp32] [--batch B] [--n N --nz NZ]
+                    [--dtype bf16|fp32] [--batch B] [--n N --nz NZ] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 ``--gpus N`` with N > 1 and no torchrun environment starts the N ranks itself: the parent - before it makes any
@@ -20,6 +20,12 @@ N-rank step on ONE card (ranks share cuda:0; RCCL refuses duplicate devices, glo
 
 ``--config`` selects the other BASELINE.json configurations; they are recorded in
 DESIGN.md, the driver's line is always the default C3'.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (``metric``, ``value``, ``ms_per_step``, ...).
+``--full`` adds what takes measurements of its own: the per-launch roofline probes (HIP events around the dominant
+kernels inside the timed steps: ``roofline*``), the fp32 side leg of the default line (``fp32_reference_arithmetic``)
+and the CPU baseline (``cpu_baseline``, minutes).  ``--dump-outputs DIR`` writes what the last timed step computed -
+its losses and a fixed, seeded sample of the trained weights - as ``DIR/<name>.npy`` (see ``dump_outputs``).
 """
 import argparse
 import json
@@ -203,6 +209,31 @@ def recorded_traffic(key):
         return None
 
 
+#: ``--dump-outputs``: at most this many elements of each network's state are written (a fixed, seeded sample)
+DUMP_STATE_ELEMS = 1 << 22
+
+
+def dump_outputs(out_dir, losses, nets):
+    """What the last timed step computed, as ``out_dir/<name>.npy``: every loss the step reported
+    (``loss_<name>.npy``, float64 scalars) and, per trained network, its state after the step - the floating-point
+    entries of its state_dict (weights and running statistics) in state_dict order, flattened into one float32
+    vector (``<net>_state.npy``).  A state of more than DUMP_STATE_ELEMS elements is sampled at that many positions
+    drawn with a fixed seed (sorted), the same positions in every run of the same workload: 34 MB in all for C3'."""
+    import re
+
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in losses.items():
+        v = v.detach().cpu() if torch.is_tensor(v) else v
+        np.save(os.path.join(out_dir, "loss_%s.npy" % re.sub(r"[^A-Za-z0-9_.-]", "_", name)), np.asarray(v, dtype=np.float64))
+    for net, module in nets.items():
+        flat = torch.cat([t.detach().reshape(-1).float() for t in module.state_dict().values() if t.is_floating_point()])
+        if flat.numel() > DUMP_STATE_ELEMS:
+            idx = np.sort(np.random.default_rng(2001).choice(flat.numel(), DUMP_STATE_ELEMS, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(os.path.join(out_dir, f"{net}_state.npy"), flat.cpu().numpy())
+
+
 def free_port():
     import socket
     s = socket.socket()
@@ -263,11 +294,17 @@ def main():
     ap.add_argument("--batch", type=int, default=None, help="samples per GPU")
     ap.add_argument("--n", type=int, default=None, help="LR X=Y extent")
     ap.add_argument("--nz", type=int, default=None, help="vertical levels")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the side measurements: roofline probes of single kernels inside the timed steps, the fp32 "
+                         "side leg of the default line and the CPU baseline (minutes)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the losses and (a seeded sample of) the weights of the last timed step as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-baseline-full", action="store_true",
-                    help="BASELINE.md section 4 to the letter: 5 warm-up + 20 timed G- and D-iterations at C1 and C1b (minutes)")
+                    help="BASELINE.md section 4 to the letter: 5 warm-up + 20 timed G- and D-iterations at C1 and C1b "
+                         "(minutes; implies --full)")
     ap.add_argument("--no-fp32-side", action="store_true",
-                    help="skip the fp32 (reference arithmetic) side measurement of the default line")
+                    help="with --full: skip the fp32 (reference arithmetic) side measurement of the default line")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="nccl = RCCL over xGMI")
     ap.add_argument("--one-device", action="store_true", help="every rank on cuda:0 (rehearsal with --backend gloo)")
     ap.add_argument("--dry-launch", action="store_true", help="rendezvous of the N ranks only (CPU, gloo)")
@@ -279,6 +316,9 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    args.full = args.full or args.cpu_baseline_full
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no torchrun environment: become the launcher BEFORE anything touches the GPU
         sys.exit(launch_ranks(args, sys.argv[1:]))
@@ -370,10 +410,12 @@ def main():
         e1.record()
         probe_events[which].append((e0, e1))
 
-    gan.G.program().launch_probe = probe
-    if kind == "gan":
-        gan.D.features.program().launch_probe = probe
+    if args.full:  # (a plain run times the steps without the per-launch events)
+        gan.G.program().launch_probe = probe
+        if kind == "gan":
+            gan.D.features.program().launch_probe = probe
 
+    last_loss = {}
     if kind == "gan":
         def step(i):
             gan.optimize_parameters(LR, HR, Z, 2 * i)      # G-iteration
@@ -385,8 +427,10 @@ def main():
         def step(i):
             gan.G.train()
             gan.optimizer_G.zero_grad(set_to_none=True)
-            l1(gan.G(LR, Z), HR).backward()
+            loss = l1(gan.G(LR, Z), HR)
+            loss.backward()
             gan.optimizer_G.step()
+            last_loss["G_pix"] = loss.detach()
 
     def barrier():
         if distributed:
@@ -438,93 +482,120 @@ def main():
     peak = 2500.0 if args.dtype == "bf16" else 157.3
     esz = 2 if args.dtype == "bf16" else 4
 
-    def mean_ms(evs):
-        ms = [a.elapsed_time(b) for a, b in evs]
-        return (sum(ms) / len(ms), len(ms)) if ms else (None, 0)
+    def rooflines():  # --full: what the launch probes timed inside the steps, against the two rooflines
+        def mean_ms(evs):
+            ms = [a.elapsed_time(b) for a, b in evs]
+            return (sum(ms) / len(ms), len(ms)) if ms else (None, 0)
 
-    k_ms, k_n = mean_ms(probe_events["mfma"])
-    k_flops = 2.0 * B * sX * sX * nz * 125 * 144 * 144
-    achieved = k_flops / (k_ms * 1e-3) / 1e12 if k_ms else None
-    # LFF forward, algorithmic bytes: the 256-channel dense buffer read once + 128 channels written +
-    # the filter.  The block's identity shortcut is the first 128 channels of that same input - the lane's own
-    # K-fragment, no second read.  Every third launch (the last block of an RRDB) also reads the RRDB
-    # shortcut: 128 more channels.  achieved = all algorithmic bytes of the timed launches / their total time.
-    vox = B * n * n * nz
-    h_b1 = vox * (256 + 128) * esz + 256 * 128 * esz
-    h_b2 = h_b1 + vox * 128 * esz
-    h1 = [a.elapsed_time(b) for a, b in probe_events["hbm"]]
-    h2 = [a.elapsed_time(b) for a, b in probe_events["hbm_res2"]]
-    h_n = len(h1) + len(h2)
-    h_ms = (sum(h1) + sum(h2)) / h_n if h_n else None
-    h_bytes = (len(h1) * h_b1 + len(h2) * h_b2) / h_n if h_n else None
-    h_ach = h_bytes / (h_ms * 1e-3) / 1e9 if h_ms else None
-    # the memory-bound conv3d pair (reference Generator_3D_Resnet_ESRGAN.py:105-110, hr_convs[2]): per launch the
-    # 144-channel HR tensor (read by the forward; written by the input gradient, which also reads the saved
-    # 144-channel output of hr_convs[0] for its LeakyReLU / Dropout3d mask) + the 3-channel side as stored
-    # (z-folded: 15 planar fp32 partial sums forward, 16 bf16 channels backward) + the filter
-    V = B * sX * sX * nz
-    kz_fold = gan.G.program().hr1.kernel[2] if gan.G.program().zfold_active() else 1
-    c_hr = 144
-    cf_bytes = V * (c_hr * esz + 3 * kz_fold * 4) + 125 * c_hr * 3 * esz
-    cd_bytes = V * ((3 * kz_fold + 7) // 8 * 8 * esz + 2 * c_hr * esz) + 125 * c_hr * 3 * esz
+        k_ms, k_n = mean_ms(probe_events["mfma"])
+        k_flops = 2.0 * B * sX * sX * nz * 125 * 144 * 144
+        achieved = k_flops / (k_ms * 1e-3) / 1e12 if k_ms else None
+        # LFF forward, algorithmic bytes: the 256-channel dense buffer read once + 128 channels written +
+        # the filter.  The block's identity shortcut is the first 128 channels of that same input - the lane's own
+        # K-fragment, no second read.  Every third launch (the last block of an RRDB) also reads the RRDB
+        # shortcut: 128 more channels.  achieved = all algorithmic bytes of the timed launches / their total time.
+        vox = B * n * n * nz
+        h_b1 = vox * (256 + 128) * esz + 256 * 128 * esz
+        h_b2 = h_b1 + vox * 128 * esz
+        h1 = [a.elapsed_time(b) for a, b in probe_events["hbm"]]
+        h2 = [a.elapsed_time(b) for a, b in probe_events["hbm_res2"]]
+        h_n = len(h1) + len(h2)
+        h_ms = (sum(h1) + sum(h2)) / h_n if h_n else None
+        h_bytes = (len(h1) * h_b1 + len(h2) * h_b2) / h_n if h_n else None
+        h_ach = h_bytes / (h_ms * 1e-3) / 1e9 if h_ms else None
+        # the memory-bound conv3d pair (reference Generator_3D_Resnet_ESRGAN.py:105-110, hr_convs[2]): per launch the
+        # 144-channel HR tensor (read by the forward; written by the input gradient, which also reads the saved
+        # 144-channel output of hr_convs[0] for its LeakyReLU / Dropout3d mask) + the 3-channel side as stored
+        # (z-folded: 15 planar fp32 partial sums forward, 16 bf16 channels backward) + the filter
+        V = B * sX * sX * nz
+        kz_fold = gan.G.program().hr1.kernel[2] if gan.G.program().zfold_active() else 1
+        c_hr = 144
+        cf_bytes = V * (c_hr * esz + 3 * kz_fold * 4) + 125 * c_hr * 3 * esz
+        cd_bytes = V * ((3 * kz_fold + 7) // 8 * 8 * esz + 2 * c_hr * esz) + 125 * c_hr * 3 * esz
 
-    def hbm_block(evs, nbytes, kernel, flops=0.0):
-        """HBM roofline of one memory-bound conv launch; ``flops`` (algorithmic, 2 x MACs) adds the OTHER roofline
-        beside it - the time the launch's arithmetic takes at the dtype's dense MFMA peak - and says which of the
-        two floors is the higher one: in fp32 (matrix rate 1/16 of bf16) most of this set is matrix-bound - the last
-        conv's 0.48 TFLOP at C2 take 3.1 ms at the fp32 MFMA peak against 0.33 ms at 8 TB/s"""
-        ms_, n_ = mean_ms(evs)
-        ach = nbytes / (ms_ * 1e-3) / 1e9 if ms_ else None
-        blk = {"bound": "hbm", "kernel": kernel, "achieved": round(ach, 1) if ach else None, "peak": 8000.0,
-               "unit": "GB/s", "frac": round(ach / 8000.0, 4) if ach else None, "traffic": None,
-               "algorithmic_bytes": int(nbytes), "launches_timed": n_,
-               "avg_launch_us": round(ms_ * 1e3, 2) if ms_ else None}
-        if flops and ms_:
-            hbm_us, mfma_us = nbytes / 8e12 * 1e6, flops / (peak * 1e12) * 1e6
-            blk.update({"algorithmic_gflop": round(flops / 1e9, 2), "hbm_floor_us": round(hbm_us, 2),
-                        "mfma_floor_us": round(mfma_us, 2), "binding_roofline": "mfma" if mfma_us > hbm_us else "hbm",
-                        "frac_of_binding_roofline": round(max(hbm_us, mfma_us) / (ms_ * 1e3), 4)})
-            if achieved:
-                # ... and the same two floors with the matrix side priced at a rate this chip has been SEEN to hold - the
-                # 5x5x5 conv's own measured rate in this run - instead of the nominal peak: a launch whose arithmetic takes
-                # longer than its bytes at that rate is co-bound, and 0.60 of the HBM figure is then out of its reach
-                ach_us = flops / (achieved * 1e12) * 1e6
-                blk.update({"mfma_floor_us_at_achieved_rate": round(ach_us, 2), "achieved_mfma_rate_tflops": round(achieved, 1),
-                            "binding_roofline_at_achieved_rate": "mfma" if ach_us > hbm_us else "hbm",
-                            "frac_of_binding_roofline_at_achieved_rate": round(max(hbm_us, ach_us) / (ms_ * 1e3), 4),
-                            "hbm_frac_ceiling_at_achieved_rate": round(min(1.0, hbm_us / ach_us), 4)})
-        return blk
+        def hbm_block(evs, nbytes, kernel, flops=0.0):
+            """HBM roofline of one memory-bound conv launch; ``flops`` (algorithmic, 2 x MACs) adds the OTHER roofline
+            beside it - the time the launch's arithmetic takes at the dtype's dense MFMA peak - and says which of the
+            two floors is the higher one: in fp32 (matrix rate 1/16 of bf16) most of this set is matrix-bound - the last
+            conv's 0.48 TFLOP at C2 take 3.1 ms at the fp32 MFMA peak against 0.33 ms at 8 TB/s"""
+            ms_, n_ = mean_ms(evs)
+            ach = nbytes / (ms_ * 1e-3) / 1e9 if ms_ else None
+            blk = {"bound": "hbm", "kernel": kernel, "achieved": round(ach, 1) if ach else None, "peak": 8000.0,
+                   "unit": "GB/s", "frac": round(ach / 8000.0, 4) if ach else None, "traffic": None,
+                   "algorithmic_bytes": int(nbytes), "launches_timed": n_,
+                   "avg_launch_us": round(ms_ * 1e3, 2) if ms_ else None}
+            if flops and ms_:
+                hbm_us, mfma_us = nbytes / 8e12 * 1e6, flops / (peak * 1e12) * 1e6
+                blk.update({"algorithmic_gflop": round(flops / 1e9, 2), "hbm_floor_us": round(hbm_us, 2),
+                            "mfma_floor_us": round(mfma_us, 2), "binding_roofline": "mfma" if mfma_us > hbm_us else "hbm",
+                            "frac_of_binding_roofline": round(max(hbm_us, mfma_us) / (ms_ * 1e3), 4)})
+                if achieved:
+                    # ... and the same two floors with the matrix side priced at a rate this chip has been SEEN to hold - the
+                    # 5x5x5 conv's own measured rate in this run - instead of the nominal peak: a launch whose arithmetic takes
+                    # longer than its bytes at that rate is co-bound, and 0.60 of the HBM figure is then out of its reach
+                    ach_us = flops / (achieved * 1e12) * 1e6
+                    blk.update({"mfma_floor_us_at_achieved_rate": round(ach_us, 2), "achieved_mfma_rate_tflops": round(achieved, 1),
+                                "binding_roofline_at_achieved_rate": "mfma" if ach_us > hbm_us else "hbm",
+                                "frac_of_binding_roofline_at_achieved_rate": round(max(hbm_us, ach_us) / (ms_ * 1e3), 4),
+                                "hbm_frac_ceiling_at_achieved_rate": round(min(1.0, hbm_us / ach_us), 4)})
+            return blk
 
-    hr1_flops = 2.0 * V * 125 * c_hr * 3  # (the fold computes 16 columns for 15: counted as the conv's 3 x 125 taps)
-    conv_d = hbm_block(probe_events["conv_dgrad"], cd_bytes,
-                       "hr_convs.2 input gradient (z-folded 15 -> 144, 5x5x1, LeakyReLU+Dropout3d mask epilogue)", hr1_flops)
-    conv_f = hbm_block(probe_events["conv_fwd"], cf_bytes, "hr_convs.2 forward (z-folded 144 -> 15, 5x5x1, planar fp32 out)",
-                       hr1_flops)
-    default_shape = args.dtype == "bf16" and n == 32 and nz == 128 and B == 1 and s == 4
-    if default_shape:
-        conv_d["traffic"], conv_f["traffic"] = recorded_traffic("hr1_dgrad"), recorded_traffic("hr1_fwd")
-    # the other members of the memory-bound conv3d set: (Cin * V_in + Cout * V_out) * sizeof + filter (SURVEY 8d)
-    tf_c, nf_c = gan.G.program().tf, gan.G.program().nf
-    side = [
-        ("terrain0_fwd", "terrain_convs.0 forward (3x3x3, 1 -> %d, LeakyReLU)" % tf_c, V * (1 + tf_c) * esz + 27 * tf_c * esz,
-         2.0 * V * 27 * tf_c),
-        ("terrain1_fwd", "terrain_convs.1 forward (3x3x3, %d -> %d, the terrain half of the concat)" % (tf_c, tf_c),
-         V * 2 * tf_c * esz + 27 * tf_c * tf_c * esz, 2.0 * V * 27 * tf_c * tf_c),
-        ("terrain1_dgrad", "terrain_convs.1 input gradient (3x3x3, %d -> %d)" % (tf_c, tf_c),
-         V * 2 * tf_c * esz + 27 * tf_c * tf_c * esz, 2.0 * V * 27 * tf_c * tf_c),
-        ("feature_fwd", "model.0 feature conv forward (3x3x3, 4 -> %d)" % nf_c, vox * (4 + nf_c) * esz + 27 * 4 * nf_c * esz,
-         2.0 * vox * 27 * 4 * nf_c),
-    ]
-    if kind == "gan":
-        d0 = gan.D.features.program().layers[0].conv
-        side.append(("d0_fwd", "D features.0.0 forward (3x3x3, %d -> %d, D(real) + D(fake) in one launch)" % (d0.cin, d0.cout),
-                     2 * V * (d0.cin + d0.cout) * esz + 27 * d0.cin * d0.cout * esz, 2.0 * 2 * V * 27 * d0.cin * d0.cout))
-    side_blocks = []
-    for key, name, nbytes, flops in side:
-        blk = hbm_block(probe_events[key], nbytes, name, flops)
+        hr1_flops = 2.0 * V * 125 * c_hr * 3  # (the fold computes 16 columns for 15: counted as the conv's 3 x 125 taps)
+        conv_d = hbm_block(probe_events["conv_dgrad"], cd_bytes,
+                           "hr_convs.2 input gradient (z-folded 15 -> 144, 5x5x1, LeakyReLU+Dropout3d mask epilogue)", hr1_flops)
+        conv_f = hbm_block(probe_events["conv_fwd"], cf_bytes, "hr_convs.2 forward (z-folded 144 -> 15, 5x5x1, planar fp32 out)",
+                           hr1_flops)
+        default_shape = args.dtype == "bf16" and n == 32 and nz == 128 and B == 1 and s == 4
         if default_shape:
-            blk["traffic"] = recorded_traffic(key)
-        side_blocks.append(blk)
+            conv_d["traffic"], conv_f["traffic"] = recorded_traffic("hr1_dgrad"), recorded_traffic("hr1_fwd")
+        # the other members of the memory-bound conv3d set: (Cin * V_in + Cout * V_out) * sizeof + filter (SURVEY 8d)
+        tf_c, nf_c = gan.G.program().tf, gan.G.program().nf
+        side = [
+            ("terrain0_fwd", "terrain_convs.0 forward (3x3x3, 1 -> %d, LeakyReLU)" % tf_c, V * (1 + tf_c) * esz + 27 * tf_c * esz,
+             2.0 * V * 27 * tf_c),
+            ("terrain1_fwd", "terrain_convs.1 forward (3x3x3, %d -> %d, the terrain half of the concat)" % (tf_c, tf_c),
+             V * 2 * tf_c * esz + 27 * tf_c * tf_c * esz, 2.0 * V * 27 * tf_c * tf_c),
+            ("terrain1_dgrad", "terrain_convs.1 input gradient (3x3x3, %d -> %d)" % (tf_c, tf_c),
+             V * 2 * tf_c * esz + 27 * tf_c * tf_c * esz, 2.0 * V * 27 * tf_c * tf_c),
+            ("feature_fwd", "model.0 feature conv forward (3x3x3, 4 -> %d)" % nf_c, vox * (4 + nf_c) * esz + 27 * 4 * nf_c * esz,
+             2.0 * vox * 27 * 4 * nf_c),
+        ]
+        if kind == "gan":
+            d0 = gan.D.features.program().layers[0].conv
+            side.append(("d0_fwd", "D features.0.0 forward (3x3x3, %d -> %d, D(real) + D(fake) in one launch)" % (d0.cin, d0.cout),
+                         2 * V * (d0.cin + d0.cout) * esz + 27 * d0.cin * d0.cout * esz, 2.0 * 2 * V * 27 * d0.cin * d0.cout))
+        side_blocks = []
+        for key, name, nbytes, flops in side:
+            blk = hbm_block(probe_events[key], nbytes, name, flops)
+            if default_shape:
+                blk["traffic"] = recorded_traffic(key)
+            side_blocks.append(blk)
+        return {
+            "roofline": {"bound": "mfma",
+                         "kernel": ("conv_tile_kernel<8,1,4,9,2> (LDS halo-tile conv)" if args.dtype == "bf16"
+                                    else "igemm_kernel<F32,4,1,2,9>") + ": hr_convs.0 5x5x5 144->144 fwd + dgrad",
+                         "achieved": round(achieved, 1) if achieved else None, "peak": peak, "unit": "TFLOP/s",
+                         "frac": round(achieved / peak, 4) if achieved else None,
+                         "traffic": recorded_traffic("hr0") if default_shape else None,
+                         "traffic_source": TRAFFIC_JSON + " (PMC passes of this round)" if default_shape else None,
+                         "traffic_measured_in_run": False,
+                         "traffic_measured_at_commit": recorded_traffic_commit() if default_shape else None,
+                         "launches_timed": k_n, "avg_launch_ms": round(k_ms, 3) if k_ms else None},
+            "roofline_hbm": {"bound": "hbm", "kernel": "conv1x1_kernel (streaming 1x1x1 GEMM): RDB LFF 256->128 fwd + residuals",
+                             "achieved": round(h_ach, 1) if h_ach else None, "peak": 8000.0, "unit": "GB/s",
+                             "frac": round(h_ach / 8000.0, 4) if h_ach else None,
+                             "traffic": recorded_traffic("lff_fwd") if default_shape else None,
+                             "traffic_measured_in_run": False,
+                             "algorithmic_bytes": int(h_bytes) if h_bytes else None, "launches_timed": h_n,
+                             "launches_with_second_residual": len(h2),
+                             "avg_launch_us": round(h_ms * 1e3, 2) if h_ms else None},
+            # the WORST of the memory-bound conv3d launches carries the name; all of them are listed
+            "roofline_hbm_conv": dict(min([conv_d, conv_f] + side_blocks,
+                                          key=lambda r: r["frac"] if r["frac"] is not None else 9.0),
+                                      traffic_measured_in_run=False),
+            "roofline_hbm_convs": [conv_d, conv_f] + side_blocks,
+        }
+
     out = {
         "metric": "GAN train-steps/sec (G+D fwd+bwd)" if kind == "gan" else "generator train-steps/sec (G fwd+bwd+Adam)",
         "value": round(value, 4), "unit": "train-steps/s",
@@ -553,35 +624,22 @@ def main():
                    "achieved_tflops_per_gpu": round(step_flops / 1e12 / (elapsed / args.steps), 1),
                    "peak_hbm_gb": round(torch.cuda.max_memory_allocated(dev) / 2**30, 2),
                    "host_issue_ms_per_step": round(issued / args.steps * 1e3, 2)},
-        "roofline": {"bound": "mfma",
-                     "kernel": ("conv_tile_kernel<8,1,4,9,2> (LDS halo-tile conv)" if args.dtype == "bf16"
-                                else "igemm_kernel<F32,4,1,2,9>") + ": hr_convs.0 5x5x5 144->144 fwd + dgrad",
-                     "achieved": round(achieved, 1) if achieved else None, "peak": peak, "unit": "TFLOP/s",
-                     "frac": round(achieved / peak, 4) if achieved else None,
-                     "traffic": recorded_traffic("hr0") if default_shape else None,
-                     "traffic_source": TRAFFIC_JSON + " (PMC passes of this round)" if default_shape else None,
-                     "traffic_measured_in_run": False,
-                     "traffic_measured_at_commit": recorded_traffic_commit() if default_shape else None,
-                     "launches_timed": k_n, "avg_launch_ms": round(k_ms, 3) if k_ms else None},
-        "roofline_hbm": {"bound": "hbm", "kernel": "conv1x1_kernel (streaming 1x1x1 GEMM): RDB LFF 256->128 fwd + residuals",
-                         "achieved": round(h_ach, 1) if h_ach else None, "peak": 8000.0, "unit": "GB/s",
-                         "frac": round(h_ach / 8000.0, 4) if h_ach else None,
-                         "traffic": recorded_traffic("lff_fwd") if default_shape else None,
-                         "traffic_measured_in_run": False,
-                         "algorithmic_bytes": int(h_bytes) if h_bytes else None, "launches_timed": h_n,
-                         "launches_with_second_residual": len(h2),
-                         "avg_launch_us": round(h_ms * 1e3, 2) if h_ms else None},
-        # the WORST of the memory-bound conv3d launches carries the name; all of them are listed
-        "roofline_hbm_conv": dict(min([conv_d, conv_f] + side_blocks,
-                                      key=lambda r: r["frac"] if r["frac"] is not None else 9.0),
-                                  traffic_measured_in_run=False),
-        "roofline_hbm_convs": [conv_d, conv_f] + side_blocks,
     }
+    if args.full:
+        out.update(rooflines())
     if dp is not None:
         out["comm"] = dp.stats.summary(args.steps)
         out["comm"]["bucket_mb"] = cfg.dist.bucket_mb
         out["comm"]["sync_bn"] = bool(cfg.dist.sync_bn)
-    if world == 1 and not args.no_fp32_side and args.dtype == "bf16" and kind == "gan" and args.config == "C3p":
+    if args.dump_outputs:
+        if kind == "gan":
+            losses = {"G_" + k: v for k, v in gan.get_G_train_loss_dict_ref().items()}
+            losses["D_train_loss"] = gan.get_D_loss_dict_ref()["train_loss"]
+            nets = {"G": gan.G, "D": gan.D}
+        else:
+            losses, nets = last_loss, {"G": gan.G}
+        dump_outputs(args.dump_outputs, losses, nets)
+    if args.full and world == 1 and not args.no_fp32_side and args.dtype == "bf16" and kind == "gan" and args.config == "C3p":
         # The reference computes in fp32 (its AMP lines are commented out, Generator_3D_Resnet_ESRGAN.py:65): the same
         # workload in that arithmetic, a few steps, reported beside the bf16 line (never as `value`).
         del step
@@ -613,7 +671,7 @@ def main():
             "note": "same workload with compute_dtype fp32 (v_mfma_f32_16x16x4_f32 tile kernels): the reference's own arithmetic"}
         del gan32
         torch.cuda.empty_cache()
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         # all cores this process may run on ("all physical cores, count stated")
         cores = granted_cores()
         print(f"[bench] cpu_baseline: oracle on {cores} threads (host reports {os.cpu_count()} CPUs) ...", file=sys.stderr,

@@ -46,10 +46,29 @@ def np_(t):
     return t.detach().cpu().numpy()
 
 
+#: largest committed file: a fixture above it is written as byte pieces NAME.000, NAME.001, ... (conftest's
+#: ``golden`` joins them again)
+PIECE_BYTES = 1_000_000
+
+
 def save(name, **arrays):
+    import glob
+    import io
+
     path = os.path.join(HERE, name)
-    np.savez_compressed(path, **arrays)
-    print(f"wrote {name}: {os.path.getsize(path) / 1024:.1f} KiB")
+    buf = io.BytesIO()
+    np.savez_compressed(buf, **arrays)
+    data = buf.getvalue()
+    for old in glob.glob(glob.escape(path)) + glob.glob(glob.escape(path) + ".[0-9][0-9][0-9]"):
+        os.remove(old)
+    if len(data) <= PIECE_BYTES:
+        with open(path, "wb") as f:
+            f.write(data)
+    else:
+        for i in range(0, len(data), PIECE_BYTES):
+            with open(f"{path}.{i // PIECE_BYTES:03d}", "wb") as f:
+                f.write(data[i:i + PIECE_BYTES])
+    print(f"wrote {name}: {len(data) / 1024:.1f} KiB")
 
 
 # --------------------------------------------------------------------------- #

@@ -1,18 +1,19 @@
 #!/bin/bash
-# usage (on the GPU box): bash tools/tuning/final_batch.sh TAG [1|2]   -> everything profiles/README.md lists for the
+# usage (on the GPU box): bash tools/tuning/final_batch.sh TAG 1|2 OUT   -> everything profiles/README.md lists for the
 # round's final build, under gpurun_out/ (copy into profiles/ afterwards with collect_profiles.sh).  Part 1: kernel stats,
 # counter passes, driver-style line, single-rank RCCL line; part 2: presets + the C2 / C1b kernel tables (two gpurun calls:
-# one call is limited to 20 minutes)
+# one call is limited to 20 minutes).  OUT: the folder collect_profiles.sh reads, for the driver-style line with --full
 set -e
 tag=${1:-r05_h}
 part=${2:-1}
+out=${3:?usage: final_batch.sh TAG 1|2 OUT}
 R=$GRAFT_REPO_ROOT
 cd $R
 if [ "$part" = "1" ]; then
-  bash $R/tools/tuning/prof.sh $tag
+  bash $R/tools/tuning/prof.sh $tag --full
   bash $R/tools/tuning/pmc_step.sh $tag
   cd $R
-  python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/${tag}_bench_default.json.log 2> gpurun_out/${tag}_bench_default.err
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$out/${tag}_bench_default.json.log" 2> "$out/${tag}_bench_default.err"
   python bench.py --gpus 1 --single-rank-group --steps 20 --warmup 5 --no-cpu-baseline --no-fp32-side > gpurun_out/${tag}_bench_single_rank_rccl.json.log 2> /dev/null
 else
   rm -f gpurun_out/${tag%_h}_presets.jsonl
