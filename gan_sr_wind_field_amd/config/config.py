@@ -9,6 +9,7 @@ Implemented table-driven: each section is a list of ``(key, kind)`` pairs.
 Extension (optional keys, defaults keep reference behaviour):
   [DEFAULT] compute_dtype = fp32 | bf16     arithmetic type of the HIP kernels
   [DIST]    backend / bucket_mb / sync_bn   data-parallel settings (see dist.py)
+  [DATA]    device_resident = True | False  training / validation splits held in device memory (device_data.py)
 """
 from __future__ import annotations
 
@@ -262,6 +263,19 @@ class DistConfig(IniConfig):
                 setattr(self, key, val)
 
 
+class DataConfig(IniConfig):
+    """[DATA] (extension): input-pipeline settings; absent section = defaults (not printed by ``asINI``)."""
+
+    device_resident: bool = False
+    _schema = (("device_resident", _B),)
+
+    def setDataConfig(self, section):
+        """``section`` None (no [DATA] in the file) restores the defaults."""
+        for key, kind in self._schema:
+            val = None if section is None else _read(section, key, kind)
+            setattr(self, key, getattr(DataConfig, key) if val is None else val)
+
+
 class Config(IniConfig):
     name: str = "default_name"
     model: str = "default_model"
@@ -283,6 +297,7 @@ class Config(IniConfig):
     dataset_val: DatasetValConfig = DatasetValConfig()
     training: TrainingConfig = TrainingConfig()
     dist: DistConfig = DistConfig()
+    data: DataConfig = DataConfig()
     compute_dtype: str = "fp32"
     is_train: bool
     is_use: bool
@@ -308,6 +323,7 @@ class Config(IniConfig):
                 setattr(self, attr, None)
         if parser.has_section("DIST"):
             self.dist.setDistConfig(parser["DIST"])
+        self.data.setDataConfig(parser["DATA"] if parser.has_section("DATA") else None)
 
     def setBaseConfig(self, base):
         self.name = base.get("name")

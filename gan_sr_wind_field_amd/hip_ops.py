@@ -929,3 +929,26 @@ def adam_multi(table: Tensor, lr: float, beta1: float, beta2: float, eps: float,
     step count after this update (shared by all tensors, as in one param group)."""
     check(_lib.lib().wsr_adam_multi(_p(table), table.shape[0], lr, beta1, beta2, eps, weight_decay, step, _stream()),
           "adam_multi")
+
+
+def gather_batch(store: Tensor, desc: Tensor, cin: int, s: int, slice_size: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """One training batch ``(LR, HR, Z)`` out of a resident store (``device_data.ResidentStore``) in ONE launch:
+    ``store`` fp32 (N, cin + 1, X, Y, NZ), ``desc`` int32 (B, 6) rows ``sample, x0, y0, k, flip_x, flip_y`` on the
+    device; ``slice_size`` 0 = the whole domain.  -> planar LR (B, cin, S/s, S/s, NZ), HR (B, 3, S, S, NZ),
+    Z (B, 1, S, S, NZ) on the current stream (``wsr_gather_batch``)."""
+    _need_cuda(store, desc)
+    if store.dtype != torch.float32 or store.dim() != 5 or not store.is_contiguous() or store.shape[1] != cin + 1:
+        raise ValueError(f"gather_batch wants a contiguous fp32 store (N, {cin + 1}, X, Y, NZ), got {tuple(store.shape)}")
+    if desc.dtype != torch.int32 or desc.dim() != 2 or desc.shape[1] != 6 or not desc.is_contiguous():
+        raise ValueError(f"gather_batch wants an int32 (B, 6) descriptor table, got {desc.dtype} {tuple(desc.shape)}")
+    N, _, X, Y, NZ = store.shape
+    B = desc.shape[0]
+    W, H = (slice_size, slice_size) if slice_size else (X, Y)
+    Wc, Hc = -(-W // s), -(-H // s)
+    opts = dict(dtype=torch.float32, device=store.device)
+    lr = torch.empty((B, cin, Wc, Hc, NZ), **opts)
+    hr = torch.empty((B, 3, W, H, NZ), **opts)
+    z = torch.empty((B, 1, W, H, NZ), **opts)
+    check(_lib.lib().wsr_gather_batch(_p(store), N, _p(desc), B, cin, s, slice_size, X, Y, NZ, _p(lr), _p(hr), _p(z),
+                                      _stream()), "gather_batch")
+    return lr, hr, z

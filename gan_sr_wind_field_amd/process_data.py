@@ -233,14 +233,18 @@ class CustomizedDataset(torch.utils.data.Dataset):
     def __len__(self) -> int:
         return len(self.filenames)
 
-    def _tensors(self, u, v, w, pressure, z, z_above_ground):
+    def _tensors(self, u, v, w, pressure, z, z_above_ground, coarseness_factor=None):
+        s = self.coarseness_factor if coarseness_factor is None else coarseness_factor
         return reformat_to_torch(u, v, w, pressure, z, z_above_ground, self.Z_MIN, self.Z_MAX, self.Z_ABOVE_GROUND_MAX,
-                                 self.UVW_MAX, self.P_MIN, self.P_MAX, coarseness_factor=self.coarseness_factor,
+                                 self.UVW_MAX, self.P_MIN, self.P_MAX, coarseness_factor=s,
                                  include_pressure=self.include_pressure, include_z_channel=self.include_z_channel,
                                  include_above_ground_channel=self.include_above_ground_channel,
                                  for_plotting=self.for_plotting)
 
-    def __getitem__(self, index):
+    def load_fields(self, index):
+        """The file side of ``__getitem__``: the sample's pickle (and, with ``interpolate_z``, its cached
+        z-interpolated copy) -> ``((z, z_above_ground, u, v, w, pressure), HR_raw, Z_raw)`` on the full domain;
+        ``HR_raw`` / ``Z_raw`` are the un-interpolated truth of ``is_test`` datasets (0 otherwise).  No random draws."""
         name = self.filenames[index]
         with open(os.path.join(DATA_ROOT, "full_dataset_files", self.subfolder_name, name), "rb") as f:
             z, z_above_ground, u, v, w, pressure = pickle.load(f)
@@ -251,23 +255,41 @@ class CustomizedDataset(torch.utils.data.Dataset):
             z, z_above_ground, u, v, w, pressure = get_interpolated_z_data(
                 os.path.join(DATA_ROOT, "interpolated_z_data", self.subfolder_name, name), self.x, self.y,
                 z_above_ground, u, v, w, pressure, self.terrain)
+        return (z, z_above_ground, u, v, w, pressure), HR_raw, Z_raw
+
+    def draw_augmentation(self):
+        """The random side of ``__getitem__``: ``(x0, y0, k, flip_x, flip_y)`` - slice origin, quarter turns, mirror
+        x / mirror y - drawn from ``np.random`` with exactly the calls the reference makes per sample, in its order
+        (beta, beta when slicing; randint(0, 4) when rotating; rand(), rand() when flipping)."""
+        x0 = y0 = k = 0
+        flip_x = flip_y = False
         if self.enable_slicing:
             # U-shaped beta(1/4, 1/4): patches cluster at the domain borders (reference :159-176)
             x0 = round(np.random.beta(0.25, 0.25) * (self.x.size - self.slice_size))
             y0 = round(np.random.beta(0.25, 0.25) * (self.y.size - self.slice_size))
+        if self.data_aug_rot:
+            k = int(np.random.randint(0, 4))
+        if self.data_aug_flip:
+            flip_x = bool(np.random.rand() > 0.5)
+            flip_y = bool(np.random.rand() > 0.5)
+        return x0, y0, k, flip_x, flip_y
+
+    def __getitem__(self, index):
+        (z, z_above_ground, u, v, w, pressure), HR_raw, Z_raw = self.load_fields(index)
+        x0, y0, k, flip_x, flip_y = self.draw_augmentation()
+        if self.enable_slicing:
             sx, sy = slice(x0, x0 + self.slice_size), slice(y0, y0 + self.slice_size)
             z, z_above_ground, u, v, w, pressure = (a[sx, sy, :] for a in (z, z_above_ground, u, v, w, pressure))
         LR, HR, Z = self._tensors(u, v, w, pressure, z, z_above_ground)
         if self.data_aug_rot:
-            k = int(np.random.randint(0, 4))
             LR, HR, Z = _rotate_wind(LR, k), _rotate_wind(HR, k), torch.rot90(Z, k, [1, 2])
         if self.data_aug_flip:
-            for axis, comp in ((1, 0), (2, 1)):  # mirror x -> u changes sign; mirror y -> v changes sign
-                if np.random.rand() > 0.5:
+            for axis, comp, flip in ((1, 0, flip_x), (2, 1, flip_y)):  # mirror x -> u changes sign; mirror y -> v
+                if flip:
                     LR, HR, Z = torch.flip(LR, [axis]), torch.flip(HR, [axis]), torch.flip(Z, [axis])
                     LR[comp], HR[comp] = -LR[comp], -HR[comp]
         if self.is_test:
-            return LR, HR, Z, name[:-4], HR_raw, Z_raw
+            return LR, HR, Z, self.filenames[index][:-4], HR_raw, Z_raw
         return LR, HR, Z
 
 

@@ -8,7 +8,10 @@ Differences, all additive: ``tensorboardX`` and ``progressbar2`` are optional (s
 loop only when ``WSR_TORCH_PROFILER=1`` (the reference always profiles iterations 3-10); and when the
 process was started by ``torchrun`` (WORLD_SIZE > 1) the loop runs data-parallel: the sampler shards the
 shuffled index list per rank, ``dist.attach`` reduces gradients / BatchNorm statistics / batch-global loss
-terms, and only rank 0 writes checkpoints, logs and validation artefacts.
+terms, and only rank 0 writes checkpoints, logs and validation artefacts.  With ``[DATA] device_resident = True`` the
+training and validation splits are loaded into device memory once and each batch is gathered there
+(``device_data.py``: same batches, same random streams as the ``num_workers = 0`` loaders; every rank holds the whole
+split and the ``DistributedSampler`` drives the descriptor loader).
 """
 from __future__ import annotations
 
@@ -69,15 +72,27 @@ def train(cfg, dataset_train, dataset_validation, x, y):
     if distributed:  # every rank sees a disjoint 1/world of each shuffled epoch
         sampler = torch.utils.data.distributed.DistributedSampler(dataset_train, num_replicas=world, rank=rank,
                                                                   shuffle=True, drop_last=True)
-    dataloader_train = torch.utils.data.DataLoader(
-        dataset_train, batch_size=cfg.dataset_train.batch_size, shuffle=sampler is None, sampler=sampler,
-        num_workers=cfg.dataset_train.num_workers, pin_memory=True, drop_last=distributed)
+    resident = cfg.data.device_resident
+    if resident:  # [DATA] device_resident: both splits in device memory, batches gathered there (device_data.py)
+        from . import device_data
+        dataloader_train = device_data.DeviceLoader(
+            device_data.ResidentStore(dataset_train, cfg.device, num_workers=cfg.dataset_train.num_workers),
+            batch_size=cfg.dataset_train.batch_size, shuffle=sampler is None, sampler=sampler, drop_last=distributed)
+    else:
+        dataloader_train = torch.utils.data.DataLoader(
+            dataset_train, batch_size=cfg.dataset_train.batch_size, shuffle=sampler is None, sampler=sampler,
+            num_workers=cfg.dataset_train.num_workers, pin_memory=True, drop_last=distributed)
     status_logger.info("finished creating training dataloader and dataset")
     dataloader_val = None
     if cfg.dataset_val and dataset_validation is not None and len(dataset_validation) > 0:
-        dataloader_val = torch.utils.data.DataLoader(
-            dataset_validation, batch_size=cfg.dataset_val.batch_size, shuffle=False,
-            num_workers=cfg.dataset_val.num_workers, pin_memory=True)
+        if resident:
+            dataloader_val = device_data.DeviceLoader(
+                device_data.ResidentStore(dataset_validation, cfg.device, num_workers=cfg.dataset_val.num_workers),
+                batch_size=cfg.dataset_val.batch_size, shuffle=False)
+        else:
+            dataloader_val = torch.utils.data.DataLoader(
+                dataset_validation, batch_size=cfg.dataset_val.batch_size, shuffle=False,
+                num_workers=cfg.dataset_val.num_workers, pin_memory=True)
         status_logger.info("finished creating validation dataloader and dataset")
     else:
         status_logger.warning("no validation dataset supplied! consider adjusting the config")

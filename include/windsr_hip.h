@@ -487,6 +487,18 @@ int wsr_bn_train_stats(const void* x, int32_t C, int64_t nvox_g, int32_t groups,
 int wsr_ragan_loss(const float* u, const float* v, const float* lu, const float* lv, const float* mu, const float* mv,
                    int32_t B, float* out, void* stream);
 
+/* ---- device-resident training data ---------------------------------------------
+ * One training batch out of a resident store (device_data.py): slice, coarsen, rotate and mirror of
+ * CustomizedDataset.__getitem__ (process_data.py), as pure data movement (copies and sign flips).
+ * store: fp32 (n_samples, Cin + 1, X, Y, NZ) - channels [0, Cin) the normalised LR channels at full resolution (0..2 =
+ * the HR wind), channel Cin the raw altitude Z.  desc: int32 [B][6] = sample, x0, y0, k, fx, fy per batch entry.
+ * S = slice size (0: the whole X x Y domain; then X == Y unless every k is even), s = coarseness.  Writes planar
+ * lr (B, Cin, ceil(S/s), ceil(S/s), NZ), hr (B, 3, S, S, NZ), z (B, 1, S, S, NZ): slice -> [::s, ::s] (lr) ->
+ * rot90(k, dims (x, y)) with the u / v mixing of the rotation -> mirror x (u negated) if fx -> mirror y (v negated)
+ * if fy.  A batch entry whose descriptor falls outside the store is not written.                                */
+int wsr_gather_batch(const float* store, int64_t n_samples, const int32_t* desc, int32_t B, int32_t Cin, int32_t s,
+                     int32_t S, int32_t X, int32_t Y, int32_t NZ, float* lr, float* hr, float* z, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
