@@ -126,12 +126,28 @@ class wind_field_GAN_3D(BaseGAN):
         Adam = torch.optim.Adam
         if fused and os.environ.get("WSR_TABLE_ADAM", "1") != "0":
             from ..tools.table_adam import TableAdam as Adam
+        # [GRAD_CLIP] (extension; absent: no clipping, no norms): the bound of each network, None = not clipped
+        gc = cfg.grad_clip
+        self._clip_bound = {"G": cfg_G.max_norm if gc.clip_generator else None,
+                            "D": gc.max_norm_discriminator if gc.clip_discriminator else None}
+        self._track_norms = bool(gc.log_grad_norms)
+        self._grad_norms = {"G": None, "D": None}
+        table = Adam is not torch.optim.Adam
+        clip_kw = {w: ({"max_grad_norm": b, "track_grad_norm": self._track_norms} if table and (b is not None or
+                                                                                               self._track_norms) else {})
+                   for w, b in self._clip_bound.items()}
         self.optimizer_G = Adam(self.G.parameters(), lr=cfg_t.learning_rate_g,
                                 weight_decay=cfg_t.adam_weight_decay_g,
-                                betas=(cfg_t.adam_beta1_g, 0.999), **fused)
+                                betas=(cfg_t.adam_beta1_g, 0.999), **fused, **clip_kw["G"])
         self.optimizer_D = Adam(self.D.parameters(), lr=cfg_t.learning_rate_d,
                                 weight_decay=cfg_t.adam_weight_decay_d,
-                                betas=(cfg_t.adam_beta1_d, 0.999), **fused)
+                                betas=(cfg_t.adam_beta1_d, 0.999), **fused, **clip_kw["D"])
+        if not table:
+            # torch's Adam: the clip is torch's, in a step pre-hook (registered before dist.attach's, so it waits for the
+            # gradient averaging itself - the norm must come from the averaged gradients on every rank)
+            for w, opt in (("G", self.optimizer_G), ("D", self.optimizer_D)):
+                if self._clip_bound[w] is not None or self._track_norms:
+                    opt.register_step_pre_hook(lambda opt_, *_, w_=w: self._clip_before_step(w_, opt_))
         if fused:
             self.optimizer_G.register_step_post_hook(lambda *_: self.G.program().filters.invalidate())
             self.optimizer_D.register_step_post_hook(lambda *_: self.D.features.program().filters.invalidate())
@@ -600,6 +616,25 @@ class wind_field_GAN_3D(BaseGAN):
         else:
             self.HR_labels, self.fake_HR_labels = a.squeeze(), b.squeeze()
             self._labels_all_09 = None
+
+    # ------------------------------------------------------------------ gradient norms
+    def _clip_before_step(self, which: str, opt) -> None:
+        if self.dp is not None:
+            self.dp.wait()  # (the wait in dist.attach's own pre-hook is then a no-op)
+        params = [p for g in opt.param_groups for p in g["params"] if p.grad is not None]
+        bound = self._clip_bound[which]
+        if bound is not None:
+            self._grad_norms[which] = torch.nn.utils.clip_grad_norm_(params, bound)
+        else:
+            self._grad_norms[which] = torch.nn.utils.get_total_norm([p.grad for p in params])
+
+    def get_grad_norms(self) -> dict:
+        """pre-clip L2 norms of the last G and D steps that ran ([GRAD_CLIP] clip_* or log_grad_norms): 0-d device
+        tensors, read by the caller when it logs (None: not measured, or no step yet)"""
+        out = {}
+        for w, opt in (("G", getattr(self, "optimizer_G", None)), ("D", getattr(self, "optimizer_D", None))):
+            out[w] = opt.last_grad_norm if hasattr(opt, "last_grad_norm") else getattr(self, "_grad_norms", {}).get(w)
+        return out
 
     # ------------------------------------------------------------------ getters
     def get_G_train_loss_dict_ref(self):

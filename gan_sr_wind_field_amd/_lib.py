@@ -21,7 +21,8 @@ EXPORTS = [
     "wsr_frag_filter_elems", "wsr_pack_filter_frag", "wsr_pack_filter_frag_multi",
     "wsr_pack_filter", "wsr_unpack_wgrad", "wsr_unpack_wgrad_multi", "wsr_lrelu_bwd_inplace", "wsr_chan_axpby", "wsr_chan_sum", "wsr_chan_sum_rows", "wsr_chan_sum_partials", "wsr_upsample2_bwd", "wsr_subpixel_fold", "wsr_subpixel_unfold", "wsr_strided_parity_filters", "wsr_strided_parity_unfold",
     "wsr_planar_to_ndhwc", "wsr_ndhwc_to_planar", "wsr_zfold", "wsr_zunfold", "wsr_wind_gradient", "wsr_wind_gradient_bwd", "wsr_plane_sum", "wsr_linear_rows", "wsr_physics_loss_workspace_floats", "wsr_physics_loss_stats", "wsr_physics_loss_bwd", "wsr_bn_stats", "wsr_bn_mean", "wsr_bn_shard_stats", "wsr_bn_combine_shards", "wsr_bn_finalize", "wsr_bn_apply_lrelu", "wsr_bn_bwd_reduce",
-    "wsr_bn_bwd_apply", "wsr_adam_step", "wsr_adam_multi", "wsr_gather_batch",
+    "wsr_bn_bwd_apply", "wsr_adam_step", "wsr_adam_multi", "wsr_gather_batch", "wsr_grad_sqnorm_multi",
+    "wsr_adam_multi_clip",
 ]
 
 
@@ -138,6 +139,8 @@ def lib() -> C.CDLL:
         "wsr_ragan_loss": [vp, vp, vp, vp, vp, vp, i32, vp, vp],   # ABI 9
         "wsr_bn_train_stats": [vp, i32, i64, i32, f32, f32, vp, vp, vp, vp, i32, vp],   # ABI 9
         "wsr_gather_batch": [vp, i64, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp],   # additive export
+        "wsr_grad_sqnorm_multi": [vp, i32, vp, vp],   # additive export
+        "wsr_adam_multi_clip": [vp, i32, vp] + [C.c_double] * 6 + [i32, vp, vp],   # additive export
     }
     for name, argtypes in sig.items():
         fn = getattr(L, name)

@@ -10,10 +10,13 @@ Extension (optional keys, defaults keep reference behaviour):
   [DEFAULT] compute_dtype = fp32 | bf16     arithmetic type of the HIP kernels
   [DIST]    backend / bucket_mb / sync_bn   data-parallel settings (see dist.py)
   [DATA]    device_resident = True | False  training / validation splits held in device memory (device_data.py)
+  [GRAD_CLIP] clip_generator / clip_discriminator / max_norm_discriminator / log_grad_norms
+            gradient-norm clipping of the optimizer steps (the generator's bound is [GENERATOR] max_norm)
 """
 from __future__ import annotations
 
 import ast
+import math
 from configparser import ConfigParser
 from typing import Any, List, Sequence, Tuple
 
@@ -276,6 +279,35 @@ class DataConfig(IniConfig):
             setattr(self, key, getattr(DataConfig, key) if val is None else val)
 
 
+class GradClipConfig(IniConfig):
+    """[GRAD_CLIP] (extension): gradient-norm clipping in the optimizer steps (tools/table_adam.py); absent section =
+    defaults, all off, and not printed by ``asINI``.  The generator's bound is [GENERATOR] max_norm."""
+
+    clip_generator: bool = False
+    clip_discriminator: bool = False
+    max_norm_discriminator: float = 1.0
+    log_grad_norms: bool = False
+    _schema = (("clip_generator", _B), ("clip_discriminator", _B), ("max_norm_discriminator", _F),
+               ("log_grad_norms", _B))
+
+    def setGradClipConfig(self, section):
+        """``section`` None (no [GRAD_CLIP] in the file) restores the defaults."""
+        self.present = section is not None
+        for key, kind in self._schema:
+            val = None if section is None else _read(section, key, kind)
+            setattr(self, key, getattr(GradClipConfig, key) if val is None else val)
+
+    def validate(self, max_norm_generator) -> None:
+        """every bound that clips must be > 0 and finite"""
+        for on, key, bound in ((self.clip_generator, "[GENERATOR] max_norm", max_norm_generator),
+                               (self.clip_discriminator, "[GRAD_CLIP] max_norm_discriminator", self.max_norm_discriminator)):
+            if on and not (bound is not None and bound > 0 and math.isfinite(bound)):
+                raise ValueError(f"{key} must be > 0 and finite when clipping is on, not {bound}")
+
+    def __str__(self) -> str:
+        return "[GRAD_CLIP]\n" + "".join(f"{k} = {getattr(self, k)}\n" for k, _ in self._schema)
+
+
 class Config(IniConfig):
     name: str = "default_name"
     model: str = "default_model"
@@ -298,6 +330,7 @@ class Config(IniConfig):
     training: TrainingConfig = TrainingConfig()
     dist: DistConfig = DistConfig()
     data: DataConfig = DataConfig()
+    grad_clip: GradClipConfig = GradClipConfig()
     compute_dtype: str = "fp32"
     is_train: bool
     is_use: bool
@@ -324,6 +357,8 @@ class Config(IniConfig):
         if parser.has_section("DIST"):
             self.dist.setDistConfig(parser["DIST"])
         self.data.setDataConfig(parser["DATA"] if parser.has_section("DATA") else None)
+        self.grad_clip.setGradClipConfig(parser["GRAD_CLIP"] if parser.has_section("GRAD_CLIP") else None)
+        self.grad_clip.validate(self.generator.max_norm)
 
     def setBaseConfig(self, base):
         self.name = base.get("name")
@@ -351,4 +386,6 @@ class Config(IniConfig):
         for sec in sections:
             if sec is not None:
                 out += "\n" + str(sec)
+        if getattr(self.grad_clip, "present", False):  # (absent: the text of a file without the extension, unchanged)
+            out += "\n" + str(self.grad_clip)
         return out

@@ -604,6 +604,17 @@ __global__ void adam_kernel(float* p, const float* __restrict__ g, float* m, flo
 
 // one workgroup per job (a chunk of one tensor); the arithmetic of adam_kernel, element for element
 struct AdamK { float step_size, beta1, omb1, beta2, omb2, eps, wd, bc2_sqrt; };
+// torch.optim.Adam's hyper-parameters are doubles: 1 - beta and the bias corrections are taken in double, rounded once
+static AdamK adam_k(double lr, double beta1, double beta2, double eps, double weight_decay, int step) {
+  const double bc1 = 1.0 - pow(beta1, (double)step);
+  const double bc2 = 1.0 - pow(beta2, (double)step);
+  AdamK k;
+  k.step_size = (float)(lr / bc1);
+  k.beta1 = (float)beta1; k.omb1 = (float)(1.0 - beta1);
+  k.beta2 = (float)beta2; k.omb2 = (float)(1.0 - beta2);
+  k.eps = (float)eps; k.wd = (float)weight_decay; k.bc2_sqrt = (float)sqrt(bc2);
+  return k;
+}
 __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, const AdamK& k) {
   if (k.wd != 0.f) g += k.wd * p;
   m = k.beta1 * m + k.omb1 * g;
@@ -637,6 +648,95 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const wsr_adam_job_t* _
   for (long i = done + threadIdx.x; i < n; i += 256) {
     float p = j.p[i], m = j.m[i], v = j.v[i];
     adam_one(p, j.g[i], m, v, k);
+    j.p[i] = p; j.m[i] = m; j.v[i] = v;
+  }
+}
+
+// ---- gradient-norm clipping (torch.nn.utils.clip_grad_norm_ folded into the table Adam) ----------------------------
+// Sum over the 256 threads of a workgroup in a fixed order (butterfly in each wave - every lane ends with the same
+// bits - then the four wave sums in LDS): the same bits from run to run, no atomics.
+template <class F>
+__device__ __forceinline__ F wg256_sum(F s, F* sh) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+  __syncthreads();
+  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
+// one workgroup per job: partials[job] = sum of g^2 over the job's chunk (4 accumulators per thread, one per float4 lane)
+__global__ __launch_bounds__(256) void grad_sqnorm_multi_kernel(const wsr_adam_job_t* __restrict__ jobs,
+                                                                float* __restrict__ partials) {
+  __shared__ float sh[4];
+  const wsr_adam_job_t j = jobs[blockIdx.x];
+  const long n = j.n;
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+  long done = 0;
+  if ((((size_t)j.g) & 15) == 0) {
+    const long n4 = n >> 2;
+    const float4* g4 = reinterpret_cast<const float4*>(j.g);
+    for (long i = threadIdx.x; i < n4; i += 256) {
+      const float4 g = g4[i];
+      a0 += g.x * g.x; a1 += g.y * g.y; a2 += g.z * g.z; a3 += g.w * g.w;
+    }
+    done = n4 << 2;
+  }
+  for (long i = done + threadIdx.x; i < n; i += 256) {
+    const float g = j.g[i];
+    a0 += g * g;
+  }
+  const float s = wg256_sum((a0 + a1) + (a2 + a3), sh);
+  if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
+// adam_multi_kernel behind the clip: every workgroup sums partials[0..n_jobs) in the same order (double, rounded once),
+// so all of them hold the same total and coefficient; clip = 0 measures only (coef 1, .grad not written)
+__global__ __launch_bounds__(256) void adam_multi_clip_kernel(const wsr_adam_job_t* __restrict__ jobs,
+                                                              const float* __restrict__ partials, int n_jobs,
+                                                              float max_norm, int clip, const AdamK k,
+                                                              float* __restrict__ total_out) {
+  __shared__ double sh[4];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n_jobs; i += 256) s += (double)partials[i];
+  const float total = (float)sqrt(wg256_sum(s, sh));
+  float coef = 1.f;
+  if (clip) {
+    const float c = max_norm / (total + 1e-6f);  // torch: max_norm / (total_norm + 1e-6), clamped to <= 1 (NaN stays NaN)
+    coef = c > 1.f ? 1.f : c;
+  }
+  if (total_out && blockIdx.x == 0 && threadIdx.x == 0) *total_out = total;
+  const wsr_adam_job_t j = jobs[blockIdx.x];
+  float* gw = const_cast<float*>(j.g);  // the scaled gradient goes back to .grad, as torch's in-place clip leaves it
+  const long n = j.n;
+  const bool vec = ((((size_t)j.p) | ((size_t)j.g) | ((size_t)j.m) | ((size_t)j.v)) & 15) == 0;
+  long done = 0;
+  if (vec) {
+    const long n4 = n >> 2;
+    float4* p4 = reinterpret_cast<float4*>(j.p);
+    float4* g4 = reinterpret_cast<float4*>(gw);
+    float4* m4 = reinterpret_cast<float4*>(j.m);
+    float4* v4 = reinterpret_cast<float4*>(j.v);
+    for (long i = threadIdx.x; i < n4; i += 256) {
+      float4 p = p4[i], m = m4[i], v = v4[i], g = g4[i];
+      if (clip) {
+        g.x *= coef; g.y *= coef; g.z *= coef; g.w *= coef;
+        g4[i] = g;
+      }
+      adam_one(p.x, g.x, m.x, v.x, k);
+      adam_one(p.y, g.y, m.y, v.y, k);
+      adam_one(p.z, g.z, m.z, v.z, k);
+      adam_one(p.w, g.w, m.w, v.w, k);
+      p4[i] = p; m4[i] = m; v4[i] = v;
+    }
+    done = n4 << 2;
+  }
+  for (long i = done + threadIdx.x; i < n; i += 256) {
+    float p = j.p[i], m = j.m[i], v = j.v[i], g = gw[i];
+    if (clip) {
+      g *= coef;
+      gw[i] = g;
+    }
+    adam_one(p, g, m, v, k);
     j.p[i] = p; j.m[i] = m; j.v[i] = v;
   }
 }
@@ -1440,14 +1540,28 @@ extern "C" int wsr_adam_step(float* p, const float* g, float* m, float* v, int64
 extern "C" int wsr_adam_multi(const wsr_adam_job_t* jobs_dev, int32_t n_jobs, double lr, double beta1, double beta2, double eps,
                               double weight_decay, int32_t step, void* stream) {
   if (!jobs_dev || n_jobs <= 0 || step < 1) return WSR_EINVAL;
-  const double bc1 = 1.0 - pow(beta1, (double)step);
-  const double bc2 = 1.0 - pow(beta2, (double)step);
-  AdamK k;
-  k.step_size = (float)(lr / bc1);
-  k.beta1 = (float)beta1; k.omb1 = (float)(1.0 - beta1);
-  k.beta2 = (float)beta2; k.omb2 = (float)(1.0 - beta2);
-  k.eps = (float)eps; k.wd = (float)weight_decay; k.bc2_sqrt = (float)sqrt(bc2);
+  const AdamK k = adam_k(lr, beta1, beta2, eps, weight_decay, step);
   hipLaunchKernelGGL(adam_multi_kernel, dim3((unsigned)n_jobs), dim3(256), 0, as_stream(stream), jobs_dev, k);
+  WSR_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int wsr_grad_sqnorm_multi(const wsr_adam_job_t* jobs_dev, int32_t n_jobs, float* partials, void* stream) {
+  if (!jobs_dev || !partials || n_jobs <= 0) return WSR_EINVAL;
+  hipLaunchKernelGGL(grad_sqnorm_multi_kernel, dim3((unsigned)n_jobs), dim3(256), 0, as_stream(stream), jobs_dev,
+                     partials);
+  WSR_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int wsr_adam_multi_clip(const wsr_adam_job_t* jobs_dev, int32_t n_jobs, const float* partials,
+                                   double max_norm, double lr, double beta1, double beta2, double eps,
+                                   double weight_decay, int32_t step, float* total_norm_out, void* stream) {
+  if (!jobs_dev || !partials || n_jobs <= 0 || step < 1 || !(max_norm > 0.0)) return WSR_EINVAL;
+  const AdamK k = adam_k(lr, beta1, beta2, eps, weight_decay, step);
+  const int clip = std::isinf(max_norm) ? 0 : 1;
+  hipLaunchKernelGGL(adam_multi_clip_kernel, dim3((unsigned)n_jobs), dim3(256), 0, as_stream(stream), jobs_dev,
+                     partials, (int)n_jobs, (float)max_norm, clip, k, total_norm_out);
   WSR_LAUNCH_CHECK();
   return 0;
 }

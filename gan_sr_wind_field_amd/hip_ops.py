@@ -931,6 +931,34 @@ def adam_multi(table: Tensor, lr: float, beta1: float, beta2: float, eps: float,
           "adam_multi")
 
 
+def _check_partials(table: Tensor, partials: Tensor) -> None:
+    if partials.dtype != torch.float32 or not partials.is_cuda or not partials.is_contiguous() \
+            or partials.numel() < table.shape[0] or partials.device != table.device:
+        raise ValueError("grad-norm partials want a contiguous fp32 device buffer of one float per job of the table")
+
+
+def grad_sqnorm_multi(table: Tensor, partials: Tensor) -> None:
+    """``partials[job]`` = sum of squares of the gradient chunk of each job of ``table`` (:func:`adam_job_table`), one
+    launch, the same bits from run to run."""
+    _check_partials(table, partials)
+    check(_lib.lib().wsr_grad_sqnorm_multi(_p(table), table.shape[0], _p(partials), _stream()), "grad_sqnorm_multi")
+
+
+def adam_multi_clip(table: Tensor, partials: Tensor, max_norm: float, lr: float, beta1: float, beta2: float,
+                    eps: float, weight_decay: float, step: int, total_norm: Optional[Tensor] = None) -> None:
+    """:func:`adam_multi` behind ``clip_grad_norm_(max_norm)`` over every gradient of ``table``: the coefficient comes
+    from ``partials`` (:func:`grad_sqnorm_multi` of the same table) on the device, the scaled gradients are written
+    back.  ``max_norm`` = inf measures only (gradients untouched, the update is :func:`adam_multi`'s).  ``total_norm``
+    (0-d fp32 device tensor) receives the pre-clip norm."""
+    _check_partials(table, partials)
+    if not max_norm > 0:
+        raise ValueError(f"adam_multi_clip: max_norm must be > 0, not {max_norm}")
+    if total_norm is not None and (total_norm.dtype != torch.float32 or total_norm.device != table.device):
+        raise ValueError("adam_multi_clip: total_norm wants a fp32 tensor on the table's device")
+    check(_lib.lib().wsr_adam_multi_clip(_p(table), table.shape[0], _p(partials), max_norm, lr, beta1, beta2, eps,
+                                         weight_decay, step, _p(total_norm), _stream()), "adam_multi_clip")
+
+
 def gather_batch(store: Tensor, desc: Tensor, cin: int, s: int, slice_size: int) -> Tuple[Tensor, Tensor, Tensor]:
     """One training batch ``(LR, HR, Z)`` out of a resident store (``device_data.ResidentStore``) in ONE launch:
     ``store`` fp32 (N, cin + 1, X, Y, NZ), ``desc`` int32 (B, 6) rows ``sample, x0, y0, k, flip_x, flip_y`` on the

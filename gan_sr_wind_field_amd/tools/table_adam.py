@@ -7,8 +7,15 @@ pointers live in a DEVICE table (``wsr_adam_multi``, one workgroup per 32 768-el
 is one launch.  Same hyper-parameters, same ``state`` layout (``step`` / ``exp_avg`` / ``exp_avg_sq`` per parameter) and
 therefore the same ``state_dict`` and checkpoints as ``torch.optim.Adam(fused=True)``, which it falls back to whenever
 the fast path does not apply (CPU tensors, a missing gradient, amsgrad / maximize / capturable / differentiable).
+
+Gradient-norm clipping (``max_grad_norm``: ``torch.nn.utils.clip_grad_norm_`` over each param group, applied INSIDE
+``step()``, i.e. after the step pre-hooks - under data parallelism the one that waits for the gradient averaging) is
+two launches on the fast path: ``wsr_grad_sqnorm_multi`` over the table, then ``wsr_adam_multi_clip``, which takes the
+coefficient on the device, writes the clipped gradients back and updates.  ``track_grad_norm`` measures without
+clipping.  Either way ``last_grad_norm`` holds the pre-clip norm as a 0-d device tensor (no host sync).
 """
-from typing import Dict, List, Tuple
+import math
+from typing import Dict, List, Optional, Tuple
 
 import torch
 
@@ -16,13 +23,46 @@ from .. import hip_ops
 
 
 class TableAdam(torch.optim.Adam):
-    def __init__(self, params, **kw):
+    def __init__(self, params, max_grad_norm: Optional[float] = None, track_grad_norm: bool = False, **kw):
         kw.setdefault("fused", True)
         super().__init__(params, **kw)
+        self.max_grad_norm = max_grad_norm           # None: no clipping
+        self.track_grad_norm = track_grad_norm       # measure the norm even when not clipping
+        self.last_grad_norm: Optional[torch.Tensor] = None  # pre-clip norm of the last measured step (one per group)
+        self._partials: Dict[int, torch.Tensor] = {}  # per param group: one float per job of its table
         self._tables: Dict[int, torch.Tensor] = {}   # per param group: device table of (param, grad, state) chunks
         self._sig: Dict[int, tuple] = {}             # ... and the (param, grad) pointers it was built from
         self._host_step: List[int] = [-1] * len(self.param_groups)  # -1: not yet read from the state
         self._steps_dirty = False
+
+    @property
+    def max_grad_norm(self) -> Optional[float]:
+        return self._max_grad_norm
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, v: Optional[float]) -> None:
+        if v is not None:
+            v = float(v)
+            if not (v > 0 and math.isfinite(v)):
+                raise ValueError(f"max_grad_norm must be > 0 and finite, not {v}")
+        self._max_grad_norm = v
+
+    def _measures(self) -> bool:
+        return self._max_grad_norm is not None or self.track_grad_norm
+
+    def _set_norms(self, norms: List[torch.Tensor]) -> None:
+        self.last_grad_norm = norms[0] if len(norms) == 1 else torch.stack(norms)
+
+    def _clip_fallback(self) -> None:
+        """torch's own clip (or, tracking only, its norm) over each group, in front of torch's step"""
+        norms = []
+        for group in self.param_groups:
+            params = [p for p in group["params"] if p.grad is not None]
+            if self._max_grad_norm is not None:
+                norms.append(torch.nn.utils.clip_grad_norm_(params, self._max_grad_norm))
+            else:
+                norms.append(torch.nn.utils.get_total_norm([p.grad for p in params]))
+        self._set_norms(norms)
 
     # ---- state bookkeeping ----------------------------------------------------------------------------------
     def _init_state(self, p: torch.Tensor) -> dict:
@@ -81,10 +121,15 @@ class TableAdam(torch.optim.Adam):
                     self._host_step[gi] = int(round(hi))
         if not fast:
             self._sync_steps()
+            if self._measures():
+                if closure is not None:  # (the gradients a closure computes exist only inside torch's step)
+                    raise ValueError("TableAdam: gradient-norm clipping does not take a closure")
+                self._clip_fallback()
             out = super().step(closure)
             self._host_step = [-1] * len(self.param_groups)
             self._sig.clear()
             return out
+        norms: List[torch.Tensor] = []
         for gi, group in enumerate(self.param_groups):
             self._host_step[gi] += 1
             if self._sig.get(gi) != sigs[gi]:
@@ -93,10 +138,25 @@ class TableAdam(torch.optim.Adam):
                     st = self._init_state(p)
                     quads.append((p, p.grad, st["exp_avg"], st["exp_avg_sq"]))
                 self._tables[gi] = hip_ops.adam_job_table(quads)
+                self._partials.pop(gi, None)
                 self._sig[gi] = sigs[gi]
             table = self._tables[gi]
             b1, b2 = group["betas"]
-            hip_ops.adam_multi(table, float(group["lr"]), b1, b2, group["eps"], group["weight_decay"], self._host_step[gi])
+            if not self._measures():
+                hip_ops.adam_multi(table, float(group["lr"]), b1, b2, group["eps"], group["weight_decay"],
+                                   self._host_step[gi])
+                continue
+            if gi not in self._partials:
+                self._partials[gi] = torch.empty(table.shape[0], dtype=torch.float32, device=table.device)
+            partials = self._partials[gi]
+            norm = torch.empty((), dtype=torch.float32, device=table.device)
+            hip_ops.grad_sqnorm_multi(table, partials)
+            bound = self._max_grad_norm if self._max_grad_norm is not None else math.inf
+            hip_ops.adam_multi_clip(table, partials, bound, float(group["lr"]), b1, b2, group["eps"],
+                                    group["weight_decay"], self._host_step[gi], total_norm=norm)
+            norms.append(norm)
+        if norms:
+            self._set_norms(norms)
         self._steps_dirty = True
         return None
 
@@ -107,6 +167,7 @@ class TableAdam(torch.optim.Adam):
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
         self._tables.clear()
+        self._partials.clear()
         self._sig.clear()
         self._host_step = [-1] * len(self.param_groups)
         self._steps_dirty = False

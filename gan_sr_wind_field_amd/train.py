@@ -159,9 +159,15 @@ def train(cfg, dataset_train, dataset_validation, x, y):
                     gan.save_model(cfg.env.this_runs_folder, epoch, it)
                 if lead and it % cfg_t.log_period == 0:
                     losses = _scalars(gan.get_G_train_loss_dict_ref())
-                    train_logger.info(f"it {it} " + " ".join(f"{k}: {v:.6g}" for k, v in losses.items()))
+                    norms = {}
+                    if cfg.grad_clip.log_grad_norms:  # ([GRAD_CLIP]: pre-clip norms, read from the device only here)
+                        norms = _scalars({k: v for k, v in gan.get_grad_norms().items() if v is not None})
+                    train_logger.info(f"it {it} " + " ".join(f"{k}: {v:.6g}" for k, v in losses.items())
+                                      + "".join(f" grad_norm_{k}: {v:.6g}" for k, v in norms.items()))
                     if tb is not None:
                         tb.add_scalars("G_loss/train", losses, it)
+                        if norms:
+                            tb.add_scalars("grad_norm/train", norms, it)
                 if dataloader_val is None or it % cfg_t.val_period != 0:
                     continue
                 _validate(cfg, gan, dataloader_val, dataset_train, it, tb, status_logger, lead)

@@ -462,6 +462,19 @@ typedef struct wsr_adam_job {
  *  exp_avg / exp_avg_sq follow torch's to the last bits instead of to 1e-5)                                           */
 int wsr_adam_multi(const wsr_adam_job_t* jobs_dev, int32_t n_jobs, double lr, double beta1, double beta2, double eps,
                    double weight_decay, int32_t step, void* stream);
+/* additive - gradient-norm clipping over the same job table (torch.nn.utils.clip_grad_norm_ in front of the Adam
+ * step, L2 norm over every gradient of the table), two launches and no host sync:
+ * wsr_grad_sqnorm_multi: partials[job] = sum of g^2 over the job's chunk (n_jobs floats; one workgroup per job, fixed
+ *   summation order: the same bits from run to run).
+ * wsr_adam_multi_clip: total = sqrt(sum of partials) (every workgroup sums them in the same order), coef =
+ *   min(1, max_norm / (total + 1e-6)); per element g *= coef, written back to the job's gradient (the `g` of the
+ *   table is updated in place), then wsr_adam_multi's update on the scaled g.  max_norm = +inf measures only: coef 1,
+ *   the gradients are not written and the update is wsr_adam_multi's bit for bit.  *total_norm_out (device, may be
+ *   NULL) = the pre-clip total.  A non-finite total gives a NaN / zero coefficient, as in torch.                    */
+int wsr_grad_sqnorm_multi(const wsr_adam_job_t* jobs_dev, int32_t n_jobs, float* partials, void* stream);
+int wsr_adam_multi_clip(const wsr_adam_job_t* jobs_dev, int32_t n_jobs, const float* partials, double max_norm,
+                        double lr, double beta1, double beta2, double eps, double weight_decay, int32_t step,
+                        float* total_norm_out, void* stream);
 
 /* ABI 9 - train-mode statistics of ALL batch groups of a BatchNorm3d layer (torch_blocks.py:20-25; the groups are the
  * reference's separate calls D(real), D(fake) of one iteration, wind_field_GAN_3D.py:247-304, batched into one pass) in four
