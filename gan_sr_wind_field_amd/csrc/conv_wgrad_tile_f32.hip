@@ -255,6 +255,10 @@ int launch_wgf(WgfArgs& a, int n_parts, int* plan, hipStream_t st) {
   int S = 256 / combos;  // ONE round of workgroups over the 256 CUs (a 257th workgroup would double the launch time)
   if (S > a.ntiles) S = a.ntiles;
   if (S < 1) S = 1;
+  if (WSR_ENV_SET("WSR_WGRAD_S")) {  // tuning / test aid, as in the bf16 planner (applies to the plan call too)
+    const int v = WSR_ENV_RAW("WSR_WGRAD_S");
+    if (v >= 1 && v <= a.ntiles) S = v;
+  }
   a.S = S;
   if (plan) { *plan = S; return 0; }
   if (a.part_stride > 0 && n_parts != S) return WSR_EINVAL;  // the caller sized `parts` for another split

@@ -40,7 +40,18 @@ enum wsr_error {
 };
 
 /* Geometry of one 3-D convolution.  X/Y/Z naming follows the reference
- * (tensor dims 2,3,4; Z = vertical levels, contiguous, never up-scaled). */
+ * (tensor dims 2,3,4; Z = vertical levels, contiguous, never up-scaled).
+ *
+ * Channel windows.  A kernel reads only whole 16-byte pieces (8 bf16 or 4 fp32
+ * channels) that overlap the window it is given: [in_off, in_off+Cin) of the
+ * input, [out_off, out_off+Cout) of dy in the gradients.  A piece may extend past
+ * the window's last channel (Cout not a multiple of the piece); the buffer must
+ * hold it, and those channels do not change the result.  Channels outside those
+ * pieces are never read.  A kernel writes nothing outside [out_off, out_off+Cout)
+ * of its output (the produced window: [in_off, in_off+Cin) of dx in an input
+ * gradient), and nothing past the end of any tensor; fp32 planar outputs, packed
+ * filter gradients and split copies are written only inside their extents.
+ * tests/kernel_bounds.py (Guarded) checks the write rule bit for bit. */
 typedef struct wsr_conv {
   int32_t dtype;                 /* wsr_dtype of activations and packed filters */
   int32_t B;                     /* batch                                         */

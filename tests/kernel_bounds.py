@@ -1,0 +1,291 @@
+"""Element-wise error bounds for the conv kernels against float64 references, and guarded output buffers.
+
+A plain helper module (like oracle_nets.py), imported by the kernel tests.
+
+References
+----------
+``ref_fwd``, ``ref_dgrad`` and ``ref_wgrad`` evaluate the operation in float64 on the CPU
+(``torch.nn.functional.conv3d`` / autograd) and return ``(ref, A)``: ``A`` is the same operation applied to
+``|operands|`` (and ``|alpha|``, ``|beta|*|res|``, ``|bias|``, ``|mask|``) - the sum of the magnitudes of every term
+that enters an element.  Tensors are logical: activations ``(B, C, X, Y, Z)``, filters ``(Cout, Cin, KX, KY, KZ)``.
+
+The bound
+---------
+For every element
+
+    |got - ref| <= rho * |ref|  +  lambda * sqrt(K) * 2^-24 * A  +  2^-100
+
+* ``rho`` = 2^-8 when the kernel stores bf16 (round to nearest of an 8-bit significand), 0 for fp32 stores.  A result
+  that is stored, read back and accumulated several times (``accumulate`` launches) pays rho once per stored value:
+  pass the sum of their magnitudes as ``rho_mag``.
+* ``K`` is the number of products in the element: taps * Cin (forward), taps * Cout (input gradient),
+  B * voxels (filter gradient), plus ``n_parts`` for an ordered reduce of split copies or atomics.
+* ``lambda`` = 16, one constant for every kernel and test (never tuned per test).
+
+Ratios near 1 on bf16 outputs are expected, not a near-failure.  Rounding to bf16 moves a value by up to 2^-8 of
+itself (half an ulp just above a power of two), and that is nearly all of the bound wherever the accumulation term is
+small: the bf16 checks are in effect a half-ulp test of the stored result, measured at 0.97-0.99 of the bound on the
+MI355X.  They are still sound - the fp32 accumulation error must fit the lambda term on top - and deterministic.  fp32
+outputs and filter gradients (rho = 0) sit at a few hundredths of the bound or less.  Neither observation is a reason
+to change lambda.
+
+Why it holds.  The test operands are exact in bf16, so every product - bf16 x bf16 in the bf16 kernels, bf16-exact
+fp32 x fp32 in the fp32 kernels - is exact in fp32.  The bf16 MFMAs add those exact products into fp32 accumulators;
+the fp32 MFMA is a k-ordered ``fmaf`` chain.  Split partial sums, float atomics and the ordered reduce of split copies
+are further fp32 additions, the epilogue (bias, alpha, beta * res, the LeakyReLU / Dropout3d scales) a few more
+roundings.  Each of those roundings contributes at most 2^-24 times a partial sum, itself at most A.  The worst case
+is gamma_K ~ K * 2^-24 * A; rounding errors of independent operands behave like a random walk, so the realistic bound
+is C * sqrt(K) * 2^-24 * A, and lambda = 16 leaves a wide margin over C.  A bf16 store adds at most 2^-8 of the stored
+value.  LeakyReLU is 1-Lipschitz, so an error in front of it passes through at most unchanged.  The 2^-100 only keeps
+the bound positive where ref and A are both zero.
+
+A kernel bug that drops one tap at one voxel, loses one split or misplaces one channel chunk changes the elements it
+touches by a sizable fraction of A / sqrt(K), far above the bound; a whole-tensor relative L2 check averages such an
+error over every element and can miss it.
+
+Guarded buffers
+---------------
+``Guarded`` allocates a tensor as a view inside a larger allocation.  The guard bands before and after it, and the
+channels outside the channel window the kernel may write, hold a sentinel (a NaN payload for fp32, a fixed finite
+pattern for bf16); ``assert_guards_intact`` compares them bit for bit.
+"""
+import math
+
+import torch
+import torch.nn.functional as F
+
+LAMBDA = 16.0
+U_FP32 = 2.0 ** -24
+RHO_BF16 = 2.0 ** -8
+TINY = 2.0 ** -100
+
+
+def rho_for(dt) -> float:
+    """rho of a kernel that stores ``dt``"""
+    return RHO_BF16 if dt == torch.bfloat16 else 0.0
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# float64 references
+# ---------------------------------------------------------------------------------------------------------------------
+
+def _d(t):
+    return None if t is None else t.detach().to(torch.float64).cpu()
+
+
+def up2(x):
+    """nearest x(2,2,1) up-sampling of (B, C, X, Y, Z)"""
+    return x.repeat_interleave(2, dim=2).repeat_interleave(2, dim=3)
+
+
+def fold2(x):
+    """adjoint of ``up2``: sum of each 2 x 2 block in x-y"""
+    B, C, X, Y, Z = x.shape
+    return x.reshape(B, C, X // 2, 2, Y // 2, 2, Z).sum(dim=(3, 5))
+
+
+def _win(t, win):
+    return t if win is None else t[:, win[0]:win[0] + win[1]]
+
+
+def _conv_slab(x, w, pad, xs):
+    """stride-1 conv3d of x (B, C, X, Y, Z) with zero padding ``pad``; ``xs`` = (x0, x1): only output x-planes
+    [x0, x1) (the input slab they read plus its halo)"""
+    if xs is None:
+        return F.conv3d(x, w, None, 1, tuple(pad))
+    kx = w.shape[2]
+    xp = F.pad(x, (pad[2], pad[2], pad[1], pad[1], pad[0], pad[0]))
+    return F.conv3d(xp[:, :, xs[0]:xs[1] + kx - 1], w, None, 1, 0)
+
+
+def ref_fwd(x, w, pad, *, ups=False, bias=None, act=False, slope=0.2, chan_scale=None, alpha=1.0, res=None, beta=0.0,
+            in_win=None, xs=None):
+    """y = alpha * s * lrelu(conv(up?(x), w) + bias) + beta * res  (the forward epilogue order of ``wsr_epilogue_t``).
+    ``in_win`` = (off, C): channels of x that enter; ``chan_scale`` (B, Cout); ``xs``: output x-planes [x0, x1) only
+    (``res`` then covers those planes).  Returns (ref, A)."""
+    x, w = _win(_d(x), in_win), _d(w)
+    if ups:
+        x = up2(x)
+    v = _conv_slab(x, w, pad, xs)
+    a = _conv_slab(x.abs(), w.abs(), pad, xs)
+    if bias is not None:
+        b = _d(bias).view(1, -1, 1, 1, 1)
+        v, a = v + b, a + b.abs()
+    if act:
+        v = F.leaky_relu(v, slope)
+    if chan_scale is not None:
+        s = _d(chan_scale).view(v.shape[0], v.shape[1], 1, 1, 1)
+        v, a = v * s, a * s.abs()
+    v, a = alpha * v, abs(alpha) * a
+    if res is not None:
+        r = _d(res)
+        v, a = v + beta * r, a + abs(beta) * r.abs()
+    return v, a
+
+
+def dgrad_filter(w):
+    """(Cout, Cin, KX, KY, KZ) -> the filter of the input gradient as a forward conv over dy: (Cin, Cout, flipped)"""
+    return w.transpose(0, 1).flip(2, 3, 4)
+
+
+def ref_dgrad(gy, w, pad, *, ups=False, alpha=1.0, mask_y=None, slope=0.2, keep=None, acc=None, xs=None):
+    """dx = (alpha * conv^T(gy, w) [+ acc]) * lrelu'(mask_y) * keep  for a stride-1 conv with padding ``pad``.
+    ``ups``: the conv read up2(x) - dx is then at x's (coarse) resolution, the 2 x 2 fold of the fine gradient;
+    ``mask_y`` (B, Cin, ...) the saved output whose sign selects 1 or ``slope``, ``keep`` (B, Cin) the Dropout3d
+    channel scale; ``acc`` a value added before the mask (accumulate launches); ``xs`` dx x-planes [x0, x1) only
+    (not with ``ups``).  Returns (ref, A)."""
+    gy, w = _d(gy), _d(w)
+    k = w.shape[2:]
+    tp = tuple(kk - 1 - p for kk, p in zip(k, pad))
+    wt = dgrad_filter(w)
+    v = alpha * _conv_slab(gy, wt, tp, xs)
+    a = abs(alpha) * _conv_slab(gy.abs(), wt.abs(), tp, xs)
+    if ups:
+        v, a = fold2(v), fold2(a)
+    if acc is not None:
+        v, a = v + _d(acc), a + _d(acc).abs()
+    if mask_y is not None:
+        m = torch.where(_d(mask_y) > 0, 1.0, slope).to(torch.float64)
+        v, a = v * m, a * m.abs()
+    if keep is not None:
+        s = _d(keep).view(v.shape[0], v.shape[1], 1, 1, 1)
+        v, a = v * s, a * s.abs()
+    return v, a
+
+
+def ref_wgrad(x, gy, k, pad, *, ups=False, in_win=None):
+    """dw[n, c, tap] = sum_{b, v} gy[b, n, v] * up?(x)[b, c, v + tap - pad] (stride 1).  Returns (ref, A) in the master
+    layout (Cout, Cin, KX, KY, KZ)."""
+    x, gy = _win(_d(x), in_win), _d(gy)
+    if ups:
+        x = up2(x)
+    out = []
+    for xx, gg in ((x, gy), (x.abs(), gy.abs())):
+        w = torch.zeros((gg.shape[1], xx.shape[1]) + tuple(k), dtype=torch.float64, requires_grad=True)
+        (g,) = torch.autograd.grad(F.conv3d(xx, w, None, 1, tuple(pad)), w, gg)
+        out.append(g)
+    return out[0], out[1]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the bound and its check
+# ---------------------------------------------------------------------------------------------------------------------
+
+def bound(ref, A, K, rho, rho_mag=None):
+    """rho * |ref| + LAMBDA * sqrt(K) * 2^-24 * A + 2^-100 (``rho_mag`` replaces |ref| when several stored values
+    were rounded: the sum of their magnitudes)"""
+    mag = ref.abs() if rho_mag is None else rho_mag
+    return rho * mag + LAMBDA * math.sqrt(K) * U_FP32 * A + TINY
+
+
+#: worst |err| / bound seen per label (up to its first "[") in this process: the calibration table of a test log
+WORST: dict = {}
+
+
+def _coords(idx, shape, kind):
+    c = []
+    for s in reversed(shape):
+        c.append(idx % s)
+        idx //= s
+    c = tuple(reversed(c))
+    if kind == "filter":  # (n, c, kx, ky, kz) -> (n, tap, c)
+        n, ci, kx, ky, kz = c
+        return f"(n={n}, tap={(kx * shape[3] + ky) * shape[4] + kz}, c={ci})"
+    return "(b={}, c={}, x={}, y={}, z={})".format(*c) if len(c) == 5 else str(c)
+
+
+def check_within(got, ref, bnd):
+    """(number of violations, worst |err| / bound, flat indices of the worst elements, ratio tensor); a non-finite
+    element of ``got`` counts as an infinite ratio"""
+    got = got.detach().to(torch.float64).cpu()
+    assert got.shape == ref.shape, (tuple(got.shape), tuple(ref.shape))
+    err = (got - ref).abs()
+    ratio = torch.where(torch.isfinite(got), err / bnd, torch.full_like(err, math.inf))
+    flat = ratio.flatten()
+    bad = int((flat > 1.0).sum())
+    worst = float(flat.max()) if flat.numel() else 0.0
+    top = torch.topk(flat, min(5, flat.numel())).indices.tolist() if flat.numel() else []
+    return bad, worst, top, ratio
+
+
+def assert_within(got, ref, bnd, label, kind="act"):
+    """every element of ``got`` within ``bnd`` of ``ref``; the message names the violating elements' coordinates
+    ((b, c, x, y, z) of activations, (n, tap, c) of filter gradients ``kind="filter"``).  Returns the worst ratio."""
+    bad, worst, top, ratio = check_within(got, ref, bnd)
+    key = label.split("[")[0]
+    WORST[key] = max(WORST.get(key, 0.0), worst)
+    if bad:
+        flat_g = got.detach().to(torch.float64).cpu().flatten()
+        flat_r, flat_b, flat_q = ref.flatten(), bnd.flatten(), ratio.flatten()
+        lines = [f"  {_coords(i, tuple(ref.shape), kind)}: got {float(flat_g[i]):.9g} ref {float(flat_r[i]):.9g} "
+                 f"bound {float(flat_b[i]):.3g} ratio {float(flat_q[i]):.3g}" for i in top]
+        raise AssertionError(f"{label}: {bad} of {ref.numel()} elements outside the bound, worst |err|/bound "
+                             f"{worst:.3g}; worst elements:\n" + "\n".join(lines))
+    print(f"[bound] {label}: worst |err|/bound {worst:.3g}")
+    return worst
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# guarded buffers
+# ---------------------------------------------------------------------------------------------------------------------
+
+GUARD_ELEMS = 1024
+_SENTINEL_BITS = {torch.float32: 0x7FE5A5A5, torch.bfloat16: 0x5A5A}  # (fp32: a quiet NaN payload; bf16: ~1.5e16)
+_INT_VIEW = {torch.float32: torch.int32, torch.bfloat16: torch.int16}
+
+
+class Guarded:
+    """``t``: a tensor of ``shape``/``dtype`` inside a larger allocation on ``device``.  ``window`` = (off, C): only
+    channels [off, off + C) of the last axis belong to the kernel's output; the rest of each row and ``guard``
+    elements before and after the tensor hold the sentinel.  ``fill``: initial value of the window (scalar, or a
+    tensor of the window's shape), else the sentinel; ``outside``: a value for the channels outside the window instead
+    of the sentinel (they are compared bit for bit all the same)."""
+
+    def __init__(self, shape, dtype, device, window=None, fill=None, guard=GUARD_ELEMS, outside=None):
+        shape = tuple(shape)
+        n = math.prod(shape)
+        self.dtype, self.guard, self.shape = dtype, guard, shape
+        self.base = torch.empty(guard + n + guard, dtype=dtype, device=device)
+        self.base.view(_INT_VIEW[dtype]).fill_(_SENTINEL_BITS[dtype])
+        self.t = self.base[guard:guard + n].view(shape)
+        ctot = shape[-1]
+        self.win = (0, ctot) if window is None else tuple(window)
+        assert 0 <= self.win[0] and self.win[0] + self.win[1] <= ctot
+        if outside is not None:
+            self.t[...] = outside
+        if fill is not None:
+            self.window_view()[...] = fill
+        keep = torch.ones(n + 2 * guard, dtype=torch.bool)
+        keep[guard:guard + n].view(-1, ctot)[:, self.win[0]:self.win[0] + self.win[1]] = False
+        self.mask = keep.to(device)
+        self.snap = self.base.view(_INT_VIEW[dtype])[self.mask].clone()
+
+    def window_view(self):
+        return self.t[..., self.win[0]:self.win[0] + self.win[1]]
+
+    def violations(self):
+        """positions (relative to the tensor's first element) of guard elements that changed"""
+        now = self.base.view(_INT_VIEW[self.dtype])[self.mask]
+        diff = (now != self.snap).nonzero().flatten()
+        return (self.mask.nonzero().flatten()[diff] - self.guard).cpu()
+
+
+def assert_guards_intact(*bufs, label=""):
+    """every guard element of every ``Guarded`` in ``bufs`` holds its sentinel, bit for bit"""
+    for i, g in enumerate(bufs):
+        pos = g.violations()
+        if pos.numel():
+            n = math.prod(g.shape)
+            where = []
+            for p in pos[:5].tolist():
+                if p < 0:
+                    where.append(f"{-p} elements before the tensor")
+                elif p >= n:
+                    where.append(f"{p - n} elements past its end")
+                else:
+                    c = []
+                    for s in reversed(g.shape):
+                        c.append(p % s)
+                        p //= s
+                    where.append(f"index {tuple(reversed(c))} outside the channel window {g.win}")
+            raise AssertionError(f"{label} buffer {i}: {pos.numel()} guard elements written: " + "; ".join(where))

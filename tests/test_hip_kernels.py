@@ -15,6 +15,7 @@ import torch.nn.functional as F
 
 from conftest import reload_wsr_env, rel_l2
 from cases import CONV_CASES
+import kernel_bounds as kb
 
 pytestmark = pytest.mark.gpu
 
@@ -39,6 +40,16 @@ def to_ndhwc(x, ctot, off, dt):
 
 def from_ndhwc(buf, off, C_):
     return buf[..., off:off + C_].permute(0, 4, 1, 2, 3).float().cpu()
+
+
+def _slabs(xo, macs):
+    """x-plane ranges of the output the float64 reference covers: all planes, or - where a full reference would take
+    seconds on the host - the first four and the last four (the first and the ragged last x tile)"""
+    return [None] if macs < 4e9 or xo <= 8 else [(0, 4), (xo - 4, xo)]
+
+
+def _xs(t, xs):
+    return t if xs is None else t[:, :, xs[0]:xs[1]]
 
 
 def packed_master(w):
@@ -272,7 +283,8 @@ def test_strided_input_gradient_in_parity_form(hip, case, batched):
     assert tuple(y.shape[2:]) == oxyz
     (dx_ref,) = torch.autograd.grad(y, x, gy)
     gb = to_ndhwc(gy, cout, 0, dt)
-    dxb = torch.full((B,) + ixyz + (cin,), float("nan"), dtype=dt, device=DEV)
+    dxg = kb.Guarded((B,) + ixyz + (cin,), dt, DEV, fill=float("nan"))
+    dxb = dxg.t
     for zc in range(sz):
         kzp = 3 if sz == 1 else (1 if zc == 0 else 2)
         wp = torch.empty(4, cin, cout, 2, 2, kzp, device=DEV)
@@ -295,6 +307,12 @@ def test_strided_input_gradient_in_parity_form(hip, case, batched):
     dx = from_ndhwc(dxb, 0, cin)
     assert not torch.isnan(dx).any()  # every lattice was written
     assert rel_l2(dx, dx_ref) < 4e-3
+    kb.assert_guards_intact(dxg, label=str(case))
+    x64 = torch.zeros((B, cin) + ixyz, dtype=torch.float64, requires_grad=True)
+    (r64,) = torch.autograd.grad(F.conv3d(x64, w.double(), None, (2, 2, sz), 1), x64, gy.double())
+    xa = torch.zeros((B, cin) + ixyz, dtype=torch.float64, requires_grad=True)
+    (A,) = torch.autograd.grad(F.conv3d(xa, w.double().abs(), None, (2, 2, sz), 1), xa, gy.double().abs())
+    kb.assert_within(dx, r64, kb.bound(r64, A, 12 * cout, kb.RHO_BF16), f"strided dgrad[{case} {batched}]")
 
 
 @pytest.mark.parametrize("B,N,K", [(1, 100, 131072), (2, 100, 20480), (5, 7, 8192)])
@@ -371,7 +389,8 @@ def test_subpixel_upconv_forward_and_dgrad(hip, shape, batched):
     for ph in range(4):
         o.pack_filter_frag(wp[ph], out=frag[ph * n:(ph + 1) * n])
     ctot = cout + 8  # the last up-conv writes a window of the wider concat buffer
-    yb = torch.full((B, 2 * X, 2 * Y, Z, ctot), float("nan"), dtype=dt, device=DEV)
+    yg = kb.Guarded((B, 2 * X, 2 * Y, Z, ctot), dt, DEV, window=(0, cout), outside=float("nan"), fill=float("nan"))
+    yb = yg.t
     bd = bias.to(DEV)
     if batched:
         d = o.make_desc(o.ConvGeom(cin, cout, (2, 2, 3), (1, 1, 1), (1, 1, 1)), dt, B, (X, Y, Z), cin, 0, ctot, 0,
@@ -385,6 +404,7 @@ def test_subpixel_upconv_forward_and_dgrad(hip, shape, batched):
             assert o.conv_fwd_tile(d, xb, frag[ph * n:(ph + 1) * n], yb, bias=bd, act=True, slope=0.2)
     y = from_ndhwc(yb, 0, cout)
     assert torch.isnan(yb[..., cout:].float()).all()  # nothing outside the window was written
+    kb.assert_guards_intact(yg, label=str(shape))
     xr = x.clone().requires_grad_(True)
     up = F.interpolate(xr, scale_factor=(2, 2, 1), mode="nearest")
     y_ref = F.leaky_relu(F.conv3d(up, w, bias, padding=1), 0.2)
@@ -396,17 +416,42 @@ def test_subpixel_upconv_forward_and_dgrad(hip, shape, batched):
         xp = F.pad(x, (1, 1, 1 - b, b, 1 - a, a))
         y_par[:, :, a::2, b::2] = F.leaky_relu(F.conv3d(xp, wpr[ph], bias), 0.2)
     assert rel_l2(y, y_par.detach()) < 4e-3
+    r64 = torch.empty(y_ref.shape, dtype=torch.float64)
+    A = torch.empty_like(r64)
+    for ph in range(4):
+        a, b = ph >> 1, ph & 1
+        xp = F.pad(x, (1, 1, 1 - b, b, 1 - a, a))
+        r64[:, :, a::2, b::2], A[:, :, a::2, b::2] = kb.ref_fwd(xp, wpr[ph], (0, 0, 0), bias=bias, act=True)
+    kb.assert_within(y, r64, kb.bound(r64, A, 12 * cin, kb.RHO_BF16), f"subpixel fwd[{shape} {batched}]")
     # input gradient
     gy = torch.randn_like(y_ref).to(dt).float()
     (dx_ref,) = torch.autograd.grad(F.conv3d(up, w, None, padding=1), xr, gy)
     gb = to_ndhwc(gy, ctot, 0, dt)
-    dxb = torch.full((B, X, Y, Z, cin), float("nan"), dtype=dt, device=DEV)
+    dxg = kb.Guarded((B, X, Y, Z, cin), dt, DEV, fill=float("nan"))
+    dxb = dxg.t
     for ph in range(4):
         a, b = ph >> 1, ph & 1
         d = o.make_desc(o.ConvGeom(cin, cout, (2, 2, 3), (1, 1, 1), (1 - a, 1 - b, 1)), dt, B, (X, Y, Z), cin, 0,
                         ctot, 0, lat=(a, b, 0))
         assert o.conv_dgrad_tile(d, gb, o.pack_filter_frag(wp[ph].contiguous(), transpose=True), dxb, accumulate=ph > 0)
-    assert rel_l2(from_ndhwc(dxb, 0, cin), dx_ref) < 1.5e-2
+    got = from_ndhwc(dxb, 0, cin)
+    assert rel_l2(got, dx_ref) < 1.5e-2
+    kb.assert_guards_intact(dxg, label=f"subpixel dgrad {shape}")
+    # float64 of the four parity launches with the rounded parity filters; every launch stores its running sum in
+    # bf16 and the next one reads it back: rho is paid on each of the four stored partial sums
+    r64 = torch.zeros((B, cin, X, Y, Z), dtype=torch.float64)
+    A = torch.zeros_like(r64)
+    mag = torch.zeros_like(r64)
+    for ph in range(4):
+        a, b = ph >> 1, ph & 1
+        wv, gv = wpr[ph].double(), gy[:, :, a::2, b::2].double()
+        for total, wt, gt in ((r64, wv, gv), (A, wv.abs(), gv.abs())):
+            xv = torch.zeros((B, cin, X, Y, Z), dtype=torch.float64, requires_grad=True)
+            (dph,) = torch.autograd.grad(F.conv3d(F.pad(xv, (1, 1, 1 - b, b, 1 - a, a)), wt), xv, gt)
+            total += dph
+        mag += r64.abs()  # the running sum this launch stores
+    kb.assert_within(got, r64, kb.bound(r64, A, 4 * 12 * cout + 4, kb.RHO_BF16, rho_mag=mag),
+                     f"subpixel dgrad[{shape}]")
 
 
 @pytest.mark.parametrize("shape", [(2, 32, 48, 8, 16, 16), (1, 128, 128, 8, 8, 32), (1, 64, 64, 5, 6, 10)])
@@ -434,14 +479,20 @@ def test_subpixel_upconv_filter_gradient(hip, shape):
         d = o.make_desc(o.ConvGeom(cin, cout, (2, 2, 3), (1, 1, 1), (1 - a, 1 - b, 1)), dt, B, (X, Y, Z), cin, 0,
                         cout + 16, 0, lat=(a, b, 0))
         n = o.conv_wgrad_nparts(d)
-        parts = torch.full((n, cout, 12, cin), float("nan"), dtype=torch.float32, device=DEV)
+        pg = kb.Guarded((n, cout, 12, cin), torch.float32, DEV)
+        parts = pg.t
         o.conv_wgrad_parts(d, xb, gb, parts, n)
         jobs.append((parts[0], dwp[ph], 1.0, n, parts[0].numel()))
-        keep.append(parts)
+        keep.append(pg)
     o.unpack_wgrad_reduce_multi(o.unpack_job_table(jobs))
-    dw = torch.empty(cout, cin, 3, 3, 3, device=DEV)
+    dwg = kb.Guarded((cout, cin, 3, 3, 3), torch.float32, DEV)
+    dw = dwg.t
     o.subpixel_unfold(dwp, dw)
     assert rel_l2(dw.cpu(), dw_ref) < 1e-3
+    kb.assert_guards_intact(dwg, *keep, label=str(shape))
+    r64, A = kb.ref_wgrad(x, gy, (3, 3, 3), (1, 1, 1), ups=True)
+    K = 4 * B * X * Y * Z + 4 * max(p.shape[0] for p in keep) + 4
+    kb.assert_within(dw.cpu(), r64, kb.bound(r64, A, K, 0.0), f"subpixel wgrad[{shape}]", kind="filter")
 
 
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
@@ -631,7 +682,8 @@ def test_wgrad_tile_kernel_bf16(hip, name, cin, cout, k, xyz, B, ups):
     xb = to_ndhwc(x, cin + 16, 8, dt)
     gb = to_ndhwc(gy, cout_p + 8, 8, dt)
     d = o.make_desc(geom, dt, B, xyz, cin + 16, 8, cout_p + 8, 8)
-    dwp = torch.zeros((cout, geom.taps, cin), dtype=torch.float32, device=DEV)
+    dwg = kb.Guarded((cout, geom.taps, cin), torch.float32, DEV, fill=0.0)
+    dwp = dwg.t
     o.conv_wgrad(d, xb, gb, dwp)
     dw = torch.zeros((cout, cin) + tuple(k), dtype=torch.float32, device=DEV)
     o.unpack_wgrad(dwp, dw)
@@ -640,6 +692,10 @@ def test_wgrad_tile_kernel_bf16(hip, name, cin, cout, k, xyz, B, ups):
         xr = x.repeat_interleave(2, dim=2).repeat_interleave(2, dim=3)
     ref = _cpu_wgrad(xr, gy, k, p)
     assert rel_l2(dw.cpu(), ref) < 2e-5, name  # fp32 accumulation of exact bf16 products
+    kb.assert_guards_intact(dwg, label=name)
+    r64, A = kb.ref_wgrad(x, gy, k, p, ups=ups)
+    K = B * math.prod(oxyz) + o.conv_wgrad_nparts(d)
+    kb.assert_within(dw.cpu(), r64, kb.bound(r64, A, K, 0.0), f"wgrad bf16 atomic[{name}]", kind="filter")
 
 
 @pytest.mark.parametrize("nf,gc,B,xyz", [(16, 8, 2, (6, 7, 9)), (128, 32, 1, (8, 8, 32))],
@@ -660,14 +716,19 @@ def test_wgrad_dense_block_fused(hip, nf, gc, B, xyz):
     cin_w = nf + (nconv - 1) * gc
     geom = o.ConvGeom(cin_w, nconv * gc, (3, 3, 3))
     d = o.make_desc(geom, dt, B, xyz, dense, 0, dense, nf)
-    dwp = torch.zeros((nconv * gc, 27, cin_w), dtype=torch.float32, device=DEV)
+    dwg = kb.Guarded((nconv * gc, 27, cin_w), torch.float32, DEV, fill=0.0)
+    dwp = dwg.t
     o.conv_wgrad_tri(d, xb, gb, dwp, nf, gc)
+    K = B * math.prod(xyz) + o.conv_wgrad_nparts(d, nf, gc)
     for i in range(nconv):
         ci = nf + i * gc
         dw = torch.zeros((gc, ci, 3, 3, 3), dtype=torch.float32, device=DEV)
         o.unpack_wgrad(dwp[i * gc:(i + 1) * gc], dw)
         ref = _cpu_wgrad(x[:, :ci], g[:, nf + i * gc:nf + (i + 1) * gc], (3, 3, 3), (1, 1, 1))
         assert rel_l2(dw.cpu(), ref) < 2e-5, i
+        r64, A = kb.ref_wgrad(x[:, :ci], g[:, nf + i * gc:nf + (i + 1) * gc], (3, 3, 3), (1, 1, 1))
+        kb.assert_within(dw.cpu(), r64, kb.bound(r64, A, K, 0.0), f"tri[{nf} {gc} conv {i}]", kind="filter")
+    kb.assert_guards_intact(dwg, label="tri")
 
 
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float32], ids=["bf16", "fp32"])
@@ -687,7 +748,8 @@ def test_conv_tile_kernels_vs_golden(golden, hip, case, dt):
     xb = to_ndhwc(x, in_ctot, in_off, dt)
     wm = packed_master(w)
     d = o.make_desc(o.ConvGeom(cin_p, cout, k, s, p), dt, B, xyz, in_ctot, in_off, out_ctot, out_off)
-    yb = torch.full((B, d.Xo, d.Yo, d.Zo, out_ctot), 7.0, dtype=dt, device=DEV)
+    yg = kb.Guarded((B, d.Xo, d.Yo, d.Zo, out_ctot), dt, DEV, window=(out_off, cout), outside=7.0, fill=7.0)
+    yb = yg.t
     tol_ref, tol_same = (1e-5, 1e-5) if f32 else (1e-2, 4e-3)
     if f32 and k == (1, 1, 1):  # (1x1x1 in fp32 stays on the generic kernel)
         assert not o.conv_fwd_tile(d, xb, o.pack_filter_frag(wm, dtype=dt), yb, bias=b, act=act, slope=0.2)
@@ -697,6 +759,12 @@ def test_conv_tile_kernels_vs_golden(golden, hip, case, dt):
     assert rel_l2(y, y_ref) < tol_ref
     assert float((yb[..., :out_off].float() - 7.0).abs().max()) == 0.0
     assert float((yb[..., out_off + cout:].float() - 7.0).abs().max()) == 0.0
+    kb.assert_guards_intact(yg, label=name)
+    # element-wise against float64 of the operands the kernel multiplies (bf16: the rounded fixtures)
+    xo, wo = (x, w) if f32 else (x.bfloat16().float(), w.bfloat16().float())
+    taps = k[0] * k[1] * k[2]
+    r64, A = kb.ref_fwd(xo, wo, p, bias=b, act=act)
+    kb.assert_within(y, r64, kb.bound(r64, A, taps * cin, kb.rho_for(dt)), f"tile fwd {dt_name(dt)}[golden {name}]")
     if not f32:
         y2 = F.conv3d(x.bfloat16().float(), w.bfloat16().float(), b.cpu() if bias else None, s, p)
         y2 = F.leaky_relu(y2, 0.2) if act else y2
@@ -711,16 +779,30 @@ def test_conv_tile_kernels_vs_golden(golden, hip, case, dt):
         o.lrelu_bwd_(gb, out_off, to_ndhwc(y_ref, out_ctot, out_off, dt), out_off, cout_p, 0.2)
     wft = o.pack_filter_frag(wm, transpose=True, dtype=dt)
     dd = o.make_desc(o.ConvGeom(cin, cout_p, k, s, p), dt, B, xyz, in_ctot, in_off, out_ctot, out_off)
-    dxb = torch.full((B,) + tuple(xyz) + (in_ctot,), 3.0, dtype=dt, device=DEV)
+    dxg = kb.Guarded((B,) + tuple(xyz) + (in_ctot,), dt, DEV, window=(in_off, cin), outside=3.0, fill=3.0)
+    dxb = dxg.t
     assert o.conv_dgrad_tile(dd, gb, wft, dxb)
     assert rel_l2(from_ndhwc(dxb, in_off, cin), dx_ref) < tol_ref
     assert float((dxb[..., :in_off].float() - 3.0).abs().max()) == 0.0
+    kb.assert_guards_intact(dxg, label=name)
+    g_in = from_ndhwc(gb, out_off, cout)  # the (masked, stored) output gradient the kernel reads
+    r64, A = kb.ref_dgrad(g_in, wo, p)
+    kb.assert_within(from_ndhwc(dxb, in_off, cin), r64, kb.bound(r64, A, taps * cout, kb.rho_for(dt)),
+                     f"tile dgrad {dt_name(dt)}[golden {name}]")
     assert o.conv_dgrad_tile(dd, gb, wft, dxb, accumulate=True)
     assert rel_l2(from_ndhwc(dxb, in_off, cin), 2 * dx_ref) < tol_ref
-    dxp = torch.zeros((B, cin) + tuple(xyz), dtype=torch.float32, device=DEV)
+    kb.assert_guards_intact(dxg, label=f"{name} accumulate")
+    # dx = stored(d) + d: one stored value |d| read back, then |2d| stored; fresh sums of A twice
+    kb.assert_within(from_ndhwc(dxb, in_off, cin), 2 * r64,
+                     kb.bound(2 * r64, 2 * A, taps * cout, kb.rho_for(dt), rho_mag=3 * r64.abs()),
+                     f"tile dgrad {dt_name(dt)}[golden {name} accumulate]")
+    dxpg = kb.Guarded((B, cin) + tuple(xyz), torch.float32, DEV, fill=0.0)
+    dxp = dxpg.t
     dd2 = o.make_desc(o.ConvGeom(cin, cout_p, k, s, p), dt, B, xyz, cin, 0, out_ctot, out_off)
     assert o.conv_dgrad_tile(dd2, gb, wft, dxp, dx_planar=True)
     assert rel_l2(dxp.cpu(), dx_ref) < tol_ref
+    kb.assert_guards_intact(dxpg, label=f"{name} planar")
+    kb.assert_within(dxp.cpu(), r64, kb.bound(r64, A, taps * cout, 0.0), f"tile dgrad planar[golden {name} {dt_name(dt)}]")
 
 
 @pytest.mark.parametrize("name,cin,cout,k,xyz,B,ups", [
@@ -790,6 +872,10 @@ def test_conv_tile_production_geometry(hip, monkeypatch, name, cin, cout, k, xyz
     _check_tile_conv(name, cin, cout, k, xyz, B, ups)
 
 
+def dt_name(dt):
+    return "bf16" if dt == torch.bfloat16 else "fp32"
+
+
 def _check_tile_conv(name, cin, cout, k, xyz, B, ups, dt=torch.bfloat16):
     o = ops()
     tol = 4e-3 if dt == torch.bfloat16 else 2e-5  # (operands are bf16-exact in both: fp32 products are exact)
@@ -804,21 +890,36 @@ def _check_tile_conv(name, cin, cout, k, xyz, B, ups, dt=torch.bfloat16):
     oxyz = (d.Xo, d.Yo, d.Zo)
     res = torch.randn((B, cout) + oxyz, generator=gen).bfloat16().float()
     rb = to_ndhwc(res, cout_p, 0, dt)
-    yb = torch.zeros((B,) + oxyz + (cout_p + 8,), dtype=dt, device=DEV)
+    yg = kb.Guarded((B,) + oxyz + (cout_p + 8,), dt, DEV, window=(0, cout), fill=0.0)
+    yb = yg.t
     wm = packed_master(w)
     assert o.conv_fwd_tile(d, xb, o.pack_filter_frag(wm, dtype=dt), yb, res=rb, res_off=0, alpha=0.2, beta=1.0)
     xr = x.repeat_interleave(2, dim=2).repeat_interleave(2, dim=3) if ups else x
     ref = 0.2 * F.conv3d(xr, w, None, 1, p) + res
     assert rel_l2(from_ndhwc(yb, 0, cout), ref) < tol, name
+    taps = k[0] * k[1] * k[2]
+    slabs = _slabs(oxyz[0], B * math.prod(oxyz) * cin * cout * taps)
+    fam = "bf16" if dt == torch.bfloat16 else "fp32"
+    for xs in slabs:
+        r64, A = kb.ref_fwd(x, w, p, ups=ups, alpha=0.2, res=_xs(res, xs), beta=1.0, xs=xs)
+        kb.assert_within(_xs(from_ndhwc(yb, 0, cout), xs), r64, kb.bound(r64, A, taps * cin, kb.rho_for(dt)),
+                         f"tile fwd {fam}[{name} x {xs}]")
+    kb.assert_guards_intact(yg, label=name)
     # input gradient (at the fine resolution when up-sampled; the 2x2 fold is a separate kernel)
     gy = torch.randn((B, cout) + oxyz, generator=gen).bfloat16().float()
     gb = to_ndhwc(gy, cout_p + 8, 0, dt)
     dd = o.make_desc(o.ConvGeom(cin, cout_p, k, (1, 1, 1), p, upsample=ups), dt, B, xyz, cin + 8, 8, cout_p + 8, 0)
-    dxb = torch.zeros((B,) + tuple(xr.shape[2:]) + (cin + 8,), dtype=dt, device=DEV)
+    dxg = kb.Guarded((B,) + tuple(xr.shape[2:]) + (cin + 8,), dt, DEV, window=(8, cin), fill=0.0)
+    dxb = dxg.t
     assert o.conv_dgrad_tile(dd, gb, o.pack_filter_frag(wm, transpose=True, dtype=dt), dxb)
     xg = xr.clone().requires_grad_(True)
     F.conv3d(xg, w, None, 1, p).backward(gy)
     assert rel_l2(from_ndhwc(dxb, 8, cin), xg.grad) < tol, name
+    for xs in slabs:
+        r64, A = kb.ref_dgrad(gy, w, p, xs=xs)
+        kb.assert_within(_xs(from_ndhwc(dxb, 8, cin), xs), r64, kb.bound(r64, A, taps * cout, kb.rho_for(dt)),
+                         f"tile dgrad {fam}[{name} x {xs}]")
+    kb.assert_guards_intact(dxg, label=name)
 
 
 @pytest.mark.parametrize("dt,C,ctot,off,nvox", [(torch.bfloat16, 128, 128, 0, 32 * 32 * 16), (torch.bfloat16, 32, 256, 96, 1000),
@@ -1022,12 +1123,15 @@ def test_conv_slide_forward_vs_cpu(hip, name, k, xyz, B, ctot, off, bias):
     ref = F.conv3d(x, w, bv, 1, p)
     outs = []
     for _ in range(2):
-        y = torch.full((B, cout) + tuple(xyz), float("nan"), dtype=torch.float32, device=DEV)
-        assert o.conv_fwd_tile(d, xb, wf, y, bias=bv.to(DEV) if bias else None, out_planar=True)
-        outs.append(y.cpu())
+        yg = kb.Guarded((B, cout) + tuple(xyz), torch.float32, DEV)
+        assert o.conv_fwd_tile(d, xb, wf, yg.t, bias=bv.to(DEV) if bias else None, out_planar=True)
+        outs.append(yg.t.cpu())
+        kb.assert_guards_intact(yg, label=name)
     assert torch.isfinite(outs[0]).all(), name
     assert rel_l2(outs[0], ref) < 2e-5, name  # fp32 accumulation of exactly representable products
     assert torch.equal(outs[0], outs[1]), name
+    r64, A = kb.ref_fwd(x, w, p, bias=bv)
+    kb.assert_within(outs[0], r64, kb.bound(r64, A, k[0] * k[1] * cin, 0.0), f"slide fwd[{name}]")
 
 
 @pytest.mark.parametrize("name,k,xyz,B,ctot,off,drop", [
@@ -1052,7 +1156,8 @@ def test_conv_slide_input_gradient_vs_cpu(hip, name, k, xyz, B, ctot, off, drop)
     p = (k[0] // 2, k[1] // 2, 0)
     gb = to_ndhwc(gy, 16, 0, dt)
     hb = to_ndhwc(h, ctot, off, dt)
-    dxb = torch.full((B,) + tuple(xyz) + (ctot,), 7.0, dtype=dt, device=DEV)
+    dxg = kb.Guarded((B,) + tuple(xyz) + (ctot,), dt, DEV, window=(off, cin), outside=7.0, fill=7.0)
+    dxb = dxg.t
     d = o.make_desc(o.ConvGeom(cin, 16, k, (1, 1, 1), p), dt, B, xyz, ctot, off, 16, 0)
     wpad = torch.cat([w, torch.zeros((1,) + tuple(w.shape[1:]))])
     wft = o.pack_filter_frag(packed_master(wpad), transpose=True)
@@ -1068,6 +1173,9 @@ def test_conv_slide_input_gradient_vs_cpu(hip, name, k, xyz, B, ctot, off, drop)
     assert rel_l2(got, ref) < 4e-3, name  # bf16 rounding of the result
     if off:
         assert bool((dxb[..., :off] == 7.0).all()), name
+    kb.assert_guards_intact(dxg, label=name)
+    r64, A = kb.ref_dgrad(gy, w, p, mask_y=h, slope=slope, keep=keep)
+    kb.assert_within(got, r64, kb.bound(r64, A, k[0] * k[1] * cout, kb.RHO_BF16), f"slide dgrad[{name}]")
 
 
 def test_conv_tile_beyond_32_bit_element_offsets(hip):
@@ -1137,10 +1245,13 @@ def test_conv_thin_forward_vs_cpu(hip, name, cin, cout, xyz, B, in_ctot, in_off,
         ref = F.leaky_relu(ref, 0.2)
     outs = []
     for _ in range(2):
-        y = torch.full((B,) + tuple(xyz) + (out_ctot,), 7.0, dtype=dt, device=DEV)
-        assert o.conv_fwd_tile(d, xb, wf, y, bias=bv.to(DEV) if bias else None, act=act, slope=0.2)
-        outs.append(y)
+        yg = kb.Guarded((B,) + tuple(xyz) + (out_ctot,), dt, DEV, window=(out_off, cout), outside=7.0, fill=7.0)
+        assert o.conv_fwd_tile(d, xb, wf, yg.t, bias=bv.to(DEV) if bias else None, act=act, slope=0.2)
+        kb.assert_guards_intact(yg, label=name)
+        outs.append(yg.t)
     got = from_ndhwc(outs[0], out_off, cout)
+    r64, A = kb.ref_fwd(x, w, (1, 1, 1), bias=bv, act=act)
+    kb.assert_within(got, r64, kb.bound(r64, A, 27 * cin, kb.RHO_BF16), f"thin fwd[{name}]")
     assert torch.isfinite(got).all(), name
     assert rel_l2(got, ref) < 4e-3, name
     assert torch.equal(outs[0], outs[1]), name
@@ -1176,13 +1287,17 @@ def test_conv_thin_input_gradient_vs_cpu(hip, name, cin, cout, xyz, B, alpha):
     d = o.make_desc(o.ConvGeom(cin, cout, (3, 3, 3), (1, 1, 1), (1, 1, 1)), dt, B, xyz, cin, 0, cop, 0, cout=cop)
     wpad = torch.cat([w, torch.zeros((cop - cout,) + tuple(w.shape[1:]))]) if cop != cout else w
     wft = o.pack_filter_frag(packed_master(wpad), transpose=True)
-    dxb = torch.full((B,) + tuple(xyz) + (cin,), float("nan"), dtype=dt, device=DEV)
+    dxg = kb.Guarded((B,) + tuple(xyz) + (cin,), dt, DEV, fill=float("nan"))
+    dxb = dxg.t
     assert o.conv_dgrad_tile(d, gb, wft, dxb, alpha=alpha)
     xg = torch.zeros((B, cin) + tuple(xyz), requires_grad=True)
     F.conv3d(xg, w, None, 1, 1).backward(gy)
     got = from_ndhwc(dxb, 0, cin)
     assert torch.isfinite(got).all(), name
     assert rel_l2(got, alpha * xg.grad) < 4e-3, name
+    kb.assert_guards_intact(dxg, label=name)
+    r64, A = kb.ref_dgrad(gy, w, (1, 1, 1), alpha=alpha)
+    kb.assert_within(got, r64, kb.bound(r64, A, 27 * cout, kb.RHO_BF16), f"thin dgrad[{name}]")
 
 
 @pytest.mark.parametrize("sz,cin,cout,xyz,B", [(1, 32, 32, (16, 16, 8), 2), (2, 64, 128, (8, 16, 12), 1),
@@ -1203,9 +1318,11 @@ def test_strided_filter_gradient_in_parity_form(hip, sz, cin, cout, xyz, B):
     oxyz = tuple(y.shape[2:])
     assert (2 * oxyz[0], 2 * oxyz[1], sz * oxyz[2]) == tuple(xyz)
     xb, gb = to_ndhwc(x, cin, 0, dt), to_ndhwc(gy, cout, 0, dt)
-    outs = []
+    outs, guards, n_max = [], [], 0
     for _ in range(2):
-        dw = torch.full((cout, cin, 4, 4, 3), float("nan"), dtype=torch.float32, device=DEV)
+        dwg = kb.Guarded((cout, cin, 4, 4, 3), torch.float32, DEV)
+        dw = dwg.t
+        guards.append(dwg)
         for zc in range(sz):
             kzp = 3 if sz == 1 else (1 if zc == 0 else 2)
             pz, mz, oz = (1, 1, 0) if sz == 1 else ((0, 2, 0) if zc == 0 else (1, 2, 1))
@@ -1216,8 +1333,11 @@ def test_strided_filter_gradient_in_parity_form(hip, sz, cin, cout, xyz, B):
                 g = o.ConvGeom(cin, cout, (2, 2, kzp), (1, 1, 1), (1 - a_, 1 - b_, pz))
                 d = o.make_desc(g, dt, B, oxyz, cin, 0, cout, 0, lat=(1 - a_, 1 - b_, 0, mz, oz, True))
                 n = o.conv_wgrad_nparts(d)
-                parts = torch.full((n, cout, g.taps, cin), float("nan"), dtype=torch.float32, device=DEV)
+                n_max = max(n_max, n)
+                pg = kb.Guarded((n, cout, g.taps, cin), torch.float32, DEV)
+                parts = pg.t
                 o.conv_wgrad_parts(d, xb, gb, parts, n)
+                guards.append(pg)
                 jobs.append((parts[0], tw[ph], 1.0, n, parts[0].numel()))
                 keep.append(parts)
             o.unpack_wgrad_reduce_multi(o.unpack_job_table(jobs))
@@ -1226,6 +1346,12 @@ def test_strided_filter_gradient_in_parity_form(hip, sz, cin, cout, xyz, B):
     assert torch.isfinite(outs[0]).all()
     assert rel_l2(outs[0], w.grad) < 2e-5  # fp32 accumulation of exactly representable products
     assert torch.equal(outs[0], outs[1])
+    kb.assert_guards_intact(*guards, label="strided wgrad")
+    w64 = torch.zeros((cout, cin, 4, 4, 3), dtype=torch.float64, requires_grad=True)
+    (r64,) = torch.autograd.grad(F.conv3d(x.double(), w64, None, (2, 2, sz), 1), w64, gy.double())
+    (A,) = torch.autograd.grad(F.conv3d(x.double().abs(), w64, None, (2, 2, sz), 1), w64, gy.double().abs())
+    kb.assert_within(outs[0], r64, kb.bound(r64, A, B * math.prod(oxyz) + n_max, 0.0),
+                     f"strided wgrad[{sz} {cin} {cout}]", kind="filter")
 
 
 @pytest.mark.parametrize("shape", [(32, 128, 3, 3, 3), (128, 256, 1, 1, 1), (256, 128, 1, 1, 1), (144, 144, 5, 5, 5),

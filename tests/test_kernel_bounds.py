@@ -1,0 +1,254 @@
+"""CPU checks of tests/kernel_bounds.py: the float64 references equal float64 autograd, the element-wise bound holds
+for CPU emulations of the kernels' arithmetic (not too tight), it rejects small local errors that the whole-tensor
+rel-L2 tolerances of the kernel tests accept (not too loose), and guarded buffers report a single stray write."""
+import math
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from conftest import rel_l2
+import kernel_bounds as kb
+
+f64 = torch.float64
+
+
+def _bf(t):
+    return t.bfloat16().float()
+
+
+# ---- references ------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("k,ups,B", [((3, 3, 3), False, 2), ((5, 5, 5), False, 1), ((3, 3, 3), True, 2),
+                                     ((5, 5, 1), False, 2), ((1, 1, 1), False, 2)])
+def test_references_equal_float64_autograd(k, ups, B):
+    gen = torch.Generator().manual_seed(sum(k) + B + ups)
+    cin, cout, ctot, off, xyz = 5, 7, 9, 3, (4, 5, 6)
+    pad = tuple(kk // 2 for kk in k)
+    xbuf = torch.randn((B, ctot) + xyz, generator=gen, dtype=f64)
+    x = xbuf[:, off:off + cin].clone().requires_grad_(True)
+    w = torch.randn((cout, cin) + k, generator=gen, dtype=f64).requires_grad_(True)
+    bias = torch.randn(cout, generator=gen, dtype=f64)
+    xin = kb.up2(x) if ups else x
+    y = F.conv3d(xin, w, None, 1, pad)
+    res = torch.randn(y.shape, generator=gen, dtype=f64)
+    cs = torch.rand((B, cout), generator=gen, dtype=f64)
+    # forward with the full epilogue, on windows
+    want = 0.3 * F.leaky_relu(y + bias.view(1, -1, 1, 1, 1), 0.2) * cs.view(B, cout, 1, 1, 1) - 0.7 * res
+    got, A = kb.ref_fwd(xbuf, w, pad, ups=ups, bias=bias, act=True, chan_scale=cs, alpha=0.3, res=res, beta=-0.7,
+                        in_win=(off, cin))
+    torch.testing.assert_close(got, want.detach(), rtol=1e-12, atol=1e-12)
+    assert bool((A >= got.abs() - 1e-12).all())
+    # ... on an x slab
+    got_s, _ = kb.ref_fwd(x, w, pad, ups=ups, xs=(1, 3))
+    torch.testing.assert_close(got_s, y.detach()[:, :, 1:3], rtol=1e-12, atol=1e-12)
+    # input gradient, with the LeakyReLU / Dropout3d mask and an accumulated value
+    gy = torch.randn(y.shape, generator=gen, dtype=f64)
+    (dx,) = torch.autograd.grad(y, x, gy, retain_graph=True)
+    h = torch.randn(x.shape, generator=gen, dtype=f64)
+    keep = torch.rand((B, cin), generator=gen, dtype=f64)
+    acc = torch.randn(x.shape, generator=gen, dtype=f64)
+    want = (0.5 * dx + acc) * torch.where(h > 0, 1.0, 0.2) * keep.view(B, cin, 1, 1, 1)
+    got, A = kb.ref_dgrad(gy, w, pad, ups=ups, alpha=0.5, mask_y=h, keep=keep, acc=acc)
+    torch.testing.assert_close(got, want, rtol=1e-12, atol=1e-12)
+    assert bool((A >= got.abs() - 1e-12).all())
+    if not ups:
+        got_s, _ = kb.ref_dgrad(gy, w, pad, xs=(2, 4))
+        torch.testing.assert_close(got_s, dx[:, :, 2:4], rtol=1e-12, atol=1e-12)
+    # filter gradient
+    (dw,) = torch.autograd.grad(y, w, gy)
+    got, A = kb.ref_wgrad(xbuf, gy, k, pad, ups=ups, in_win=(off, cin))
+    torch.testing.assert_close(got, dw, rtol=1e-12, atol=1e-12)
+    assert bool((A >= got.abs() - 1e-12).all())
+
+
+# ---- CPU emulations of the kernels' arithmetic pass the bound ---------------------------------------------------------
+
+def _fp32_tap_order(x, w, pad):
+    """fp32 conv summed tap by tap in reverse order (a different fp32 summation order than the CPU conv's)"""
+    k = w.shape[2:]
+    xp = F.pad(x, (pad[2], pad[2], pad[1], pad[1], pad[0], pad[0]))
+    out = None
+    X, Y, Z = (xp.shape[2 + i] - k[i] + 1 for i in range(3))
+    for kx in reversed(range(k[0])):
+        for ky in reversed(range(k[1])):
+            for kz in reversed(range(k[2])):
+                t = torch.einsum("bcxyz,nc->bnxyz", xp[:, :, kx:kx + X, ky:ky + Y, kz:kz + Z], w[:, :, kx, ky, kz])
+                out = t if out is None else out + t
+    return out
+
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float32], ids=["bf16", "fp32"])
+@pytest.mark.parametrize("k,cin,cout", [((3, 3, 3), 32, 24), ((5, 5, 5), 16, 16), ((1, 1, 1), 64, 32)])
+def test_bound_holds_for_emulated_kernel_arithmetic(dt, k, cin, cout):
+    gen = torch.Generator().manual_seed(cin + cout + k[0])
+    B, xyz = 2, (6, 7, 9)
+    pad = tuple(kk // 2 for kk in k)
+    taps = math.prod(k)
+    x = _bf(torch.randn((B, cin) + xyz, generator=gen))
+    w = _bf(torch.randn((cout, cin) + k, generator=gen) / math.sqrt(cin * taps))
+    res = _bf(torch.randn((B, cout) + xyz, generator=gen))
+    rho = kb.rho_for(dt)
+    ratios = {}
+    # forward + residual epilogue
+    y = 0.2 * _fp32_tap_order(x, w, pad) + res
+    y = y.to(dt).float()
+    ref, A = kb.ref_fwd(x, w, pad, alpha=0.2, res=res, beta=1.0)
+    ratios["fwd"] = kb.assert_within(y, ref, kb.bound(ref, A, taps * cin, rho), f"emul fwd {dt}")
+    # input gradient
+    gy = _bf(torch.randn((B, cout) + xyz, generator=gen))
+    dx = _fp32_tap_order(gy, kb.dgrad_filter(w), tuple(kk - 1 - p for kk, p in zip(k, pad))).to(dt).float()
+    ref, A = kb.ref_dgrad(gy, w, pad)
+    ratios["dgrad"] = kb.assert_within(dx, ref, kb.bound(ref, A, taps * cout, rho), f"emul dgrad {dt}")
+    # filter gradient: three fp32 split copies over the voxels, ordered fp32 sum
+    n_parts = 3
+    parts = []
+    for s in range(n_parts):
+        g = gy.clone()
+        sel = torch.zeros(xyz[0], dtype=torch.bool)
+        sel[s::n_parts] = True
+        g[:, :, ~sel] = 0
+        wv = torch.zeros((cout, cin) + k, requires_grad=True)
+        (p,) = torch.autograd.grad(F.conv3d(x, wv, None, 1, pad), wv, g)
+        parts.append(p)
+    dw = parts[0]
+    for p in parts[1:]:
+        dw = dw + p
+    ref, A = kb.ref_wgrad(x, gy, k, pad)
+    ratios["wgrad"] = kb.assert_within(dw, ref, kb.bound(ref, A, B * math.prod(xyz) + n_parts, 0.0),
+                                       f"emul wgrad {dt}", kind="filter")
+    print("largest |err|/bound:", {n: f"{r:.3g}" for n, r in ratios.items()})
+    assert max(ratios.values()) <= 1.0
+
+
+# ---- small local errors pass the rel-L2 tolerances but fail the bound ---------------------------------------------------
+
+def _fails(got, ref, bnd):
+    bad, worst, _, _ = kb.check_within(got, ref, bnd)
+    return bad > 0 and worst > 1.0
+
+
+def test_one_dropped_tap_at_one_voxel_is_caught():
+    """bf16 3x3x3 forward, 4 096 voxels: the output at one tile corner misses one tap.  The old check
+    (rel-L2 < 4e-3 against the fp32 conv of the same bf16 operands) accepts it; the bound does not, and it names the
+    voxel."""
+    gen = torch.Generator().manual_seed(7)
+    cin = cout = 16
+    xyz, pad = (16, 16, 16), (1, 1, 1)
+    x = _bf(torch.randn((1, cin) + xyz, generator=gen))
+    w = _bf(torch.randn((cout, cin, 3, 3, 3), generator=gen) / math.sqrt(cin * 27))
+    y32 = F.conv3d(x, w, None, 1, pad)
+    v = (7, 7, 15)  # corner of an 8 x 8 x 16 tile
+    xp = F.pad(x, (1, 1, 1, 1, 1, 1))[0]
+    contribs = [torch.einsum("c,nc->n", xp[:, v[0] + t // 9, v[1] + t // 3 % 3, v[2] + t % 3], w[:, :, t // 9, t // 3 % 3, t % 3])
+                for t in range(27)]
+    norms = torch.stack([c.norm() for c in contribs])
+    contrib = contribs[int(norms.argsort()[13])]  # the tap of median weight at that voxel
+    bad = y32.clone()
+    bad[0, :, v[0], v[1], v[2]] -= contrib
+    bad = _bf(bad)
+    assert rel_l2(bad, y32) < 4e-3  # the blind spot of the old tolerance
+    ref, A = kb.ref_fwd(x, w, pad)
+    bnd = kb.bound(ref, A, 27 * cin, kb.RHO_BF16)
+    kb.assert_within(_bf(y32), ref, bnd, "unmutated")
+    assert _fails(bad, ref, bnd)
+    with pytest.raises(AssertionError, match=r"x=7, y=7, z=15"):
+        kb.assert_within(bad, ref, bnd, "dropped tap")
+
+
+def test_one_filter_gradient_element_off_by_1e3_relative_is_caught():
+    """one element of an fp32 filter gradient off by 1e-3 of its value passes rel-L2 < 2e-5 but not the bound"""
+    gen = torch.Generator().manual_seed(3)
+    cin = cout = 16
+    B, xyz, k, pad = 2, (6, 6, 8), (3, 3, 3), (1, 1, 1)
+    x = _bf(torch.randn((B, cin) + xyz, generator=gen))
+    gy = _bf(torch.randn((B, cout) + xyz, generator=gen))
+    ref, A = kb.ref_wgrad(x, gy, k, pad)
+    dw = ref.float()
+    flat = dw.view(-1)
+    i = int((flat.abs() - flat.abs().square().mean().sqrt()).abs().argmin())  # an element of typical size
+    flat[i] *= 1 + 1e-3
+    assert rel_l2(dw, ref) < 2e-5
+    bnd = kb.bound(ref, A, B * math.prod(xyz), 0.0)
+    kb.assert_within(ref.float(), ref, bnd, "unmutated", kind="filter")
+    assert _fails(dw, ref, bnd)
+    n, c = i // (cin * 27), (i // 27) % cin
+    with pytest.raises(AssertionError, match=rf"n={n}, tap={i % 27}, c={c}\)"):
+        kb.assert_within(dw, ref, bnd, "off by 1e-3", kind="filter")
+
+
+def test_one_voxel_missing_from_one_split_is_caught():
+    """deterministic split form of a 64 -> 64 3x3x3 filter gradient (B = 2, ragged z extent 14: the last tile of 4
+    z-levels holds 2): split 1's partial sum lacks the product of the last voxel of a ragged last tile for one
+    (n, tap, c).  The ordered sum passes rel-L2 < 2e-5; the bound names the element."""
+    gen = torch.Generator().manual_seed(5)
+    cin = cout = 64
+    B, xyz, k, pad = 2, (8, 16, 14), (3, 3, 3), (1, 1, 1)
+    x = _bf(torch.randn((B, cin) + xyz, generator=gen))
+    gy = _bf(torch.randn((B, cout) + xyz, generator=gen))
+    n_parts = 3
+    tiles_z = torch.arange(xyz[2]) // 4  # z tiles of 4 levels, dealt round-robin to the splits
+    parts = []
+    for s in range(n_parts):
+        g = gy.clone()
+        g[..., tiles_z % n_parts != s] = 0
+        wv = torch.zeros((cout, cin) + k, requires_grad=True)
+        (p,) = torch.autograd.grad(F.conv3d(x, wv, None, 1, pad), wv, g)
+        parts.append(p)
+    ref, A = kb.ref_wgrad(x, gy, k, pad)
+    bnd = kb.bound(ref, A, B * math.prod(xyz) + n_parts, 0.0)
+    # the last voxel of the ragged last z tile (z = 13, tile 3 -> split 0) of sample 1: the product it adds at
+    # (n, tap, c) = gy[1, n, v] * x[1, c, v + tap - 1]; take the (n, c, tap) with the product nearest 0.3
+    s_bad = int(tiles_z[-1]) % n_parts
+    v = (3, 9, 13)
+    xp = F.pad(x, (1, 1, 1, 1, 1, 1))[1]
+    best = None
+    for t in range(27):
+        kx, ky, kz = t // 9, (t // 3) % 3, t % 3
+        prod = torch.outer(gy[1, :, v[0], v[1], v[2]], xp[:, v[0] + kx, v[1] + ky, v[2] + kz])
+        if prod.abs().max() == 0:
+            continue
+        j = int((prod.abs() - 0.3).abs().argmin())
+        cand = (abs(float(prod.view(-1)[j]) - 0.3), t, j // cin, j % cin, float(prod.view(-1)[j]))
+        best = cand if best is None or cand < best else best
+    _, t, n, c, p = best
+    parts[s_bad][n, c, t // 9, (t // 3) % 3, t % 3] -= p
+    dw = parts[0]
+    for q in parts[1:]:
+        dw = dw + q
+    assert rel_l2(dw, ref) < 2e-5
+    assert _fails(dw, ref, bnd)
+    with pytest.raises(AssertionError, match=rf"n={n}, tap={t}, c={c}\)"):
+        kb.assert_within(dw, ref, bnd, "missing voxel", kind="filter")
+
+
+# ---- guards --------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float32], ids=["bf16", "fp32"])
+def test_guards_report_a_single_stray_write(dt):
+    shape, win = (2, 3, 4, 5, 24), (8, 12)
+    g = kb.Guarded(shape, dt, "cpu", window=win, fill=1.0)
+    assert bool((g.window_view() == 1.0).all())
+    g.window_view().fill_(2.0)  # writes inside the window are the kernel's business
+    kb.assert_guards_intact(g, label="clean")
+    if dt == torch.float32:
+        assert torch.isnan(g.t[..., :8]).all()
+    else:
+        assert torch.isfinite(g.t[..., :8].float()).all() and bool((g.t[..., :8] != 0).all())
+    # one channel outside the window
+    g.t[1, 2, 3, 4, 20] = 0.0
+    with pytest.raises(AssertionError, match=r"index \(1, 2, 3, 4, 20\) outside the channel window"):
+        kb.assert_guards_intact(g, label="window")
+    # one element past the end / in front of the tensor
+    for where, pos in (("past its end", g.guard + g.t.numel() + 17), ("before the tensor", g.guard - 3)):
+        h = kb.Guarded(shape, dt, "cpu")
+        kb.assert_guards_intact(h)
+        h.base[pos] = 1.0
+        with pytest.raises(AssertionError, match=where):
+            kb.assert_guards_intact(h)
+    # a sentinel NaN re-written as another NaN is a write too (bit-for-bit comparison)
+    if dt == torch.float32:
+        h = kb.Guarded(shape, dt, "cpu")
+        h.base[5] = float("nan")
+        with pytest.raises(AssertionError):
+            kb.assert_guards_intact(h)
