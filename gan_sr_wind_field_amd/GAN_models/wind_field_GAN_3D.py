@@ -83,6 +83,7 @@ class wind_field_GAN_3D(BaseGAN):
         self.epsilon_PSNR = torch.tensor(1e-8, device=dev)
         self.feature_extractor = None
         self.dp = None  # set by dist.attach()
+        self._ema_cfg = None  # the [EMA] section when it is present (training only)
 
         cfg_G, cfg_gan = cfg.generator, cfg.gan_config
         # The ini's use_mixed_precision flags are parsed but - as in the reference, whose AMP
@@ -136,9 +137,18 @@ class wind_field_GAN_3D(BaseGAN):
         clip_kw = {w: ({"max_grad_norm": b, "track_grad_norm": self._track_norms} if table and (b is not None or
                                                                                                self._track_norms) else {})
                    for w, b in self._clip_bound.items()}
+        # [EMA] (extension; absent: no shadows): the moving average of the generator's weights rides in the generator's
+        # optimizer launch; the factor of each step is set from the iteration number (0 before start_iter: a copy)
+        self._ema_cfg = cfg.ema if getattr(cfg.ema, "present", False) else None
+        ema_kw = {}
+        if self._ema_cfg is not None:
+            self.init_ema()
+            self._ema_decay_now = self._ema_cfg.decay_at(0)
+            if table:
+                ema_kw = {"ema_decay": self._ema_decay_now, "ema_shadows": self.ema_shadows}
         self.optimizer_G = Adam(self.G.parameters(), lr=cfg_t.learning_rate_g,
                                 weight_decay=cfg_t.adam_weight_decay_g,
-                                betas=(cfg_t.adam_beta1_g, 0.999), **fused, **clip_kw["G"])
+                                betas=(cfg_t.adam_beta1_g, 0.999), **fused, **clip_kw["G"], **ema_kw)
         self.optimizer_D = Adam(self.D.parameters(), lr=cfg_t.learning_rate_d,
                                 weight_decay=cfg_t.adam_weight_decay_d,
                                 betas=(cfg_t.adam_beta1_d, 0.999), **fused, **clip_kw["D"])
@@ -148,6 +158,8 @@ class wind_field_GAN_3D(BaseGAN):
             for w, opt in (("G", self.optimizer_G), ("D", self.optimizer_D)):
                 if self._clip_bound[w] is not None or self._track_norms:
                     opt.register_step_pre_hook(lambda opt_, *_, w_=w: self._clip_before_step(w_, opt_))
+        if self._ema_cfg is not None and not table:  # torch's Adam: the same formula with torch ops, behind its step
+            self.optimizer_G.register_step_post_hook(lambda *_: self._ema_after_step())
         if fused:
             self.optimizer_G.register_step_post_hook(lambda *_: self.G.program().filters.invalidate())
             self.optimizer_D.register_step_post_hook(lambda *_: self.D.features.program().filters.invalidate())
@@ -568,6 +580,8 @@ class wind_field_GAN_3D(BaseGAN):
         if training_iteration:
             period = it_int // self.d_g_train_period
             if period % (self.d_g_train_ratio + 1) == 0:
+                if self._ema_cfg is not None:
+                    self._set_ema_decay(it_int)
                 self.update_G(LR, HR, Z, it, True)
             else:
                 with torch.no_grad():
@@ -616,6 +630,18 @@ class wind_field_GAN_3D(BaseGAN):
         else:
             self.HR_labels, self.fake_HR_labels = a.squeeze(), b.squeeze()
             self._labels_all_09 = None
+
+    # ------------------------------------------------------------------ moving average of G's weights ([EMA])
+    def _set_ema_decay(self, it: int) -> None:
+        if self._in_ema_scope:
+            raise RuntimeError("a training iteration inside ema_scope(): the generator holds the averaged weights")
+        self._ema_decay_now = self._ema_cfg.decay_at(it)
+        if hasattr(self.optimizer_G, "ema_decay"):
+            self.optimizer_G.ema_decay = self._ema_decay_now
+
+    def _ema_after_step(self) -> None:
+        from ..tools.table_adam import ema_update_
+        ema_update_(self.ema_shadows, list(self.G.parameters()), self._ema_decay_now)
 
     # ------------------------------------------------------------------ gradient norms
     def _clip_before_step(self, which: str, opt) -> None:

@@ -22,7 +22,7 @@ EXPORTS = [
     "wsr_pack_filter", "wsr_unpack_wgrad", "wsr_unpack_wgrad_multi", "wsr_lrelu_bwd_inplace", "wsr_chan_axpby", "wsr_chan_sum", "wsr_chan_sum_rows", "wsr_chan_sum_partials", "wsr_upsample2_bwd", "wsr_subpixel_fold", "wsr_subpixel_unfold", "wsr_strided_parity_filters", "wsr_strided_parity_unfold",
     "wsr_planar_to_ndhwc", "wsr_ndhwc_to_planar", "wsr_zfold", "wsr_zunfold", "wsr_wind_gradient", "wsr_wind_gradient_bwd", "wsr_plane_sum", "wsr_linear_rows", "wsr_physics_loss_workspace_floats", "wsr_physics_loss_stats", "wsr_physics_loss_bwd", "wsr_bn_stats", "wsr_bn_mean", "wsr_bn_shard_stats", "wsr_bn_combine_shards", "wsr_bn_finalize", "wsr_bn_apply_lrelu", "wsr_bn_bwd_reduce",
     "wsr_bn_bwd_apply", "wsr_adam_step", "wsr_adam_multi", "wsr_gather_batch", "wsr_grad_sqnorm_multi",
-    "wsr_adam_multi_clip",
+    "wsr_adam_multi_clip", "wsr_adam_multi_ema", "wsr_adam_multi_clip_ema",
 ]
 
 
@@ -141,6 +141,8 @@ def lib() -> C.CDLL:
         "wsr_gather_batch": [vp, i64, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp],   # additive export
         "wsr_grad_sqnorm_multi": [vp, i32, vp, vp],   # additive export
         "wsr_adam_multi_clip": [vp, i32, vp] + [C.c_double] * 6 + [i32, vp, vp],   # additive export
+        "wsr_adam_multi_ema": [vp, vp, i32] + [C.c_double] * 5 + [i32, C.c_double, vp],   # additive export
+        "wsr_adam_multi_clip_ema": [vp, vp, i32, vp] + [C.c_double] * 6 + [i32, C.c_double, vp, vp],   # additive export
     }
     for name, argtypes in sig.items():
         fn = getattr(L, name)

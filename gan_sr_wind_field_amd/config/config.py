@@ -12,6 +12,9 @@ Extension (optional keys, defaults keep reference behaviour):
   [DATA]    device_resident = True | False  training / validation splits held in device memory (device_data.py)
   [GRAD_CLIP] clip_generator / clip_discriminator / max_norm_discriminator / log_grad_norms
             gradient-norm clipping of the optimizer steps (the generator's bound is [GENERATOR] max_norm)
+  [EMA]     decay / start_iter / validate_with_ema / test_with_ema
+            exponential moving average of the generator's weights, updated inside the optimizer step
+            (tools/table_adam.py), saved as G_ema_{it}.pth, used for validation and --test
 """
 from __future__ import annotations
 
@@ -308,6 +311,41 @@ class GradClipConfig(IniConfig):
         return "[GRAD_CLIP]\n" + "".join(f"{k} = {getattr(self, k)}\n" for k, _ in self._schema)
 
 
+class EmaConfig(IniConfig):
+    """[EMA] (extension): moving average ``e <- decay * e + (1 - decay) * w`` of the generator's weights after every
+    generator step; absent section = off, and not printed by ``asINI``.  Generator steps at iterations before
+    ``start_iter`` copy (``e = w``)."""
+
+    present: bool = False
+    decay: float = 0.999
+    start_iter: int = 0
+    validate_with_ema: bool = True
+    test_with_ema: bool = True
+    _schema = (("decay", _F), ("start_iter", _I), ("validate_with_ema", _B), ("test_with_ema", _B))
+
+    def setEmaConfig(self, section):
+        """``section`` None (no [EMA] in the file) restores the defaults and switches the average off."""
+        self.present = section is not None
+        for key, kind in self._schema:
+            val = None if section is None else _read(section, key, kind)
+            setattr(self, key, getattr(EmaConfig, key) if val is None else val)
+
+    def validate(self) -> None:
+        if not self.present:
+            return
+        if not 0.0 < self.decay < 1.0:  # (NaN fails both)
+            raise ValueError(f"[EMA] decay must be > 0 and < 1, not {self.decay}")
+        if self.start_iter < 0:
+            raise ValueError(f"[EMA] start_iter must be >= 0, not {self.start_iter}")
+
+    def decay_at(self, it: int) -> float:
+        """the factor of the generator step of iteration ``it``"""
+        return self.decay if int(it) >= self.start_iter else 0.0
+
+    def __str__(self) -> str:
+        return "[EMA]\n" + "".join(f"{k} = {getattr(self, k)}\n" for k, _ in self._schema)
+
+
 class Config(IniConfig):
     name: str = "default_name"
     model: str = "default_model"
@@ -331,6 +369,7 @@ class Config(IniConfig):
     dist: DistConfig = DistConfig()
     data: DataConfig = DataConfig()
     grad_clip: GradClipConfig = GradClipConfig()
+    ema: EmaConfig = EmaConfig()
     compute_dtype: str = "fp32"
     is_train: bool
     is_use: bool
@@ -359,6 +398,8 @@ class Config(IniConfig):
         self.data.setDataConfig(parser["DATA"] if parser.has_section("DATA") else None)
         self.grad_clip.setGradClipConfig(parser["GRAD_CLIP"] if parser.has_section("GRAD_CLIP") else None)
         self.grad_clip.validate(self.generator.max_norm)
+        self.ema.setEmaConfig(parser["EMA"] if parser.has_section("EMA") else None)
+        self.ema.validate()
 
     def setBaseConfig(self, base):
         self.name = base.get("name")
@@ -388,4 +429,6 @@ class Config(IniConfig):
                 out += "\n" + str(sec)
         if getattr(self.grad_clip, "present", False):  # (absent: the text of a file without the extension, unchanged)
             out += "\n" + str(self.grad_clip)
+        if getattr(self.ema, "present", False):
+            out += "\n" + str(self.ema)
         return out

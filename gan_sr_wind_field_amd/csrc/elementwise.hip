@@ -742,6 +742,133 @@ __global__ __launch_bounds__(256) void adam_multi_clip_kernel(const wsr_adam_job
 }
 
 
+// ---- moving average of the weights (EMA) folded into the table Adam --------------------------------------------------
+// e <- d * e + (1 - d) * p on the p that adam_one has just produced, from registers: one read and one write of the
+// shadow chunk, no launch of its own.  ema[job] is the shadow of the job's chunk (a table parallel to the job table).
+struct EmaK { float d, omd; };
+// 1 - d is taken in double and rounded once, as adam_k does with 1 - beta
+static EmaK ema_k(double decay) {
+  EmaK k;
+  k.d = (float)decay; k.omd = (float)(1.0 - decay);
+  return k;
+}
+// two roundings: fl(omd * p), then the fused d * e + that.  d == 0 is a select (e = p bit for bit whatever the old e
+// holds - 0 * inf would be NaN): "the shadow follows the weights".
+__device__ __forceinline__ float ema_one(float e, float p, const EmaK& k) {
+  return k.d == 0.f ? p : __fmaf_rn(k.d, e, __fmul_rn(k.omd, p));
+}
+// The float4 path of p, g, m, v is taken exactly when adam_multi_kernel takes it, whatever the shadow's alignment (the
+// two paths of that kernel need not round alike); a shadow that is not 16-byte aligned moves element by element there.
+__device__ __forceinline__ float4 ema_load4(const float4* e4, const float* e, long i, bool evec) {
+  return evec ? e4[i] : make_float4(e[4 * i], e[4 * i + 1], e[4 * i + 2], e[4 * i + 3]);
+}
+__device__ __forceinline__ void ema_store4(float4* e4, float* e, long i, bool evec, const float4 r) {
+  if (evec) {
+    e4[i] = r;
+  } else {
+    e[4 * i] = r.x; e[4 * i + 1] = r.y; e[4 * i + 2] = r.z; e[4 * i + 3] = r.w;
+  }
+}
+
+// adam_multi_kernel + the shadow update (p, m, v: the same operations in the same order, bit for bit)
+__global__ __launch_bounds__(256) void adam_multi_ema_kernel(const wsr_adam_job_t* __restrict__ jobs,
+                                                             float* const* __restrict__ ema, const AdamK k,
+                                                             const EmaK ek) {
+  const wsr_adam_job_t j = jobs[blockIdx.x];
+  float* je = ema[blockIdx.x];
+  const long n = j.n;
+  const bool vec = ((((size_t)j.p) | ((size_t)j.g) | ((size_t)j.m) | ((size_t)j.v)) & 15) == 0;
+  const bool evec = (((size_t)je) & 15) == 0;
+  long done = 0;
+  if (vec) {
+    const long n4 = n >> 2;
+    float4* p4 = reinterpret_cast<float4*>(j.p);
+    const float4* g4 = reinterpret_cast<const float4*>(j.g);
+    float4* m4 = reinterpret_cast<float4*>(j.m);
+    float4* v4 = reinterpret_cast<float4*>(j.v);
+    float4* e4 = reinterpret_cast<float4*>(je);
+    for (long i = threadIdx.x; i < n4; i += 256) {
+      float4 p = p4[i], m = m4[i], v = v4[i];
+      const float4 g = g4[i];
+      const float4 e = ema_load4(e4, je, i, evec);
+      adam_one(p.x, g.x, m.x, v.x, k);
+      adam_one(p.y, g.y, m.y, v.y, k);
+      adam_one(p.z, g.z, m.z, v.z, k);
+      adam_one(p.w, g.w, m.w, v.w, k);
+      p4[i] = p; m4[i] = m; v4[i] = v;
+      ema_store4(e4, je, i, evec, make_float4(ema_one(e.x, p.x, ek), ema_one(e.y, p.y, ek), ema_one(e.z, p.z, ek),
+                                              ema_one(e.w, p.w, ek)));
+    }
+    done = n4 << 2;
+  }
+  for (long i = done + threadIdx.x; i < n; i += 256) {
+    float p = j.p[i], m = j.m[i], v = j.v[i];
+    adam_one(p, j.g[i], m, v, k);
+    j.p[i] = p; j.m[i] = m; j.v[i] = v;
+    je[i] = ema_one(je[i], p, ek);
+  }
+}
+
+// adam_multi_clip_kernel + the shadow update (total, coefficient, g, p, m, v: bit for bit)
+__global__ __launch_bounds__(256) void adam_multi_clip_ema_kernel(const wsr_adam_job_t* __restrict__ jobs,
+                                                                  float* const* __restrict__ ema,
+                                                                  const float* __restrict__ partials, int n_jobs,
+                                                                  float max_norm, int clip, const AdamK k,
+                                                                  const EmaK ek, float* __restrict__ total_out) {
+  __shared__ double sh[4];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n_jobs; i += 256) s += (double)partials[i];
+  const float total = (float)sqrt(wg256_sum(s, sh));
+  float coef = 1.f;
+  if (clip) {
+    const float c = max_norm / (total + 1e-6f);
+    coef = c > 1.f ? 1.f : c;
+  }
+  if (total_out && blockIdx.x == 0 && threadIdx.x == 0) *total_out = total;
+  const wsr_adam_job_t j = jobs[blockIdx.x];
+  float* je = ema[blockIdx.x];
+  float* gw = const_cast<float*>(j.g);
+  const long n = j.n;
+  const bool vec = ((((size_t)j.p) | ((size_t)j.g) | ((size_t)j.m) | ((size_t)j.v)) & 15) == 0;
+  const bool evec = (((size_t)je) & 15) == 0;
+  long done = 0;
+  if (vec) {
+    const long n4 = n >> 2;
+    float4* p4 = reinterpret_cast<float4*>(j.p);
+    float4* g4 = reinterpret_cast<float4*>(gw);
+    float4* m4 = reinterpret_cast<float4*>(j.m);
+    float4* v4 = reinterpret_cast<float4*>(j.v);
+    float4* e4 = reinterpret_cast<float4*>(je);
+    for (long i = threadIdx.x; i < n4; i += 256) {
+      float4 p = p4[i], m = m4[i], v = v4[i], g = g4[i];
+      const float4 e = ema_load4(e4, je, i, evec);
+      if (clip) {
+        g.x *= coef; g.y *= coef; g.z *= coef; g.w *= coef;
+        g4[i] = g;
+      }
+      adam_one(p.x, g.x, m.x, v.x, k);
+      adam_one(p.y, g.y, m.y, v.y, k);
+      adam_one(p.z, g.z, m.z, v.z, k);
+      adam_one(p.w, g.w, m.w, v.w, k);
+      p4[i] = p; m4[i] = m; v4[i] = v;
+      ema_store4(e4, je, i, evec, make_float4(ema_one(e.x, p.x, ek), ema_one(e.y, p.y, ek), ema_one(e.z, p.z, ek),
+                                              ema_one(e.w, p.w, ek)));
+    }
+    done = n4 << 2;
+  }
+  for (long i = done + threadIdx.x; i < n; i += 256) {
+    float p = j.p[i], m = j.m[i], v = j.v[i], g = gw[i];
+    if (clip) {
+      g *= coef;
+      gw[i] = g;
+    }
+    adam_one(p, g, m, v, k);
+    j.p[i] = p; j.m[i] = m; j.v[i] = v;
+    je[i] = ema_one(je[i], p, ek);
+  }
+}
+
+
 // per-channel sum over voxels of an NDHWC window, pass 1: thread = (voxel lane, 4-channel group); the
 // workgroup's partial sums go to row blockIdx.x of `part` (no atomics: C addresses would serialise them)
 template <class T>
@@ -1562,6 +1689,33 @@ extern "C" int wsr_adam_multi_clip(const wsr_adam_job_t* jobs_dev, int32_t n_job
   const int clip = std::isinf(max_norm) ? 0 : 1;
   hipLaunchKernelGGL(adam_multi_clip_kernel, dim3((unsigned)n_jobs), dim3(256), 0, as_stream(stream), jobs_dev,
                      partials, (int)n_jobs, (float)max_norm, clip, k, total_norm_out);
+  WSR_LAUNCH_CHECK();
+  return 0;
+}
+
+static bool ema_decay_ok(double d) { return d >= 0.0 && d < 1.0; }  // (false for NaN)
+
+extern "C" int wsr_adam_multi_ema(const wsr_adam_job_t* jobs_dev, float* const* ema_dev, int32_t n_jobs, double lr,
+                                  double beta1, double beta2, double eps, double weight_decay, int32_t step,
+                                  double ema_decay, void* stream) {
+  if (!jobs_dev || !ema_dev || n_jobs <= 0 || step < 1 || !ema_decay_ok(ema_decay)) return WSR_EINVAL;
+  const AdamK k = adam_k(lr, beta1, beta2, eps, weight_decay, step);
+  hipLaunchKernelGGL(adam_multi_ema_kernel, dim3((unsigned)n_jobs), dim3(256), 0, as_stream(stream), jobs_dev, ema_dev,
+                     k, ema_k(ema_decay));
+  WSR_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int wsr_adam_multi_clip_ema(const wsr_adam_job_t* jobs_dev, float* const* ema_dev, int32_t n_jobs,
+                                       const float* partials, double max_norm, double lr, double beta1, double beta2,
+                                       double eps, double weight_decay, int32_t step, double ema_decay,
+                                       float* total_norm_out, void* stream) {
+  if (!jobs_dev || !ema_dev || !partials || n_jobs <= 0 || step < 1 || !(max_norm > 0.0) || !ema_decay_ok(ema_decay))
+    return WSR_EINVAL;
+  const AdamK k = adam_k(lr, beta1, beta2, eps, weight_decay, step);
+  const int clip = std::isinf(max_norm) ? 0 : 1;
+  hipLaunchKernelGGL(adam_multi_clip_ema_kernel, dim3((unsigned)n_jobs), dim3(256), 0, as_stream(stream), jobs_dev,
+                     ema_dev, partials, (int)n_jobs, (float)max_norm, clip, k, ema_k(ema_decay), total_norm_out);
   WSR_LAUNCH_CHECK();
   return 0;
 }

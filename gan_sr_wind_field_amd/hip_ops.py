@@ -959,6 +959,57 @@ def adam_multi_clip(table: Tensor, partials: Tensor, max_norm: float, lr: float,
                                          weight_decay, step, _p(total_norm), _stream()), "adam_multi_clip")
 
 
+def ema_ptr_table(tensors, shadows) -> Tensor:
+    """Device array of one ``float*`` per job of ``adam_job_table(tensors)``, chunk for chunk: the shadow (moving
+    average) of each parameter chunk.  ``shadows``: one contiguous fp32 tensor per entry of ``tensors``, same size and
+    device as its parameter."""
+    import numpy as np
+
+    if len(shadows) != len(tensors):
+        raise ValueError("ema_ptr_table wants one shadow per parameter")
+    rows = []
+    for quad, e in zip(tensors, shadows):
+        n = quad[0].numel()
+        if e.dtype != torch.float32 or not e.is_contiguous() or e.numel() != n or e.device != quad[0].device:
+            raise ValueError("ema_ptr_table wants contiguous fp32 shadows of their parameter's size and device")
+        if e.data_ptr() == quad[0].data_ptr():
+            raise ValueError("ema_ptr_table: a shadow shares its parameter's storage")
+        rows += [e.data_ptr() + 4 * off for off in range(0, n, ADAM_CHUNK)]
+    return _table_to_device(np.asarray(rows, dtype=np.int64).reshape(-1, 1), tensors[0][0].device)
+
+
+def _check_ema(table: Tensor, ema_table: Tensor, ema_decay: float) -> None:
+    if ema_table.shape[0] != table.shape[0] or ema_table.device != table.device:
+        raise ValueError("the EMA pointer table wants one row per job of the Adam table, on its device")
+    if not 0.0 <= ema_decay < 1.0:
+        raise ValueError(f"ema_decay must be in [0, 1), not {ema_decay}")
+
+
+def adam_multi_ema(table: Tensor, ema_table: Tensor, lr: float, beta1: float, beta2: float, eps: float,
+                   weight_decay: float, step: int, ema_decay: float) -> None:
+    """:func:`adam_multi` that also moves the shadows of ``ema_table`` (:func:`ema_ptr_table` of the same tensors)
+    towards the new parameters, ``e = ema_decay * e + (1 - ema_decay) * p``, in the same launch; ``ema_decay`` = 0
+    copies (``e = p``).  Parameters and optimizer state come out as :func:`adam_multi` leaves them, bit for bit."""
+    _check_ema(table, ema_table, ema_decay)
+    check(_lib.lib().wsr_adam_multi_ema(_p(table), _p(ema_table), table.shape[0], lr, beta1, beta2, eps, weight_decay,
+                                        step, ema_decay, _stream()), "adam_multi_ema")
+
+
+def adam_multi_clip_ema(table: Tensor, ema_table: Tensor, partials: Tensor, max_norm: float, lr: float, beta1: float,
+                        beta2: float, eps: float, weight_decay: float, step: int, ema_decay: float,
+                        total_norm: Optional[Tensor] = None) -> None:
+    """:func:`adam_multi_clip` with the shadow update of :func:`adam_multi_ema` in the same launch."""
+    _check_partials(table, partials)
+    _check_ema(table, ema_table, ema_decay)
+    if not max_norm > 0:
+        raise ValueError(f"adam_multi_clip_ema: max_norm must be > 0, not {max_norm}")
+    if total_norm is not None and (total_norm.dtype != torch.float32 or total_norm.device != table.device):
+        raise ValueError("adam_multi_clip_ema: total_norm wants a fp32 tensor on the table's device")
+    check(_lib.lib().wsr_adam_multi_clip_ema(_p(table), _p(ema_table), table.shape[0], _p(partials), max_norm, lr,
+                                             beta1, beta2, eps, weight_decay, step, ema_decay, _p(total_norm),
+                                             _stream()), "adam_multi_clip_ema")
+
+
 def gather_batch(store: Tensor, desc: Tensor, cin: int, s: int, slice_size: int) -> Tuple[Tensor, Tensor, Tensor]:
     """One training batch ``(LR, HR, Z)`` out of a resident store (``device_data.ResidentStore``) in ONE launch:
     ``store`` fp32 (N, cin + 1, X, Y, NZ), ``desc`` int32 (B, 6) rows ``sample, x0, y0, k, flip_x, flip_y`` on the

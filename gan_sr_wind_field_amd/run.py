@@ -156,6 +156,15 @@ def main(argv=None) -> None:
         train(cfg, dataset_train, dataset_validation, x, y)
         log.info("run.py: finished training")
         cfg.is_train = False
+    if cfg.is_test and cfg.ema.present and cfg.ema.test_with_ema:
+        # [EMA] test_with_ema: evaluate the averaged weights, saved beside the generator checkpoint
+        from .GAN_models.baseGAN import ema_path_of
+        ema_path = ema_path_of(cfg.env.generator_load_path)
+        if not os.path.isfile(ema_path):
+            raise FileNotFoundError(f"[EMA] test_with_ema: {ema_path} does not exist (the averaged weights of "
+                                    f"{cfg.env.generator_load_path})")
+        log.info(f"run.py: testing the averaged generator weights {ema_path}")
+        cfg.env.generator_load_path = ema_path
     if cfg.is_test or cfg.is_use:
         log.info("run.py: starting testing")
         test(cfg, dataset_test)

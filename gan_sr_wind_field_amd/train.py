@@ -11,7 +11,10 @@ shuffled index list per rank, ``dist.attach`` reduces gradients / BatchNorm stat
 terms, and only rank 0 writes checkpoints, logs and validation artefacts.  With ``[DATA] device_resident = True`` the
 training and validation splits are loaded into device memory once and each batch is gathered there
 (``device_data.py``: same batches, same random streams as the ``num_workers = 0`` loaders; every rank holds the whole
-split and the ``DistributedSampler`` drives the descriptor loader).
+split and the ``DistributedSampler`` drives the descriptor loader).  With ``[EMA]`` the generator keeps a moving average
+of its weights (updated inside its optimizer step), ``G_ema_{it}.pth`` is saved beside ``G_{it}.pth`` and, with
+``validate_with_ema``, the validation epochs run on the averaged weights (``gan.ema_scope()``); the replicas of a
+data-parallel run are bit-identical, hence so are their averages: no collective, rank 0 saves.
 """
 from __future__ import annotations
 
@@ -170,7 +173,9 @@ def train(cfg, dataset_train, dataset_validation, x, y):
                             tb.add_scalars("grad_norm/train", norms, it)
                 if dataloader_val is None or it % cfg_t.val_period != 0:
                     continue
-                _validate(cfg, gan, dataloader_val, dataset_train, it, tb, status_logger, lead)
+                # ([EMA] validate_with_ema: losses, PSNR and figures of the averaged weights; training goes on with the live ones)
+                with gan.ema_scope() if cfg.ema.present and cfg.ema.validate_with_ema else contextlib.nullcontext():
+                    _validate(cfg, gan, dataloader_val, dataset_train, it, tb, status_logger, lead)
     if tb is not None:
         tb.close()
     return gan

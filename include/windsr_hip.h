@@ -486,6 +486,19 @@ int wsr_grad_sqnorm_multi(const wsr_adam_job_t* jobs_dev, int32_t n_jobs, float*
 int wsr_adam_multi_clip(const wsr_adam_job_t* jobs_dev, int32_t n_jobs, const float* partials, double max_norm,
                         double lr, double beta1, double beta2, double eps, double weight_decay, int32_t step,
                         float* total_norm_out, void* stream);
+/* additive - exponential moving average (EMA) of the parameters inside the same launches: ema_dev is a DEVICE array
+ * parallel to the job table, ema_dev[job] = the shadow of job's chunk (n floats; wsr_adam_job_t is unchanged).  Per
+ * element, after the update has produced the new p:  e = fma(d, e, fl(omd * p))  - two roundings - with
+ * d = (float)ema_decay and omd = (float)(1.0 - ema_decay) (taken in double, rounded once); ema_decay == 0 selects
+ * e = p bit for bit whatever the old e holds (inf, NaN).  0 <= ema_decay < 1, else WSR_EINVAL.  p, m, v - and with
+ * clipping the written-back g and *total_norm_out - are those of wsr_adam_multi / wsr_adam_multi_clip bit for bit.
+ * p, g, m, v take the float4 path exactly when they do in wsr_adam_multi (all four 16-byte aligned); the shadow moves
+ * as float4 there when it is aligned too, element by element otherwise - the same arithmetic either way.             */
+int wsr_adam_multi_ema(const wsr_adam_job_t* jobs_dev, float* const* ema_dev, int32_t n_jobs, double lr, double beta1,
+                       double beta2, double eps, double weight_decay, int32_t step, double ema_decay, void* stream);
+int wsr_adam_multi_clip_ema(const wsr_adam_job_t* jobs_dev, float* const* ema_dev, int32_t n_jobs,
+                            const float* partials, double max_norm, double lr, double beta1, double beta2, double eps,
+                            double weight_decay, int32_t step, double ema_decay, float* total_norm_out, void* stream);
 
 /* ABI 9 - train-mode statistics of ALL batch groups of a BatchNorm3d layer (torch_blocks.py:20-25; the groups are the
  * reference's separate calls D(real), D(fake) of one iteration, wind_field_GAN_3D.py:247-304, batched into one pass) in four
