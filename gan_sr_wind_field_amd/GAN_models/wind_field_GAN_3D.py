@@ -79,8 +79,9 @@ class wind_field_GAN_3D(BaseGAN):
         self.device_check = ""
         self.batch_size = 1
         dev = getattr(cfg, "device", self.device)
-        self.max_diff_squared = torch.tensor(4.0, device=dev)  # HR is in [-1, 1]
-        self.epsilon_PSNR = torch.tensor(1e-8, device=dev)
+        self._max_diff_squared, self._epsilon_PSNR = 4.0, 1e-8  # (the same two as Python floats: no device read)
+        self.max_diff_squared = torch.tensor(self._max_diff_squared, device=dev)  # HR is in [-1, 1]
+        self.epsilon_PSNR = torch.tensor(self._epsilon_PSNR, device=dev)
         self.feature_extractor = None
         self.dp = None  # set by dist.attach()
         self._ema_cfg = None  # the [EMA] section when it is present (training only)
@@ -591,10 +592,30 @@ class wind_field_GAN_3D(BaseGAN):
             return
         fake_HR = self.update_G(LR, HR, Z, it, False)
         self.update_D(HR, fake_HR, it, False)
+        if self.cfg.eval.on and HR.is_cuda:
+            self._device_val_metrics(LR, HR, fake_HR)
+            return
         self.metrics_dict["val_PSNR"], self.metrics_dict["Trilinear_PSNR"] = compute_PSNR_for_SR_and_trilinear(
             LR, HR, fake_HR, self.max_diff_squared, self.epsilon_PSNR, interpolate=True, device=self.device,
             scale=self.cfg.scale)
         self.metrics_dict["trilinear_pix_loss"] = self.pixel_criterion(HR, _trilinear(LR, self.cfg.scale))
+
+    def _device_val_metrics(self, LR, HR, fake_HR) -> None:
+        """[EVAL] device_metrics: the two PSNRs and the baseline's pixel loss of a validation batch from ONE
+        ``hip_ops.field_metrics`` launch (the baseline is blended on the fly inside it); the values stay device tensors
+        (float64) - nothing here waits for the device."""
+        from .. import hip_ops
+        from ..test import metrics_from_sums
+
+        sums = hip_ops.field_metrics(HR.contiguous(), fake_HR.detach().float().contiguous(), LR=LR.contiguous(),
+                                     scale=self.cfg.scale).sum(dim=0)
+        nvox = HR.shape[0] * HR.shape[2] * HR.shape[3] * HR.shape[4]
+        if self.pixel_criterion is None:  # (the host path fails on the same configuration: no pixel loss to report)
+            raise TypeError("the baseline's pixel loss needs [TRAINING] pixel_criterion = l1 or l2")
+        m = metrics_from_sums(sums.unbind(), nvox, 1.0, self._max_diff_squared, self._epsilon_PSNR)
+        self.metrics_dict["val_PSNR"], self.metrics_dict["Trilinear_PSNR"] = m["PSNR"], m["PSNR_trilinear"]
+        l2 = str(self.cfg.training.pixel_criterion).lower() == "l2"
+        self.metrics_dict["trilinear_pix_loss"] = sums[1] / (3 * nvox) if l2 else m["old_pix_trilinear"]
 
     def optimize_parameters(self, LR, HR, Z, it):
         self.compute_losses_and_optimize(LR, HR, Z, it, training_iteration=True)

@@ -23,6 +23,7 @@ EXPORTS = [
     "wsr_planar_to_ndhwc", "wsr_ndhwc_to_planar", "wsr_zfold", "wsr_zunfold", "wsr_wind_gradient", "wsr_wind_gradient_bwd", "wsr_plane_sum", "wsr_linear_rows", "wsr_physics_loss_workspace_floats", "wsr_physics_loss_stats", "wsr_physics_loss_bwd", "wsr_bn_stats", "wsr_bn_mean", "wsr_bn_shard_stats", "wsr_bn_combine_shards", "wsr_bn_finalize", "wsr_bn_apply_lrelu", "wsr_bn_bwd_reduce",
     "wsr_bn_bwd_apply", "wsr_adam_step", "wsr_adam_multi", "wsr_gather_batch", "wsr_grad_sqnorm_multi",
     "wsr_adam_multi_clip", "wsr_adam_multi_ema", "wsr_adam_multi_clip_ema",
+    "wsr_trilinear_xy", "wsr_field_metrics", "wsr_column_interp",
 ]
 
 
@@ -143,6 +144,9 @@ def lib() -> C.CDLL:
         "wsr_adam_multi_clip": [vp, i32, vp] + [C.c_double] * 6 + [i32, vp, vp],   # additive export
         "wsr_adam_multi_ema": [vp, vp, i32] + [C.c_double] * 5 + [i32, C.c_double, vp],   # additive export
         "wsr_adam_multi_clip_ema": [vp, vp, i32, vp] + [C.c_double] * 6 + [i32, C.c_double, vp, vp],   # additive export
+        "wsr_trilinear_xy": [vp, i32, i32, i32, i32, i32, i32, vp, vp],   # additive export
+        "wsr_field_metrics": [vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp],   # additive export
+        "wsr_column_interp": [vp, vp, vp, i32, i32, i64, i32, vp, vp],   # additive export
     }
     for name, argtypes in sig.items():
         fn = getattr(L, name)

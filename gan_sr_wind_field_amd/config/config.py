@@ -15,6 +15,10 @@ Extension (optional keys, defaults keep reference behaviour):
   [EMA]     decay / start_iter / validate_with_ema / test_with_ema
             exponential moving average of the generator's weights, updated inside the optimizer step
             (tools/table_adam.py), saved as G_ema_{it}.pth, used for validation and --test
+  [EVAL]    device_metrics / batch_size / reverse_interpolate
+            validation and --test take the trilinear baseline and the error sums from the HIP kernels
+            (csrc/eval_metrics.hip); --test runs batch_size fields per launch and can write the metrics on the raw
+            terrain-following levels
 """
 from __future__ import annotations
 
@@ -346,6 +350,43 @@ class EmaConfig(IniConfig):
         return "[EMA]\n" + "".join(f"{k} = {getattr(self, k)}\n" for k, _ in self._schema)
 
 
+class EvalConfig(IniConfig):
+    """[EVAL] (extension): device-side evaluation (csrc/eval_metrics.hip); absent section = off, and not printed by
+    ``asINI``.  ``device_metrics``: the validation batches and ``run.py --test`` take the trilinear baseline and the
+    error sums from the HIP kernels; ``batch_size``: fields per generator forward / metrics launch of ``--test``;
+    ``reverse_interpolate``: ``--test`` also writes the ``*_reverse_interpolate.csv`` files."""
+
+    present: bool = False
+    device_metrics: bool = True
+    batch_size: int = 8
+    reverse_interpolate: bool = False
+    _schema = (("device_metrics", _B), ("batch_size", _I), ("reverse_interpolate", _B))
+
+    def setEvalConfig(self, section):
+        """``section`` None (no [EVAL] in the file) restores the defaults and switches the section off."""
+        self.present = section is not None
+        for key, kind in self._schema:
+            val = None if section is None else _read(section, key, kind)
+            setattr(self, key, getattr(EvalConfig, key) if val is None else val)
+
+    def validate(self, interpolate_z) -> None:
+        if not self.present:
+            return
+        if self.batch_size < 1:
+            raise ValueError(f"[EVAL] batch_size must be >= 1, not {self.batch_size}")
+        if self.reverse_interpolate and not interpolate_z:
+            raise ValueError("[EVAL] reverse_interpolate = True needs [GAN] interpolate_z = True: the metrics on the "
+                             "raw levels exist only for data that was interpolated onto flat levels")
+
+    @property
+    def on(self) -> bool:
+        """the device kernels replace the host evaluation"""
+        return bool(self.present and self.device_metrics)
+
+    def __str__(self) -> str:
+        return "[EVAL]\n" + "".join(f"{k} = {getattr(self, k)}\n" for k, _ in self._schema)
+
+
 class Config(IniConfig):
     name: str = "default_name"
     model: str = "default_model"
@@ -370,6 +411,7 @@ class Config(IniConfig):
     data: DataConfig = DataConfig()
     grad_clip: GradClipConfig = GradClipConfig()
     ema: EmaConfig = EmaConfig()
+    eval: EvalConfig = EvalConfig()
     compute_dtype: str = "fp32"
     is_train: bool
     is_use: bool
@@ -400,6 +442,8 @@ class Config(IniConfig):
         self.grad_clip.validate(self.generator.max_norm)
         self.ema.setEmaConfig(parser["EMA"] if parser.has_section("EMA") else None)
         self.ema.validate()
+        self.eval.setEvalConfig(parser["EVAL"] if parser.has_section("EVAL") else None)
+        self.eval.validate(self.gan_config.interpolate_z)
 
     def setBaseConfig(self, base):
         self.name = base.get("name")
@@ -431,4 +475,6 @@ class Config(IniConfig):
             out += "\n" + str(self.grad_clip)
         if getattr(self.ema, "present", False):
             out += "\n" + str(self.ema)
+        if getattr(self.eval, "present", False):
+            out += "\n" + str(self.eval)
         return out

@@ -1031,3 +1031,90 @@ def gather_batch(store: Tensor, desc: Tensor, cin: int, s: int, slice_size: int)
     check(_lib.lib().wsr_gather_batch(_p(store), N, _p(desc), B, cin, s, slice_size, X, Y, NZ, _p(lr), _p(hr), _p(z),
                                       _stream()), "gather_batch")
     return lr, hr, z
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# device-side evaluation ([EVAL] device_metrics; csrc/eval_metrics.hip)
+# ---------------------------------------------------------------------------------------------------------------------
+FIELD_METRICS_SUMS = 7        # WSR_FIELD_METRICS_SUMS
+FIELD_METRICS_MAX_ROWS = 2048  # WSR_FIELD_METRICS_MAX_ROWS
+
+
+def _planar5(name: str, what: str, t: Tensor, min_c: int = 1) -> None:
+    if t.dtype != torch.float32 or t.dim() != 5 or not t.is_contiguous() or t.shape[1] < min_c or t.numel() == 0:
+        raise ValueError(f"{name} wants {what} as a contiguous fp32 (B, C >= {min_c}, X, Y, NZ) tensor, got "
+                         f"{t.dtype} {tuple(t.shape)}")
+
+
+def trilinear_xy(LR: Tensor, s: int) -> Tensor:
+    """The trilinear baseline ``F.interpolate(LR[:, :3], scale_factor=(s, s, 1), mode="trilinear",
+    align_corners=True)`` in one launch: ``LR`` fp32 (B, Cin >= 3, Xl, Yl, NZ) -> (B, 3, Xl * s, Yl * s, NZ); only
+    channels 0..2 are read (``wsr_trilinear_xy``)."""
+    _need_cuda(LR)
+    _planar5("trilinear_xy", "LR", LR, 3)
+    s = int(s)
+    if s < 1:
+        raise ValueError(f"trilinear_xy wants a scale >= 1, not {s}")
+    B, cin, Xl, Yl, NZ = LR.shape
+    out = torch.empty((B, 3, Xl * s, Yl * s, NZ), dtype=torch.float32, device=LR.device)
+    check(_lib.lib().wsr_trilinear_xy(_p(LR), B, cin, Xl, Yl, NZ, s, _p(out), _stream()), "trilinear_xy")
+    return out
+
+
+def field_metrics(HR: Tensor, SR: Tensor, *, LR: Optional[Tensor] = None, scale: Optional[int] = None,
+                  TL: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """Seven sums per sample over channels 0..2 of ``HR`` and ``SR`` (B, C >= 3, X, Y, NZ) -> float64 (B, 7):
+    sum (HR-SR)^2, sum (HR-TL)^2, sum |HR-SR|, sum |HR-TL| over components; sum ||HR-SR||, sum ||HR-TL||, sum ||HR||
+    over voxels.  The baseline is the tensor ``TL`` (B, C >= 3, X, Y, NZ), or made on the fly from ``LR``
+    (B, C >= 3, X / scale, Y / scale, NZ) and ``scale`` - the bits of ``trilinear_xy``, never written to memory.  One
+    pass, no atomics: the same bits on every call.  ``out``: a float64 (B, 7) slice to write into
+    (``wsr_field_metrics``)."""
+    if (TL is None) == (LR is None) or (LR is not None and scale is None):
+        raise ValueError("field_metrics wants either TL= or LR= and scale=")
+    _need_cuda(HR, SR, LR, TL, out)
+    _planar5("field_metrics", "HR", HR, 3)
+    _planar5("field_metrics", "SR", SR, 3)
+    B, _, X, Y, NZ = HR.shape
+    if (SR.shape[0],) + tuple(SR.shape[2:]) != (B, X, Y, NZ):
+        raise ValueError(f"field_metrics: SR {tuple(SR.shape)} does not match HR {tuple(HR.shape)}")
+    s = 0
+    if TL is not None:
+        _planar5("field_metrics", "TL", TL, 3)
+        if (TL.shape[0],) + tuple(TL.shape[2:]) != (B, X, Y, NZ):
+            raise ValueError(f"field_metrics: TL {tuple(TL.shape)} does not match HR {tuple(HR.shape)}")
+    else:
+        _planar5("field_metrics", "LR", LR, 3)
+        s = int(scale)
+        if s < 1 or (LR.shape[0], LR.shape[2] * s, LR.shape[3] * s, LR.shape[4]) != (B, X, Y, NZ):
+            raise ValueError(f"field_metrics: LR {tuple(LR.shape)} x{s} does not match HR {tuple(HR.shape)}")
+    if out is None:
+        out = torch.empty((B, FIELD_METRICS_SUMS), dtype=torch.float64, device=HR.device)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (B, FIELD_METRICS_SUMS) or not out.is_contiguous():
+        raise ValueError(f"field_metrics wants out as a contiguous float64 ({B}, 7) tensor, got {out.dtype} "
+                         f"{tuple(out.shape)}")
+    partials = torch.empty(B * FIELD_METRICS_MAX_ROWS * FIELD_METRICS_SUMS, dtype=torch.float32, device=HR.device)
+    check(_lib.lib().wsr_field_metrics(_p(HR), HR.shape[1], _p(SR), SR.shape[1], _p(TL), 0 if TL is None else TL.shape[1],
+                                       _p(LR), 0 if LR is None else LR.shape[1], s, B, X, Y, NZ, _p(partials), _p(out),
+                                       _stream()), "field_metrics")
+    return out
+
+
+def column_interp(vals: Tensor, z_src: Tensor, z_dst: Tensor) -> Tensor:
+    """``np.interp(z_dst[col], z_src[col], vals[c][col])`` for every column of ``vals`` fp32 (B, C, X, Y, NZ) with source
+    and query levels (B, 1, X, Y, NZ), NZ <= 128: queries outside the source range get the end values, slope and blend
+    are evaluated in double and rounded once to fp32 (``process_data.reverse_interpolate_z_axis`` in one launch;
+    ``wsr_column_interp``)."""
+    _need_cuda(vals, z_src, z_dst)
+    _planar5("column_interp", "vals", vals)
+    _planar5("column_interp", "z_src", z_src)
+    _planar5("column_interp", "z_dst", z_dst)
+    B, C, X, Y, NZ = vals.shape
+    if tuple(z_src.shape) != (B, 1, X, Y, NZ) or tuple(z_dst.shape) != (B, 1, X, Y, NZ):
+        raise ValueError(f"column_interp wants levels ({B}, 1, {X}, {Y}, {NZ}), got {tuple(z_src.shape)} and "
+                         f"{tuple(z_dst.shape)}")
+    if NZ > 128:
+        raise ValueError(f"column_interp stages one column in LDS: at most 128 levels, not {NZ}")
+    out = torch.empty_like(vals)
+    check(_lib.lib().wsr_column_interp(_p(vals), _p(z_src), _p(z_dst), B, C, X * Y, NZ, _p(out), _stream()),
+          "column_interp")
+    return out

@@ -167,7 +167,8 @@ def main(argv=None) -> None:
         cfg.env.generator_load_path = ema_path
     if cfg.is_test or cfg.is_use:
         log.info("run.py: starting testing")
-        test(cfg, dataset_test)
+        # ([EVAL] reverse_interpolate: also the metrics on the raw terrain-following levels)
+        test(cfg, dataset_test, reverse_interpolate=bool(cfg.eval.present and cfg.eval.reverse_interpolate))
         log.info("run.py: finished testing")
     log.info(f"run.py: log file location: {cfg.env.status_log_file}  run file location: {cfg.env.train_log_file}")
 

@@ -8,10 +8,20 @@ Artefacts (relative to the working directory / the run folder, as in the referen
     ./test_output/<cfg.name>____metrics_reverse_interpolate.csv    (+ averages_reverse_interpolate.csv)
         when ``interpolate_z`` and ``reverse_interpolate``: metrics on the raw terrain-following levels
     <run folder>/fields/test_fields_<name>.pkl                     HR / SR / TL / LR / Z every log_period-th batch
+
+With ``[EVAL] device_metrics = True`` on a GPU the loop runs ``batch_size`` fields per generator forward and takes the
+seven error sums of every field from ONE ``hip_ops.field_metrics`` launch per batch (the trilinear baseline is blended
+on the fly inside it); the rows stay in a device table that is read once per ``log_period`` batches and at the end, and
+``metrics_from_sums`` turns them into the nine metrics on the host, in double.  SR and the baseline leave the device only
+for the pickled fields (``log_period`` counts batches: every ``log_period``-th batch pickles all of its fields, a larger
+set than without the section).  With ``reverse_interpolate`` the re-levelling is ``hip_ops.column_interp``.  Same CSV files,
+headers and row order; the values differ in their low digits (another summation order).  On a CPU device the section keeps the
+composed torch path below.
 """
 from __future__ import annotations
 
 import logging
+import math
 import os
 import pickle as pkl
 
@@ -42,6 +52,26 @@ def field_metrics(HR: torch.Tensor, SR: torch.Tensor, trilinear: torch.Tensor, U
     }
 
 
+def metrics_from_sums(sums_row, nvox, UVW_MAX, max_diff_squared=4.0, eps=1e-8) -> dict:
+    """The nine ``METRIC_NAMES`` from the seven sums of ``hip_ops.field_metrics`` over ``nvox`` voxels (X * Y * Z times
+    the number of fields summed): ``sums_row`` = sum (HR-SR)^2, sum (HR-TL)^2, sum |HR-SR|, sum |HR-TL| over the three
+    components, sum ||HR-SR||, sum ||HR-TL||, sum ||HR|| over voxels.  The formulas of ``field_metrics`` above and of
+    ``calculate_PSNR``, defined once for the evaluation loop and the validation batches: Python floats (double) in,
+    Python floats out; 0-d tensors in (a validation batch, which must not synchronise), 0-d tensors out."""
+    sq, sq_tl, ab, ab_tl, ln, ln_tl, ln_hr = sums_row
+    log10 = torch.log10 if torch.is_tensor(sq) else math.log10
+
+    def psnr(s):
+        return 10.0 * log10(max_diff_squared / (s / nvox + eps))
+
+    return {
+        "PSNR": psnr(sq), "PSNR_trilinear": psnr(sq_tl),
+        "relative_error": ln / ln_hr, "pix": ln / nvox * UVW_MAX, "trilinear_pix": ln_tl / nvox * UVW_MAX,
+        "relative_error_trilinear": ln_tl / ln_hr, "average_wind_speed": ln_hr / nvox * UVW_MAX,
+        "old_pix": ab / (3 * nvox) * UVW_MAX, "old_pix_trilinear": ab_tl / (3 * nvox) * UVW_MAX,
+    }
+
+
 def write_metrics(HR, SR, trilinear, field_name, dest_file, UVW_MAX):
     m = field_metrics(HR, SR, trilinear, UVW_MAX)
     dest_file.write(f"{field_name}," + ",".join(str(m[k]) for k in METRIC_NAMES) + "\n")
@@ -64,11 +94,85 @@ def _header(path: str, line: str) -> None:
             f.write(line + "\n")
 
 
+def _host_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev):
+    """one field at a time; baseline, re-levelling and metrics on the host (the reference's loop)"""
+    dev = cfg.device
+    for j, (LR, HR, Z, names, HR_raw, Z_raw) in enumerate(loader):
+        TL = nn.functional.interpolate(LR[:, :3], scale_factor=(cfg.scale, cfg.scale, 1), mode="trilinear",
+                                       align_corners=True)
+        for i in range(LR.shape[0]):
+            with torch.no_grad():
+                SR_i = gan.G(LR[i:i + 1].to(dev, non_blocking=True), Z[i:i + 1].to(dev, non_blocking=True)).cpu()
+            HR_i, TL_i = HR[i:i + 1, :3], TL[i:i + 1]
+            if rev:  # back onto the raw terrain-following levels of every column
+                SR_r = reverse_interpolate_z_axis(SR_i.numpy(), Z_raw[i:i + 1].numpy(), Z[i:i + 1].numpy())
+                TL_r = reverse_interpolate_z_axis(TL_i.numpy(), Z_raw[i:i + 1].numpy(), Z[i:i + 1].numpy())
+                vals = write_metrics(HR_raw[i:i + 1, :3], SR_r, TL_r, names[i], out_rev, uvw)
+                for k, v in zip(METRIC_NAMES, vals):
+                    avg_rev[k] += v / n
+            vals = write_metrics(HR_i, SR_i, TL_i, names[i], out, uvw)
+            for k, v in zip(METRIC_NAMES, vals):
+                avg[k] += v / n
+            if j % cfg.training.log_period == 0:
+                write_fields(LR[i], HR[i], SR_i[0], TL[i], Z[i], cfg.env.this_runs_folder, names[i],
+                             HR_raw[i] if rev else None, Z_raw[i] if rev else None, None)
+
+
+def _device_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev):
+    """[EVAL] device_metrics: one generator forward and one metrics launch per batch; the (B, 7) rows wait in a device
+    table and are read once per ``log_period`` batches and at the end"""
+    from . import hip_ops
+
+    dev, s = cfg.device, cfg.scale
+    pending = []  # (names, nvox, sums (B, 7), sums on the raw levels (B, 7) or None) of the batches not yet written
+
+    def flush():
+        if not pending:
+            return
+        table = torch.cat([t for p in pending for t in p[2:] if t is not None]).cpu().tolist()  # the ONE read
+        at = 0
+        for names, nvox, _, raw in pending:
+            for dest, acc, present in ((out, avg, True), (out_rev, avg_rev, raw is not None)):
+                if not present:
+                    continue
+                for name in names:
+                    m = metrics_from_sums(table[at], nvox, uvw)
+                    at += 1
+                    dest.write(f"{name}," + ",".join(str(m[k]) for k in METRIC_NAMES) + "\n")
+                    for k in METRIC_NAMES:
+                        acc[k] += m[k] / n
+        pending.clear()
+
+    for j, (LR, HR, Z, names, HR_raw, Z_raw) in enumerate(loader):
+        LR_d, HR_d, Z_d = (t.to(dev, non_blocking=True).contiguous() for t in (LR, HR, Z))
+        with torch.no_grad():
+            SR_d = gan.G(LR_d, Z_d).float().contiguous()
+        nvox = HR.shape[2] * HR.shape[3] * HR.shape[4]
+        sums = hip_ops.field_metrics(HR_d, SR_d, LR=LR_d, scale=s)  # (the baseline is blended inside, never stored)
+        keep = j % cfg.training.log_period == 0
+        TL_d = hip_ops.trilinear_xy(LR_d, s) if rev or keep else None
+        sums_raw = None
+        if rev:  # back onto the raw terrain-following levels of every column, metrics against the raw truth
+            raw_d, zraw_d = (t.to(dev, non_blocking=True).contiguous() for t in (HR_raw, Z_raw))
+            sums_raw = hip_ops.field_metrics(raw_d, hip_ops.column_interp(SR_d, Z_d, zraw_d),
+                                             TL=hip_ops.column_interp(TL_d, Z_d, zraw_d))
+        # (per field: the sums in the order the rows are written - all of `out`, then all of `out_rev`, per batch)
+        pending.append((list(names), nvox, sums, sums_raw))
+        if keep:
+            SR_h, TL_h = SR_d.cpu(), TL_d.cpu()
+            for i in range(LR.shape[0]):
+                write_fields(LR[i], HR[i], SR_h[i], TL_h[i], Z[i], cfg.env.this_runs_folder, names[i],
+                             HR_raw[i] if rev else None, Z_raw[i] if rev else None, None)
+            flush()
+    flush()
+
+
 def test(cfg, dataset_test, reverse_interpolate: bool = False):
     log = logging.getLogger("status")
     if cfg.dataset_test is None:
         raise ValueError("Test dataset not supplied")
-    loader = torch.utils.data.DataLoader(dataset_test, batch_size=1, shuffle=False,
+    loader = torch.utils.data.DataLoader(dataset_test, batch_size=cfg.eval.batch_size if cfg.eval.present else 1,
+                                         shuffle=False,
                                          num_workers=min(8, os.cpu_count() or 1), pin_memory=True)
     if cfg.model.lower() != "wind_field_gan_3d":
         raise NotImplementedError(f"only wind_field_GAN_3D is supported - not {cfg.model}")
@@ -97,25 +201,10 @@ def test(cfg, dataset_test, reverse_interpolate: bool = False):
     with open(metrics_path, "w") as out, (open(rev_path, "w") if rev else open(os.devnull, "w")) as out_rev:
         out.write(cols + "\n")
         out_rev.write(cols + "\n")
-        for j, (LR, HR, Z, names, HR_raw, Z_raw) in enumerate(loader):
-            TL = nn.functional.interpolate(LR[:, :3], scale_factor=(cfg.scale, cfg.scale, 1), mode="trilinear",
-                                           align_corners=True)
-            for i in range(LR.shape[0]):
-                with torch.no_grad():
-                    SR_i = gan.G(LR[i:i + 1].to(dev, non_blocking=True), Z[i:i + 1].to(dev, non_blocking=True)).cpu()
-                HR_i, TL_i = HR[i:i + 1, :3], TL[i:i + 1]
-                if rev:  # back onto the raw terrain-following levels of every column
-                    SR_r = reverse_interpolate_z_axis(SR_i.numpy(), Z_raw[i:i + 1].numpy(), Z[i:i + 1].numpy())
-                    TL_r = reverse_interpolate_z_axis(TL_i.numpy(), Z_raw[i:i + 1].numpy(), Z[i:i + 1].numpy())
-                    vals = write_metrics(HR_raw[i:i + 1, :3], SR_r, TL_r, names[i], out_rev, uvw)
-                    for k, v in zip(METRIC_NAMES, vals):
-                        avg_rev[k] += v / n
-                vals = write_metrics(HR_i, SR_i, TL_i, names[i], out, uvw)
-                for k, v in zip(METRIC_NAMES, vals):
-                    avg[k] += v / n
-                if j % cfg.training.log_period == 0:
-                    write_fields(LR[i], HR[i], SR_i[0], TL[i], Z[i], cfg.env.this_runs_folder, names[i],
-                                 HR_raw[i] if rev else None, Z_raw[i] if rev else None, None)
+        if cfg.eval.on and torch.device(dev).type == "cuda":
+            _device_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev)
+        else:
+            _host_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev)
     with open("./test_output/averages.csv", "a") as f:
         f.write(cfg.name + "," + ",".join(str(avg[k]) for k in METRIC_NAMES) + "\n")
     for k in METRIC_NAMES:

@@ -14,7 +14,10 @@ training and validation splits are loaded into device memory once and each batch
 split and the ``DistributedSampler`` drives the descriptor loader).  With ``[EMA]`` the generator keeps a moving average
 of its weights (updated inside its optimizer step), ``G_ema_{it}.pth`` is saved beside ``G_{it}.pth`` and, with
 ``validate_with_ema``, the validation epochs run on the averaged weights (``gan.ema_scope()``); the replicas of a
-data-parallel run are bit-identical, hence so are their averages: no collective, rank 0 saves.
+data-parallel run are bit-identical, hence so are their averages: no collective, rank 0 saves.  With ``[EVAL]
+device_metrics = True`` a validation batch takes its PSNRs and the baseline's pixel loss from one ``hip_ops.field_metrics``
+launch, the epoch's running means stay device tensors and are read once, and the image sample's baseline comes from
+``hip_ops.trilinear_xy``; every rank still runs the whole split.
 """
 from __future__ import annotations
 
@@ -190,13 +193,22 @@ def _validate(cfg, gan, dataloader_val, dataset_train, it, tb, status_logger, le
     D_vals = {k: 0.0 for k in gan.get_D_loss_dict_ref()}
     M_vals = {k: 0.0 for k in gan.get_metrics_dict_ref()}
     n = len(dataloader_val)
+    on_device = cfg.eval.on and torch.device(dev).type == "cuda"
     for LR, HR, Z in dataloader_val:
         LR, HR, Z = (t.to(dev, non_blocking=True) for t in (LR, HR, Z))
         gan.validation(LR, HR, Z, it)
         for acc, src in ((G_vals, gan.get_G_val_loss_dict_ref()), (D_vals, gan.get_D_loss_dict_ref()),
                          (M_vals, gan.get_metrics_dict_ref())):
             for k, v in src.items():
-                acc[k] += float(v) / n
+                if on_device:  # [EVAL]: the running means stay on the device, nothing is read inside the epoch
+                    acc[k] = acc[k] + torch.as_tensor(v, device=dev).detach().double() / n
+                else:
+                    acc[k] += float(v) / n
+    if on_device:  # the ONE read of the validation epoch
+        keys = [(acc, k) for acc in (G_vals, D_vals, M_vals) for k in acc]
+        flat = torch.stack([torch.as_tensor(acc[k], dtype=torch.float64, device=dev).reshape(()) for acc, k in keys])
+        for (acc, k), v in zip(keys, flat.cpu().tolist()):
+            acc[k] = v
     if not lead:
         return
     b = int(torch.randint(LR.shape[0], size=(1,)))
@@ -204,8 +216,12 @@ def _validate(cfg, gan, dataloader_val, dataset_train, it, tb, status_logger, le
     LR_i, Z_i = LR[b:b + 1], Z[b:b + 1]
     with torch.no_grad():
         SR_i = (uvw * gan.G(LR_i, Z_i)).squeeze(0)
-        TL_i = (uvw * nn.functional.interpolate(LR_i[:, :3], scale_factor=(cfg.scale, cfg.scale, 1), mode="trilinear",
-                                                align_corners=True)).squeeze(0)
+        if on_device:
+            from . import hip_ops
+            TL_i = (uvw * hip_ops.trilinear_xy(LR_i.contiguous(), cfg.scale)).squeeze(0)
+        else:
+            TL_i = (uvw * nn.functional.interpolate(LR_i[:, :3], scale_factor=(cfg.scale, cfg.scale, 1),
+                                                    mode="trilinear", align_corners=True)).squeeze(0)
     imgs = {"HR": (uvw * HR[b]).cpu().numpy(), "SR": SR_i.cpu().numpy(), "BC": TL_i.cpu().numpy(),
             "LR": (uvw * LR_i[0, :3]).cpu().numpy()}
     if cfg.use_tensorboard_logger:

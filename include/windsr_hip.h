@@ -536,6 +536,34 @@ int wsr_ragan_loss(const float* u, const float* v, const float* lu, const float*
 int wsr_gather_batch(const float* store, int64_t n_samples, const int32_t* desc, int32_t B, int32_t Cin, int32_t s,
                      int32_t S, int32_t X, int32_t Y, int32_t NZ, float* lr, float* hr, float* z, void* stream);
 
+/* ---- device-side evaluation ([EVAL] device_metrics; csrc/eval_metrics.hip) ---------------------------
+ * Everything fp32 planar (B, C, X, Y, NZ), z innermost; replaces the ATen / numpy work of test.py:101-115 and
+ * wind_field_GAN_3D.py:594-597 (F.interpolate, about fifteen reductions per field, np.interp per column).
+ *
+ * wsr_trilinear_xy: tl (B, 3, Xl*s, Yl*s, NZ) = F.interpolate(lr[:, :3], scale_factor=(s, s, 1), mode="trilinear",
+ * align_corners=True) of lr (B, Cin >= 3, Xl, Yl, NZ); only channels 0..2 of lr are read.
+ *
+ * wsr_field_metrics: sums (B, WSR_FIELD_METRICS_SUMS) doubles per sample over channels 0..2 of hr (B, hr_c, X, Y, NZ) and
+ * sr (B, sr_c, X, Y, NZ): sum (hr-sr)^2, sum (hr-tl)^2, sum |hr-sr|, sum |hr-tl| over components, then sum ||hr-sr||,
+ * sum ||hr-tl||, sum ||hr|| over voxels (vector lengths).  The baseline is EITHER the tensor tl (B, tl_c >= 3, X, Y, NZ)
+ * with lr = NULL, OR made on the fly from lr (B, lr_c >= 3, X/s, Y/s, NZ) and s with tl = NULL (same bits as
+ * wsr_trilinear_xy; never written to memory).  partials: workspace of B * WSR_FIELD_METRICS_MAX_ROWS *
+ * WSR_FIELD_METRICS_SUMS floats.  No atomics: a fixed summation order, the same bits on every call.
+ *
+ * wsr_column_interp: out[b, c, col, :] = np.interp(z_dst[b, col, :], z_src[b, col, :], vals[b, c, col, :]) for the
+ * ncols = X * Y columns of every sample; z_src / z_dst (B, 1, X, Y, NZ), vals / out (B, C, X, Y, NZ), NZ <= 128.
+ * z_src increasing along z.  Queries outside the source range get the end values; slope and blend are evaluated in
+ * double and rounded once to fp32.                                                                              */
+#define WSR_FIELD_METRICS_SUMS 7
+#define WSR_FIELD_METRICS_MAX_ROWS 2048
+int wsr_trilinear_xy(const float* lr, int32_t B, int32_t Cin, int32_t Xl, int32_t Yl, int32_t NZ, int32_t s, float* tl,
+                     void* stream);
+int wsr_field_metrics(const float* hr, int32_t hr_c, const float* sr, int32_t sr_c, const float* tl, int32_t tl_c,
+                      const float* lr, int32_t lr_c, int32_t s, int32_t B, int32_t X, int32_t Y, int32_t NZ,
+                      float* partials, double* sums, void* stream);
+int wsr_column_interp(const float* vals, const float* z_src, const float* z_dst, int32_t B, int32_t C, int64_t ncols,
+                      int32_t NZ, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
