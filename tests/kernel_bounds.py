@@ -8,6 +8,9 @@ References
 (``torch.nn.functional.conv3d`` / autograd) and return ``(ref, A)``: ``A`` is the same operation applied to
 ``|operands|`` (and ``|alpha|``, ``|beta|*|res|``, ``|bias|``, ``|mask|``) - the sum of the magnitudes of every term
 that enters an element.  Tensors are logical: activations ``(B, C, X, Y, Z)``, filters ``(Cout, Cin, KX, KY, KZ)``.
+``ref_pointwise`` is the voxel-local (1x1x1) operation with the streaming kernel's whole epilogue on ``(nvox, C)``
+matrices: two residuals limited to the first ``res_c1`` produced channels and a LeakyReLU-backward mask on a channel
+window.
 
 The bound
 ---------
@@ -38,6 +41,12 @@ is gamma_K ~ K * 2^-24 * A; rounding errors of independent operands behave like 
 is C * sqrt(K) * 2^-24 * A, and lambda = 16 leaves a wide margin over C.  A bf16 store adds at most 2^-8 of the stored
 value.  LeakyReLU is 1-Lipschitz, so an error in front of it passes through at most unchanged.  The 2^-100 only keeps
 the bound positive where ref and A are both zero.
+
+The streaming 1x1x1 kernel (``ref_pointwise``, K = reduction channels + 3) starts its accumulators from
+bias + (beta / alpha) * res + (beta2 / alpha) * res2 and multiplies by alpha at the end: the quotient and the final
+product are two more fp32 roundings of terms that A already contains, which is what the "+ 3" pays for.  Its in-place
+and accumulating forms still store each element once - the accumulated values are read as exact bf16 operands, like
+any residual - so rho is paid once, on |ref|.
 
 A kernel bug that drops one tap at one voxel, loses one split or misplaces one channel chunk changes the elements it
 touches by a sizable fraction of A / sqrt(K), far above the bound; a whole-tensor relative L2 check averages such an
@@ -165,6 +174,42 @@ def ref_wgrad(x, gy, k, pad, *, ups=False, in_win=None):
         (g,) = torch.autograd.grad(F.conv3d(xx, w, None, 1, tuple(pad)), w, gg)
         out.append(g)
     return out[0], out[1]
+
+
+def _f32(v) -> float:
+    """a scalar as the C side receives it (``float`` across the ABI)"""
+    return float(torch.tensor(float(v), dtype=torch.float32))
+
+
+def ref_pointwise(x, w, *, bias=None, act=False, slope=0.2, alpha=1.0, res=None, beta=0.0, res_c1=None, res2=None,
+                  beta2=0.0, mask_y=None, mask_win=None, mask_slope=0.2):
+    """y = alpha * lrelu?(x @ w.T + bias) + beta * res[:, :c1] + beta2 * res2[:, :c1] on logical matrices: x (nvox, red),
+    w (n_out, red), the residuals (nvox, >= c1) with c1 = ``res_c1`` (default n_out; zero past it).  Columns
+    ``mask_win`` = [c0, c1) of y are then multiplied by 1 where ``mask_y`` (nvox, c1 - c0) > 0, else by ``mask_slope``.
+    The scalars are taken as the fp32 values the C side receives.  For the input gradient pass x = dy and w = W.T.
+    Returns (ref, A)."""
+    x, w = _d(x), _d(w)
+    alpha, beta, beta2, slope, mask_slope = (_f32(s) for s in (alpha, beta, beta2, slope, mask_slope))
+    v, a = x @ w.T, x.abs() @ w.abs().T
+    if bias is not None:
+        b = _d(bias).view(1, -1)
+        v, a = v + b, a + b.abs()
+    if act:
+        v = F.leaky_relu(v, slope)
+    v, a = alpha * v, abs(alpha) * a
+    c1 = v.shape[1] if res_c1 is None else min(res_c1, v.shape[1])
+    for r, s in ((res, beta), (res2, beta2)):
+        if r is not None:
+            r = _d(r)[:, :c1]
+            v[:, :c1] += s * r
+            a[:, :c1] += abs(s) * r.abs()
+    if mask_y is not None:
+        m0, m1 = mask_win
+        m = torch.where(_d(mask_y) > 0, 1.0, mask_slope).to(torch.float64)
+        assert m.shape == (v.shape[0], m1 - m0), (tuple(m.shape), mask_win)
+        v[:, m0:m1] *= m
+        a[:, m0:m1] *= m.abs()
+    return v, a
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -2,6 +2,7 @@
 for CPU emulations of the kernels' arithmetic (not too tight), it rejects small local errors that the whole-tensor
 rel-L2 tolerances of the kernel tests accept (not too loose), and guarded buffers report a single stray write."""
 import math
+import re
 
 import pytest
 import torch
@@ -252,3 +253,169 @@ def test_guards_report_a_single_stray_write(dt):
         h.base[5] = float("nan")
         with pytest.raises(AssertionError):
             kb.assert_guards_intact(h)
+
+
+# ---- the streaming 1x1x1 kernel's epilogue: a subtly wrong kernel fails the bound of ref_pointwise ---------------------
+
+def _bits(v):
+    """bf16 scalar from its bit pattern"""
+    return torch.tensor([v - 65536 if v >= 32768 else v], dtype=torch.int16).view(torch.bfloat16)[0]
+
+
+NEG_ZERO, POS_SUB, NEG_SUB = 0x8000, 0x0001, 0x8001
+
+
+class _Stream:
+    """an accumulating masked 128 -> 256 input gradient on 665 voxels (42 strips of 16, the last holds 9), every
+    epilogue term in use: dx = alpha * dy @ W + beta * acc[:, :128] + beta2 * res2[:, :128], columns [224, 256)
+    masked by the sign of columns [8, 40) of a saved output.  ``emul`` is the kernel's arithmetic in fp32 (accumulator
+    start bias + beta/alpha * res + beta2/alpha * res2, final * alpha, mask, one bf16 store) with switches for the
+    mistakes a kernel could make."""
+    nvox, red, n_out, c1, y_off, win = 665, 128, 256, 128, 8, (224, 256)
+    alpha, beta, beta2, slope = 0.2 * 0.3, 0.3, 1.0, 0.2
+
+    def __init__(self):
+        gen = torch.Generator().manual_seed(41)
+        self.dy = _bf(torch.randn(self.nvox, self.red, generator=gen))
+        self.w = _bf(torch.randn(self.n_out, self.red, generator=gen) / math.sqrt(self.red))
+        self.acc = _bf(torch.randn(self.nvox, self.n_out, generator=gen))    # dx's layout: the buffer's old contents
+        self.res2 = _bf(torch.randn(self.nvox, self.n_out, generator=gen))
+        self.y = torch.randn(self.nvox, 48, generator=gen).bfloat16()
+        plain = self.dy @ self.w.T
+        # (-0.0 and a positive subnormal where the unmasked value is large: a wrong classification must show)
+        self.v0, self.v1 = 37, 650
+        self.j0 = int(plain[self.v0, self.win[0]:].abs().argmax())
+        self.j1 = int(plain[self.v1, self.win[0]:].abs().argmax())
+        self.y[self.v0, self.y_off + self.j0] = _bits(NEG_ZERO)
+        self.y[self.v1, self.y_off + self.j1] = _bits(POS_SUB)
+        self.y[5, self.y_off + 3] = _bits(NEG_SUB)
+        self.y[6, self.y_off + 4] = 0.0
+        my = self.y[:, self.y_off:self.y_off + 32]
+        assert bool(my[self.v1, self.j1].double() > 0) and not bool(my[self.v0, self.j0].double() > 0)
+        self.ref, self.A = kb.ref_pointwise(self.dy, self.w, alpha=self.alpha, res=self.acc, beta=self.beta,
+                                            res_c1=self.c1, res2=self.res2, beta2=self.beta2, mask_y=my,
+                                            mask_win=self.win, mask_slope=self.slope)
+        self.bnd = kb.bound(self.ref, self.A, self.red + 3, kb.RHO_BF16)
+
+    def emul(self, *, res_c1=None, res2_c1=None, beta=None, beta2=None, win=None, y_off=None, flip=()):
+        f = lambda v: torch.tensor(float(v), dtype=torch.float32)
+        c1 = self.c1 if res_c1 is None else res_c1
+        c2 = self.c1 if res2_c1 is None else res2_c1
+        alpha = f(self.alpha)
+        rs1 = f(self.beta if beta is None else beta) / alpha
+        rs2 = f(self.beta2 if beta2 is None else beta2) / alpha
+        start = torch.zeros(self.nvox, self.n_out)
+        start[:, :c1] += rs1 * self.acc[:, :c1]
+        start[:, :c2] += rs2 * self.res2[:, :c2]
+        out = (start + self.dy @ self.w.T) * alpha
+        m0, m1 = self.win if win is None else win
+        yo = self.y_off if y_off is None else y_off
+        pos = self.y[:, yo:yo + (m1 - m0)].float() > 0
+        for v, j in flip:
+            pos[v, j] = ~pos[v, j]
+        out[:, m0:m1] *= torch.where(pos, torch.ones(()), f(self.slope))
+        return _bf(out)
+
+    def violations(self, got):
+        _, _, _, ratio = kb.check_within(got, self.ref, self.bnd)
+        return {(int(v), int(c)) for v, c in (ratio > 1.0).nonzero().tolist()}
+
+
+@pytest.fixture(scope="module")
+def stream():
+    return _Stream()
+
+
+def test_ref_pointwise_equals_the_1x1x1_conv_references():
+    """on a 1x1x1 conv ``ref_pointwise`` is ``ref_fwd`` / ``ref_dgrad`` of the same operands (scalars exact in fp32:
+    ``ref_pointwise`` takes them as the C side receives them)"""
+    gen = torch.Generator().manual_seed(9)
+    B, cin, cout, xyz = 2, 12, 7, (3, 4, 5)
+    x = torch.randn((B, cin) + xyz, generator=gen, dtype=f64)
+    w = torch.randn((cout, cin, 1, 1, 1), generator=gen, dtype=f64)
+    bias = torch.randn(cout, generator=gen, dtype=f64)
+    res = torch.randn((B, cout) + xyz, generator=gen, dtype=f64)
+    rows = lambda t: t.permute(0, 2, 3, 4, 1).reshape(-1, t.shape[1])
+    want, wa = kb.ref_fwd(x, w, (0, 0, 0), bias=bias, act=True, slope=0.25, alpha=0.5, res=res, beta=0.25)
+    got, ga = kb.ref_pointwise(rows(x), w.view(cout, cin), bias=bias, act=True, slope=0.25, alpha=0.5,
+                               res=rows(res), beta=0.25)
+    torch.testing.assert_close(got, rows(want), rtol=1e-12, atol=1e-12)
+    torch.testing.assert_close(ga, rows(wa), rtol=1e-12, atol=1e-12)
+    gy = torch.randn((B, cout) + xyz, generator=gen, dtype=f64)
+    h = torch.randn((B, cin) + xyz, generator=gen, dtype=f64)
+    acc = torch.randn((B, cin) + xyz, generator=gen, dtype=f64)
+    want, wa = kb.ref_dgrad(gy, w, (0, 0, 0), alpha=0.5, mask_y=h, slope=0.25, acc=acc)
+    got, ga = kb.ref_pointwise(rows(gy), w.view(cout, cin).T, alpha=0.5, res=rows(acc), beta=1.0, mask_y=rows(h),
+                               mask_win=(0, cin), mask_slope=0.25)
+    torch.testing.assert_close(got, rows(want), rtol=1e-12, atol=1e-12)
+    torch.testing.assert_close(ga, rows(wa), rtol=1e-12, atol=1e-12)
+    # partial residuals, a mask window, scalars as fp32
+    r2 = torch.randn((B * math.prod(xyz), cin), generator=gen, dtype=f64)
+    got, _ = kb.ref_pointwise(rows(gy), w.view(cout, cin).T, alpha=0.3, res=rows(acc), beta=0.7, res_c1=8, res2=r2,
+                              beta2=0.1, mask_y=rows(h)[:, :4], mask_win=(8, 12), mask_slope=0.2)
+    a32, b32, c32, s32 = (float(torch.tensor(v, dtype=torch.float32)) for v in (0.3, 0.7, 0.1, 0.2))
+    want = a32 * rows(gy) @ w.view(cout, cin)
+    want[:, :8] += b32 * rows(acc)[:, :8] + c32 * r2[:, :8]
+    want[:, 8:12] *= torch.where(rows(h)[:, :4] > 0, 1.0, s32)
+    torch.testing.assert_close(got, want, rtol=1e-12, atol=1e-12)
+
+
+def test_stream_emulation_is_within_the_bound(stream):
+    worst = kb.assert_within(stream.emul(), stream.ref, stream.bnd, "emul stream 1x1x1")
+    assert worst <= 1.0 and not stream.violations(stream.emul())
+
+
+def _rejected(s, got, region, min_hits, label):
+    """``got`` violates the bound inside ``region`` (a predicate on (voxel, column)) only, at >= ``min_hits`` elements,
+    and the assertion's message names elements of it"""
+    bad = s.violations(got)
+    assert len(bad) >= min_hits, (label, len(bad))
+    assert all(region(v, c) for v, c in bad), (label, sorted(bad)[:5])
+    with pytest.raises(AssertionError) as e:
+        kb.assert_within(got, s.ref, s.bnd, label)
+    # (the message lists the five worst elements with their ratios: those above 1 are the violations it names)
+    named = [(int(v), int(c)) for v, c, q in
+             re.findall(r"^\s+\((\d+), (\d+)\):.* ratio (\S+)$", str(e.value), flags=re.M) if float(q) > 1.0]
+    assert named and all(region(v, c) for v, c in named), (label, str(e.value))
+    return named
+
+
+STREAM_MUTATIONS = {  # name -> (emul switches, region of the wrong elements, least number of violations)
+    "res_on_8_channels_too_many": (dict(res_c1=136), lambda v, c: 128 <= c < 136, 665 * 8 * 9 // 10),
+    "res2_past_res_c1": (dict(res2_c1=256), lambda v, c: c >= 128, 665 * 128 * 9 // 10),
+    "res2_dropped": (dict(beta2=0.0), lambda v, c: c < 128, 665 * 128 * 9 // 10),
+    "mask_window_shifted_by_8": (dict(win=(216, 248)), lambda v, c: c >= 216, 665 * 8),
+    "mask_read_at_y_off_plus_8": (dict(y_off=16), lambda v, c: c >= 224, 665 * 32 // 4),
+    "acc_beta_ignored": (dict(beta=1.0), lambda v, c: c < 128, 665 * 128 * 9 // 10),
+}
+
+
+@pytest.mark.parametrize("name", list(STREAM_MUTATIONS))
+def test_stream_epilogue_mutation_is_caught(stream, name):
+    kw, region, min_hits = STREAM_MUTATIONS[name]
+    _rejected(stream, stream.emul(**kw), region, min_hits, name)
+
+
+@pytest.mark.parametrize("which", ["negative_zero_taken_as_positive", "positive_subnormal_taken_as_not_positive"])
+def test_stream_mask_sign_of_special_values_is_caught(stream, which):
+    s = stream
+    v, j = (s.v0, s.j0) if which.startswith("negative") else (s.v1, s.j1)
+    named = _rejected(s, s.emul(flip=[(v, j)]), lambda vv, c: (vv, c) == (v, s.win[0] + j), 1, which)
+    assert named[0] == (v, s.win[0] + j)
+
+
+def test_stream_exchanged_strips_are_caught(stream):
+    s = stream
+    got = s.emul()
+    a, b = got[48:64].clone(), got[320:336].clone()  # strips 3 and 20
+    got[48:64], got[320:336] = b, a
+    _rejected(s, got, lambda v, c: 48 <= v < 64 or 320 <= v < 336, 32 * 256 * 9 // 10, "strips exchanged")
+
+
+def test_stream_stale_tail_is_caught(stream):
+    s = stream
+    got = s.emul()
+    tail = s.nvox - s.nvox % 16
+    assert s.nvox % 16 == 9
+    got[tail:] = s.acc[tail:]  # the last strip's voxels keep the buffer's old contents
+    _rejected(s, got, lambda v, c: v >= tail, 9 * 256 * 9 // 10, "stale tail")
