@@ -36,17 +36,12 @@ int wsr_ct_run_masked(CtArgs& a, int tpk, hipStream_t st);  // conv_tile_masked.
 int wsr_ct_run_narrow_masked(CtArgs& a, int tpk, hipStream_t st);  // conv_tile_narrow_masked.hip
 int wsr_ct_run_small(CtArgs& a, int tpk, hipStream_t st);          // conv_tile_small.hip
 int wsr_ct_run_tm3(CtArgs& a, int tpk, hipStream_t st);            // conv_tile_tm3.hip
-int wsr_ct_run_narrow_wk(CtArgs& a, int tpk, hipStream_t st);      // conv_tile_narrow_wk.hip
 int wsr_ct_run_simple_narrow(CtArgs& a, int tpk, int tm3, hipStream_t st);  // conv_tile_simple_narrow.hip
 int wsr_ct_run_simple_n128(CtArgs& a, int tpk, int tm3, hipStream_t st);    // conv_tile_simple_n128.hip
-int wsr_ct_run_simple_mid(CtArgs& a, int tpk, hipStream_t st);              // conv_tile_simple_mid.hip
 int wsr_ct_run_simple_small(CtArgs& a, int tpk, hipStream_t st);            // conv_tile_simple_small.hip
 long wsr_ct_tiles(const CtArgs& a, int rows);                      // conv_tile_tm3.hip
 int wsr_ct_run_strided(CtArgs& a, int tpk, hipStream_t st);        // conv_tile_strided.hip
 int wsr_ct_run_f32(CtArgs& a, int tpk, hipStream_t st);            // conv_tile_f32*.hip
-#ifdef WSR_TUNING
-int wsr_ct_run_w4(CtArgs& a, int tpk, int which, hipStream_t st);  // conv_tile_w4.hip (make TUNING=1)
-#endif
 
 namespace {
 
@@ -54,14 +49,6 @@ int dispatch_ct(CtArgs& a, int tpk, hipStream_t st) {
   const int N = a.Cout;
   if (a.f32) return wsr_ct_run_f32(a, tpk, st);  // (stride 1 only: the entry points checked)
   if ((a.sx | a.sy | a.sz) != 1) return wsr_ct_run_strided(a, tpk, st);
-#ifdef WSR_TUNING
-  if (WSR_ENV_SET("WSR_CT_W4")) {  // tuning switch: four-wave workgroups
-    if ((long)a.B * a.Xo * a.Yo * a.Zo >= 128L * 512) {
-      const int rc = wsr_ct_run_w4(a, tpk, WSR_ENV_RAW("WSR_CT_W4"), st);
-      if (rc != WSR_EUNSUPPORTED) return rc;
-    }
-  }
-#endif
   // small volumes (< 128 tiles of 512 voxels): 128-voxel tiles where an instantiation exists
   // (SIMPLE: instantiations with the general forms' run-time switches folded away, for the plain stride-1 launches of the
   // trunk - conv_tile_impl.h; each returns WSR_EUNSUPPORTED for anything else)
@@ -82,13 +69,7 @@ int dispatch_ct(CtArgs& a, int tpk, hipStream_t st) {
     const long n4 = wsr_ct_tiles(a, 512), n3 = wsr_ct_tiles(a, 384);
     tm3 = ((n3 + 255) / 256) * 3 < ((n4 + 255) / 256) * 4;
   }
-  // the source-grouped stages of a dense block's forward (act = 2 with a partial activation window; engine.conv_dense)
-  if ((simple & 1) && tpk == 2 && N > 32 && N <= 96 && !a.mask_y && a.act == 2 && a.act_c1 != 0x7FFFFFFF && a.nphase != 4 &&
-      !a.ups && !WSR_ENV_SET("WSR_CT_NO_MID")) {
-    const int rc = wsr_ct_run_simple_mid(a, tpk, st);
-    if (rc != WSR_EUNSUPPORTED) return rc;
-  }
-  if ((simple & 1) && tpk == 2 && N > 16 && N <= 32 && !(WSR_ENV_INT("WSR_CT_NARROW_WK", 0))) {
+  if ((simple & 1) && tpk == 2 && N > 16 && N <= 32) {
     const int rc = wsr_ct_run_simple_narrow(a, tpk, tm3, st);
     if (rc != WSR_EUNSUPPORTED) return rc;
   }
@@ -98,10 +79,6 @@ int dispatch_ct(CtArgs& a, int tpk, hipStream_t st) {
   }
   if (tm3) {
     const int rc = wsr_ct_run_tm3(a, tpk, st);
-    if (rc != WSR_EUNSUPPORTED) return rc;
-  }
-  if (tpk == 2 && N > 16 && N <= 32 && a.nphase != 4 && WSR_ENV_INT("WSR_CT_NARROW_WK", 0)) {  // (tuning: 16-wave K-step shares)
-    const int rc = wsr_ct_run_narrow_wk(a, tpk, st);
     if (rc != WSR_EUNSUPPORTED) return rc;
   }
   if (a.mask_y) return N <= 64 ? wsr_ct_run_narrow_masked(a, tpk, st) : wsr_ct_run_masked(a, tpk, st);
@@ -498,7 +475,7 @@ int wsr_conv1x1_bf16(const unsigned short* in, int in_ctot, int in_off, int red,
                      unsigned short* out, int out_ctot, int out_off, int n_out, long nvox, const float* bias,
                      const unsigned short* res, int res_ctot, int res_off, int res_c1, float alpha, float beta, int act,
                      float slope, const wsr_lrelu_mask_t* mask, const unsigned short* res2, int res2_ctot, int res2_off,
-                     float beta2, hipStream_t st);  // conv_1x1.hip
+                     float beta2, hipStream_t st);  // conv_1x1_v2.hip
 
 // conv_thin.hip: sliding-window kernel of the 3x3x3 convs with <= 16 reduction channels
 int wsr_conv_thin3(const unsigned short* in, int in_ctot, int in_off, int red, const unsigned short* wfrag,

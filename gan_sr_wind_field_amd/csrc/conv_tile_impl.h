@@ -411,53 +411,14 @@ void conv_tile_kernel(const CtArgs a) {
 #ifdef WSR_CT_STAMPS
   long long st_dma = 0, st_bar = 0;  // shader cycles this wave spent waiting for its DMAs / at the phase barrier
 #endif
-  // Epilogue operands requested EARLY (round 6; the 32-wide SIMPLE instantiations: one workgroup per CU by LDS, so the
-  // registers are free): the partial sums / running gradient a launch adds to (`res`) and the saved activation its
-  // LeakyReLU mask is taken from were written by earlier launches - their loads go out at the top of the LAST phase and
-  // land under its K-steps instead of costing a global-memory round trip between the main loop and the first store.
-  // Measured and NOT shipped (build the 32-wide translation units with -DWSR_CT_EPF to have it; profiles/r06_i_ab_epilogue_prefetch.txt):
-  // C3' 90.12 / 90.17 ms with, 89.93 / 90.07 without - the loads' latency was not what the 3 us epilogue is made of - and the
-  // 145-164 registers it takes end the two-workgroups-per-CU form of multi-round launches (C4 332.2 vs 326.8 ms).
-#ifdef WSR_CT_EPF
-  constexpr bool EPF = SIMPLE == 1 && TN <= 2 && WK == 1;
-#else
-  constexpr bool EPF = false;
-#endif
-  V4 pre_rr[EPF ? TN : 1][EPF ? TM : 1], pre_yy[EPF ? TN : 1][EPF ? TM : 1];
-  auto epilogue_prefetch = [&]() __attribute__((always_inline)) {
-    if constexpr (EPF) {
-      const int cob_ = (nt0 + wn * TN) * 16 + fg * 4;
-      const long vpb = (long)a.Xo * a.Yo * a.Zo;
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        const unsigned mv = mtab[(wm * TM + i) * 16 + fr];
-        const int gx = x0 + (int)(mv & 255), gy = y0 + (int)((mv >> 8) & 255), gz = z0 + (int)((mv >> 16) & 255);
-        const bool ok = !(mv >> 24) && gx < a.Xo && gy < a.Yo && gz < a.Zo;
-        const long m = ok ? (long)b * vpb + ((long)gx * a.Yo + gy) * a.Zo + gz : -1;
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          const int co0 = cob_ + 16 * j;
-          pre_rr[j][i] = ct_zero4<T>();
-          pre_yy[j][i] = ct_ones4<T>();
-          if (m < 0 || co0 >= a.Cout) continue;
-          if (a.res && co0 < a.res_c1)
-            pre_rr[j][i] = *reinterpret_cast<const V4*>(reinterpret_cast<const E*>(a.res) + m * a.res_ctot + a.res_off + co0);
-          if (MASK && a.mask_y && co0 >= a.mask_c0 && co0 < a.mask_c1)
-            pre_yy[j][i] = *reinterpret_cast<const V4*>(reinterpret_cast<const E*>(a.mask_y) + m * a.mask_ctot + a.mask_off +
-                                                        (co0 - a.mask_c0));
-        }
-      }
-    }
-  };
+  // (requesting the epilogue's `res` / mask operands at the top of the last phase was measured and not kept; the variant
+  // was removed - record: profiles/r06_i_ab_epilogue_prefetch.txt)
   const int total_phases = nchunks_l * nstages;
   int chunk = 0, st = 0;
   // static priority for the second-dispatched half (it loses the issue arbitration against the older half on
   // every phase otherwise: MI355X_MICROARCH.md, two waves per SIMD, item 4)
   if (a.prio && wave >= WAVES / 2) __builtin_amdgcn_s_setprio(1);
   for (int ph = 0; ph < total_phases; ++ph) {
-    if constexpr (EPF) {
-      if (ph + 1 == total_phases) epilogue_prefetch();
-    }
     // ---- prefetch: next weight stage, and a slice of the next chunk's activations.  The burst costs each
     // wave several hundred issue cycles during which it feeds no MFMAs, so the two halves of the workgroup
     // (waves w and w + WAVES/2 share a SIMD) take turns: the first half issues at the top of the phase, the
@@ -688,14 +649,6 @@ void conv_tile_kernel(const CtArgs a) {
     // LeakyReLU backward of the layer whose output gradient this is (channels [mask_c0, mask_c1)): the
     // multiply by (y > 0 ? 1 : slope) happens in this epilogue, after the accumulation, not in its own pass
     const bool masked = MASK && co0 >= a.mask_c0 && co0 < a.mask_c1;
-    if constexpr (EPF) {  // (requested at the top of the last phase: epilogue_prefetch)
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        rr[s][i] = pre_rr[j][i];
-        yy[s][i] = pre_yy[j][i];
-      }
-      return;
-    }
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
       rr[s][i] = ct_zero4<T>();
@@ -862,14 +815,14 @@ int launch_ct(CtArgs& a, hipStream_t st) {
   int ts_max = 0;
   // (one chunk: the second activation buffer would never be filled - the LDS it frees lets a second workgroup share
   // the CU, whose prologue and epilogue then overlap this one's main loop: terrain convs, 3-channel inputs)
-  const int xb_first = WSR_ENV_INT("WSR_CT_XBUFS", (a.nchunks == 1 || (NTW == 1 && WSR_ENV_SET("WSR_CT_N16_ONEBUF"))) ? 1 : 2);  // env: tuning aid
+  const int xb_first = WSR_ENV_INT("WSR_CT_XBUFS", a.nchunks == 1 ? 1 : 2);  // env: tuning aid
   // Two workgroups per CU for the 32-wide launches (WSR_CT_DIET=1, round 6): their 125 registers leave room for four
   // waves per SIMD, so a workgroup that keeps to half the LDS (one activation buffer, shorter weight stages) shares
   // its CU with a second one whose prologue / epilogue / DMA waits then run under this one's K-steps.
   // Measured (profiles/r06_b_ab_diet.txt, single launches, same device): at batch 4 (1 024 tiles = four rounds) the
   // 32 -> 32 / 64 -> 32 / 96 -> 32 growth stages take 55.8 / 78.2 / 102.6 us as one 128 KB workgroup per CU and
   // 45.1 / 69.8 / 98.8 us as two 67 KB ones; at batch 1 (256 tiles: nothing to share a CU with) the single buffer costs
-  // 14.6 -> 15.6, 20.5 -> 23.0, 28.3 -> 33.9 us, and 512 tiles of 256 voxels (WSR_CT_NARROW_M=256) are no better than
+  // 14.6 -> 15.6, 20.5 -> 23.0, 28.3 -> 33.9 us, and 512 tiles of 256 voxels are no better than
   // that (16.0 / 24.9 / 34.3): the diet is taken from two rounds of workgroups on (WSR_CT_DIET=0 / 1 forces it).
   const long nwg_all = (long)a.B * ((a.Xo + a.TX - 1) / a.TX) * ((a.Yo + a.TY - 1) / a.TY) * ((a.Zo + a.TZ - 1) / a.TZ) *
                        ((a.Cout + 16 * NTW - 1) / (16 * NTW)) * (a.nphase == 4 ? 4 : 1);
@@ -1003,9 +956,6 @@ static void pick_tile(CtArgs& a, int M) {
     while (tx * ty < rest) {  // power of two: balanced split, y first
       if (ty <= tx) ty <<= 1; else tx <<= 1;
     }
-  } else if (WSR_ENV_SET("WSR_CT_SQUARE_TILES")) {  // (rounds 1-4: the most nearly square x-y tile, whatever the extents)
-    while ((tx + 1) * (tx + 1) <= rest) ++tx;
-    ty = rest / tx;
   } else {
     // z extents such as the reference's 10 levels leave an x-y budget that is no power of two (512 / 10 = 51): take the
     // split that covers THIS volume with the fewest tiles - 16 x 16 x 10 (the LR patches of the shipped configurations,
@@ -1036,6 +986,5 @@ static void pick_tile(CtArgs& a, int M) {
   }
   a.TX = tx; a.TY = ty; a.TZ = tz;
 }
-
 
 }  // namespace

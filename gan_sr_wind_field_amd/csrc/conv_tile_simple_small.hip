@@ -7,7 +7,7 @@
 
 int wsr_ct_run_simple_small(CtArgs& a, int tpk, hipStream_t st) {
   const int N = a.Cout;
-  if (tpk != 2 || WSR_ENV_INT("WSR_CT_SMALL_WK", 1) == 0) return WSR_EUNSUPPORTED;
+  if (tpk != 2) return WSR_EUNSUPPORTED;
   if (N <= 32) {
     pick_tile(a, 128);
     if (a.mask_y) return launch_ct<2, 1, 4, 2, 2, true, BF16, 4, true>(a, st);

@@ -35,13 +35,6 @@ STACK_DGRAD = __import__("os").environ.get("WSR_STACK_DGRAD", "1") != "0"
 #: split the growth convs of a dense block into one conv over the block input + narrow convs over the growth
 #: channels (WSR_STACK_FWD=0: one launch per conv over its whole input window)
 STACK_FWD = __import__("os").environ.get("WSR_STACK_FWD", "1") != "0"
-#: ... and the growth-channel part of that forward grouped by SOURCE window (round 6, measured and NOT kept: WSR_FWD_REGROUP=1 turns
-#: it on): the window conv j - 1 just produced is contracted into the windows of all later convs at once - 96 / 64 / 32 outputs at a
-#: reduction of one window - instead of every conv re-reading every earlier window (32 outputs at 1 / 2 / 3 windows).  Same FLOPs, fewer
-#: LDS fragment reads and halo bytes per MFMA; at C3' the three launches take 37.2 + 27.5 + 16.6 = 81.3 us against 72 us for the per-conv
-#: stages (step 88.8 vs 87.6 ms, profiles/r06_g_ab_fwd_regroup.txt): prologue and epilogue grow with the produced width (a 96-wide
-#: epilogue re-reads and re-writes three windows of partial sums) and eat what the wider K-steps save.
-FWD_REGROUP = __import__("os").environ.get("WSR_FWD_REGROUP", "0") == "1"
 #: train-mode BatchNorm statistics of all batch groups of a discriminator layer in four launches (wsr_bn_train_stats, round 6;
 #: WSR_FUSED_BN_STATS=0: six launches per group); single-process runs only - SyncBN has its collective between the passes
 FUSED_BN_STATS = __import__("os").environ.get("WSR_FUSED_BN_STATS", "1") != "0"
@@ -62,10 +55,6 @@ WGRAD_STREAM = int(__import__("os").environ.get("WSR_WGRAD_STREAM", "0"))
 #: fp32 programs (the reference's own arithmetic) on the LDS halo-tile kernels too: stride-1 convs, dense-block stacking,
 #: the z-folded last conv (WSR_F32_TILE=0: generic implicit-GEMM kernels as in rounds 1-3)
 F32_TILE = __import__("os").environ.get("WSR_F32_TILE", "1") != "0"
-#: the LeakyReLU backward of the discriminator's first conv in the epilogue of the strided input gradient above it
-#: (WSR_FOLD_D_MASK=1; default off: measured equal - same-device A/B 97.5 / 97.5 against 97.5 / 98.0 ms per step - the
-#: masked 32-wide parity launches grow by what the pass over the 128^3 x 32 tensor costs; parity-tested either way)
-FOLD_D_MASK = __import__("os").environ.get("WSR_FOLD_D_MASK", "0") != "0"
 # Filter gradient of the z-folded last conv with the operands' roles exchanged (GeneratorProgram.backward): the 16-channel
 # output gradient is the image that is shifted per tap, the 144-channel activation the one that is read once
 SWAP_THIN_WGRAD = __import__("os").environ.get("WSR_THIN_WGRAD_SWAP", "1") != "0"
@@ -560,11 +549,6 @@ class ProgramBase:
                   nc * gc, nf)]
         specs += [((id(convs[0].weight), "grow", i), [(convs[i].weight, False, nf, i * gc, 0, 0)], gc, i * gc)
                   for i in range(1, nc)]
-        if FWD_REGROUP and self.dt == torch.bfloat16:
-            # by source window j (= the output of conv j - 1, channels [nf + (j-1) gc, nf + j gc)): the rows of convs j .. nc-1
-            specs += [((id(convs[0].weight), "src", j),
-                       [(convs[i].weight, False, nf + (j - 1) * gc, gc, 0, (i - j) * gc) for i in range(j, nc)],
-                       (nc - j) * gc, gc) for j in range(1, nc)]
         return specs
 
     def conv_dense(self, convs: Sequence[ConvSite], buf: Tensor) -> bool:
@@ -588,34 +572,6 @@ class ProgramBase:
             run_pre()
         if not done[0]:
             return False
-        # Grouped by SOURCE window (FWD_REGROUP; volumes of >= 128 tiles of 512 voxels - below that the 128-voxel-tile
-        # kernels run and a launch is one workgroup's dependent K-loop either way): stage j adds the contribution of window
-        # j to the windows of convs j .. nc-1 and completes conv j's (bias + LeakyReLU on its first gc channels only).  Each
-        # later window's partial sums pass through bf16 once per stage (conv 3: three times instead of once).
-        if (FWD_REGROUP and self.dt == torch.bfloat16 and nc > 2 and gc * (nc - 1) <= 96
-                and B * xyz[0] * xyz[1] * xyz[2] >= 128 * 512):
-            for j in range(1, nc):
-                n_out = (nc - j) * gc
-                dj = ops.make_desc(ConvGeom(gc, n_out, k, (1, 1, 1), pad), self.dt, B, xyz, ctot, nf + (j - 1) * gc, ctot,
-                                   nf + j * gc)
-                bj = convs[j].bias.detach() if convs[j].bias is not None else None
-                fr = self.filters.get_stacked((id(convs[0].weight), "src", j))
-                ok = []
-
-                def run_src(dj=dj, bj=bj, fr=fr, off=nf + j * gc, c1=gc if j < nc - 1 else 0):
-                    ok.append(ops.conv_fwd_tile(dj, buf, fr, buf, bias=bj, res=buf, res_off=off, beta=1.0, act=2, slope=sl,
-                                                act_c1=c1))
-
-                if self.launch_probe is not None:
-                    self.launch_probe(f"fwd_dense_src{j}:" + convs[0].name, run_src)
-                else:
-                    run_src()
-                if not ok[0]:
-                    if j == 1:
-                        break  # nothing written yet: the per-conv stages below take over
-                    raise RuntimeError("source-grouped dense-block stage outside the tile kernels (set WSR_FWD_REGROUP=0)")
-            else:
-                return True
         for i in range(1, nc):
             di = ops.make_desc(ConvGeom(i * gc, gc, k, (1, 1, 1), pad), self.dt, B, xyz, ctot, nf, ctot, nf + i * gc)
             bi = convs[i].bias.detach() if convs[i].bias is not None else None
@@ -1511,7 +1467,7 @@ class GeneratorProgram(ProgramBase):
         return flat
 
     def stacked_fwd_specs(self):
-        key = (self.use_tile, STACK_FWD, FWD_REGROUP)
+        key = (self.use_tile, STACK_FWD)
         if self._stack_fwd_specs is None or self._stack_fwd_specs[0] != key:
             specs = [sp for rdbs in self.rrdbs for convs, _, _ in rdbs if STACK_FWD and self.dense_stackable(convs)
                      for sp in self.dense_fwd_specs(convs)]
@@ -1732,10 +1688,8 @@ class DiscriminatorProgram(ProgramBase):
                     self._dparity_stamp[li] = stamp
         super().refresh_filters(backward)
 
-    def strided_dgrad(self, li: int, gy: Tensor, gin: Tensor, mask=None) -> None:
-        """gin (B, X, Y, Z, cin) = input gradient of down-sampling conv ``li`` from gy (B, X/2, Y/2, Z/s, cout).
-        ``mask`` = (y, y_off, c0, c1, slope): the LeakyReLU derivative of the layer below (whose output ``y`` is this
-        conv's input) rides on the epilogues - every voxel of gin is written by exactly one parity launch."""
+    def strided_dgrad(self, li: int, gy: Tensor, gin: Tensor) -> None:
+        """gin (B, X, Y, Z, cin) = input gradient of down-sampling conv ``li`` from gy (B, X/2, Y/2, Z/s, cout)."""
         s = self.layers[li].conv
         sz = s.stride[2]
         B, oxyz = gy.shape[0], tuple(gy.shape[1:4])
@@ -1747,13 +1701,13 @@ class DiscriminatorProgram(ProgramBase):
                 if batched:
                     d = ops.make_desc(g, self.dt, B, oxyz, gy.shape[-1], 0, gin.shape[-1], 0, cin=self.cp(s.cout),
                                       cout=self.cp(s.cin), lat=(0, 0, 4, sz, zc))
-                    if ops.conv_fwd_tile(d, gy, frs[0], gin, mask=mask):
+                    if ops.conv_fwd_tile(d, gy, frs[0], gin):
                         continue
                 for ph, ps in enumerate(par):
                     d = ops.make_desc(ConvGeom(s.cout, s.cin, ps.kernel, (1, 1, 1), ps.pad), self.dt, B, oxyz,
                                       gy.shape[-1], 0, gin.shape[-1], 0, cin=self.cp(s.cout), cout=self.cp(s.cin),
                                       lat=(ph >> 1, ph & 1, 0, sz, zc))
-                    if not ops.conv_fwd_tile(d, gy, frs[ph], gin, mask=mask):
+                    if not ops.conv_fwd_tile(d, gy, frs[ph], gin):
                         raise RuntimeError("strided input gradient outside the tile kernels (set WSR_STRIDED_DGRAD=0)")
 
         if self.launch_probe is not None:
@@ -1930,7 +1884,6 @@ class DiscriminatorProgram(ProgramBase):
         if lo and (need_dw or lo % Bg):
             raise ValueError("a partial backward pass starts at a group boundary and has no parameter gradients")
         g = g_feat.contiguous()  # (covers samples [lo, B) only)
-        premasked = False  # g already carries the LeakyReLU derivative of the layer it is the output gradient of
         dx = None
         recs = saved["recs"]
         bn_grad_jobs: Dict[int, tuple] = {}  # group -> (gradient slots, per-channel sums): BatchNorm weight / bias gradients
@@ -1953,9 +1906,8 @@ class DiscriminatorProgram(ProgramBase):
             if self.trace is not None:
                 self.trace.append(("g", li, g.clone()))
             if l.bn is None:
-                if l.act and not premasked:
+                if l.act:
                     ops.lrelu_bwd_(g, 0, act_o, 0, g.shape[-1], sl)
-                premasked = False
                 gy = g
             else:
                 bn = l.bn
@@ -2025,13 +1977,7 @@ class DiscriminatorProgram(ProgramBase):
             if li > 0:
                 gin = self._empty(inp.shape, g)
                 if self.strided_dgrad_active(li) and lattice_ok:
-                    # the layer below has no BatchNorm (the first conv: conv + LeakyReLU): its leaky_relu_backward rides on
-                    # the epilogues of this input gradient instead of a pass of its own over the largest tensor of D
-                    below = self.layers[li - 1]
-                    premasked = (below.bn is None and below.act and inp.shape[-1] == below.conv.cout
-                                 and below.conv.cout <= 32 and FOLD_D_MASK)
-                    self.strided_dgrad(li, gy, gin, mask=(recs[li - 1]["a"][lo:], 0, 0, below.conv.cout, sl)
-                                       if premasked else None)
+                    self.strided_dgrad(li, gy, gin)
                 else:
                     self.dgrad(s, gy, 0, gin, 0, tuple(inp.shape[1:4]))
                 if self.trace is not None:

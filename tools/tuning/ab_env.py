@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """A/B of tuning switches on single launches: runs tools/bench_conv.py cases once per environment setting.
 
-    python tools/tuning/ab_env.py "WSR_CT_W4=0,1,2,4" hr0 lr grow up
+    python tools/tuning/ab_env.py "WSR_CT_DIET=-,0,1" grow
 """
 import os
 import sys

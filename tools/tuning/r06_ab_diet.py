@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Round 6 A/B: two co-resident workgroups per CU for the 32-wide growth launches (WSR_CT_DIET, WSR_CT_NARROW_M).
+"""Round 6 A/B: two co-resident workgroups per CU for the 32-wide growth launches (WSR_CT_DIET).
 
 Single launches through the C-ABI (tools/bench_conv.py cases), batch 1 and batch 4, each variant on the same device in
 one process:   python tools/tuning/r06_ab_diet.py > gpurun_out/r06_b_ab_diet.txt
@@ -22,12 +22,10 @@ def cases(B):
 
 
 if __name__ == "__main__":
-    variants = [("baseline", {}), ("diet", {"WSR_CT_DIET": "1"}), ("M256", {"WSR_CT_NARROW_M": "256"}),
-                ("diet+M256", {"WSR_CT_DIET": "1", "WSR_CT_NARROW_M": "256"})]
+    variants = [("baseline", {}), ("diet", {"WSR_CT_DIET": "1"})]
     for rep in range(2):
         for name, env in variants:
-            for k in ("WSR_CT_DIET", "WSR_CT_NARROW_M"):
-                os.environ.pop(k, None)
+            os.environ.pop("WSR_CT_DIET", None)
             os.environ.update(env)
             bc.o._lib.lib().wsr_reload_env()
             print(f"---- {name} (pass {rep})", flush=True)
