@@ -623,6 +623,19 @@ class wind_field_GAN_3D(BaseGAN):
     def validation(self, LR, HR, Z, it):
         self.compute_losses_and_optimize(LR, HR, Z, it, training_iteration=False)
 
+    # ------------------------------------------------------------------ geometric self-ensemble ([ENSEMBLE])
+    def G_ensemble(self, LR, Z, members=None, with_var: bool = False):
+        """The generator averaged over ``members`` (1, 2, 4 or 8; None: ``[ENSEMBLE] members``) symmetries of the square
+        (``ensemble.self_ensemble``): one generator forward on the stacked batch under ``no_grad``, with the weights the
+        generator holds (inside ``ema_scope()`` the averaged ones) and in the mode it is in.  -> fp32 ``mean``
+        (B, 3, X, Y, NZ), or ``(mean, var)`` with the population variance per component between the members."""
+        from ..ensemble import self_ensemble
+
+        if members is None:
+            members = self.cfg.ensemble.members
+        with torch.no_grad():
+            return self_ensemble(self.G, LR.contiguous(), Z.contiguous(), members=members, with_var=with_var)
+
     def make_new_labels(self, it):
         """Real / fake label vectors of this iteration (reference :627-678)."""
         t = self.cfg.training

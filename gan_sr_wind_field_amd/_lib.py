@@ -24,6 +24,7 @@ EXPORTS = [
     "wsr_bn_bwd_apply", "wsr_adam_step", "wsr_adam_multi", "wsr_gather_batch", "wsr_grad_sqnorm_multi",
     "wsr_adam_multi_clip", "wsr_adam_multi_ema", "wsr_adam_multi_clip_ema",
     "wsr_trilinear_xy", "wsr_field_metrics", "wsr_column_interp",
+    "wsr_dihedral_members", "wsr_ensemble_reduce",
 ]
 
 
@@ -147,6 +148,8 @@ def lib() -> C.CDLL:
         "wsr_trilinear_xy": [vp, i32, i32, i32, i32, i32, i32, vp, vp],   # additive export
         "wsr_field_metrics": [vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp],   # additive export
         "wsr_column_interp": [vp, vp, vp, i32, i32, i64, i32, vp, vp],   # additive export
+        "wsr_dihedral_members": [vp, i32, i32, i32, i32, i32, C.POINTER(C.c_int32), i32, i32, vp, vp],   # additive export
+        "wsr_ensemble_reduce": [vp, C.POINTER(C.c_int32), i32, i32, i32, i32, i32, vp, vp, vp],   # additive export
     }
     for name, argtypes in sig.items():
         fn = getattr(L, name)

@@ -19,6 +19,9 @@ Extension (optional keys, defaults keep reference behaviour):
             validation and --test take the trilinear baseline and the error sums from the HIP kernels
             (csrc/eval_metrics.hip); --test runs batch_size fields per launch and can write the metrics on the raw
             terrain-following levels
+  [ENSEMBLE] members / write_spread
+            --test averages the generator over 1, 2, 4 or 8 symmetries of the square (ensemble.py,
+            csrc/ensemble.hip) and can write the spread between the members
 """
 from __future__ import annotations
 
@@ -387,6 +390,33 @@ class EvalConfig(IniConfig):
         return "[EVAL]\n" + "".join(f"{k} = {getattr(self, k)}\n" for k, _ in self._schema)
 
 
+class EnsembleConfig(IniConfig):
+    """[ENSEMBLE] (extension): geometric self-ensemble of ``run.py --test`` (ensemble.py, csrc/ensemble.hip); absent
+    section = off, and not printed by ``asINI``.  ``members``: 1, 2, 4 or 8 symmetries of the square the generator is
+    averaged over; ``write_spread``: ``--test`` also writes ``<name>____ensemble_spread.csv`` and pickles ``SR_spread``."""
+
+    present: bool = False
+    members: int = 8
+    write_spread: bool = False
+    _schema = (("members", _I), ("write_spread", _B))
+
+    def setEnsembleConfig(self, section):
+        """``section`` None (no [ENSEMBLE] in the file) restores the defaults and switches the section off."""
+        self.present = section is not None
+        for key, kind in self._schema:
+            val = None if section is None else _read(section, key, kind)
+            setattr(self, key, getattr(EnsembleConfig, key) if val is None else val)
+
+    def validate(self) -> None:
+        if not self.present:
+            return
+        if self.members not in (1, 2, 4, 8):
+            raise ValueError(f"[ENSEMBLE] members must be 1, 2, 4 or 8, not {self.members}")
+
+    def __str__(self) -> str:
+        return "[ENSEMBLE]\n" + "".join(f"{k} = {getattr(self, k)}\n" for k, _ in self._schema)
+
+
 class Config(IniConfig):
     name: str = "default_name"
     model: str = "default_model"
@@ -412,6 +442,7 @@ class Config(IniConfig):
     grad_clip: GradClipConfig = GradClipConfig()
     ema: EmaConfig = EmaConfig()
     eval: EvalConfig = EvalConfig()
+    ensemble: EnsembleConfig = EnsembleConfig()
     compute_dtype: str = "fp32"
     is_train: bool
     is_use: bool
@@ -444,6 +475,8 @@ class Config(IniConfig):
         self.ema.validate()
         self.eval.setEvalConfig(parser["EVAL"] if parser.has_section("EVAL") else None)
         self.eval.validate(self.gan_config.interpolate_z)
+        self.ensemble.setEnsembleConfig(parser["ENSEMBLE"] if parser.has_section("ENSEMBLE") else None)
+        self.ensemble.validate()
 
     def setBaseConfig(self, base):
         self.name = base.get("name")
@@ -477,4 +510,6 @@ class Config(IniConfig):
             out += "\n" + str(self.ema)
         if getattr(self.eval, "present", False):
             out += "\n" + str(self.eval)
+        if getattr(self.ensemble, "present", False):
+            out += "\n" + str(self.ensemble)
         return out

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <initializer_list>
+
 #include "../../include/windsr_hip.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
@@ -84,6 +86,17 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 }
 
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
+
+// ---- planar fp32 streams (data_gather.hip's layout: a thread moves V consecutive floats of a z-innermost run) ------
+static inline bool aligned_to(const void* p, int bytes) { return (((size_t)p) & (size_t)(bytes - 1)) == 0; }
+
+// widest piece (4 / 2 / 1 floats) that divides NZ and that every non-null pointer is aligned for
+static inline int piece_width(int NZ, std::initializer_list<const void*> ptrs) {
+  int v = NZ % 4 == 0 ? 4 : (NZ % 2 == 0 ? 2 : 1);
+  for (const void* p : ptrs)
+    while (v > 1 && p && !aligned_to(p, 4 * v)) v >>= 1;
+  return v;
+}
 
 // ---- tuning switches ------------------------------------------------------------------------------------
 // Environment switches (WSR_*) are tuning / A-B aids.  Reading them with getenv on every launch cost 3-7 scans of

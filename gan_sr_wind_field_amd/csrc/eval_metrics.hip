@@ -255,16 +255,6 @@ __global__ __launch_bounds__(EV_BLOCK) void column_interp_kernel(const float* __
   }
 }
 
-inline bool aligned_to(const void* p, int bytes) { return (((size_t)p) & (size_t)(bytes - 1)) == 0; }
-
-// widest piece that divides NZ and that every pointer is aligned for
-inline int piece_width(int NZ, std::initializer_list<const void*> ptrs) {
-  int v = NZ % 4 == 0 ? 4 : (NZ % 2 == 0 ? 2 : 1);
-  for (const void* p : ptrs)
-    while (v > 1 && p && !aligned_to(p, 4 * v)) v >>= 1;
-  return v;
-}
-
 inline bool tl_geom(TlGeom& g, int Cin, int Xl, int Yl, int NZ, int s) {
   if (Cin < 3 || Xl <= 0 || Yl <= 0 || NZ <= 0 || s <= 0) return false;
   const long X = (long)Xl * s, Y = (long)Yl * s;

@@ -1118,3 +1118,54 @@ def column_interp(vals: Tensor, z_src: Tensor, z_dst: Tensor) -> Tensor:
     check(_lib.lib().wsr_column_interp(_p(vals), _p(z_src), _p(z_dst), B, C, X * Y, NZ, _p(out), _stream()),
           "column_interp")
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# geometric self-ensemble ([ENSEMBLE]; csrc/ensemble.hip)
+# ---------------------------------------------------------------------------------------------------------------------
+def _member_codes(name: str, codes, X: int, Y: int):
+    codes = [int(c) for c in codes]
+    if len(codes) not in (1, 2, 4, 8) or any(c < 0 or c > 7 for c in codes):
+        raise ValueError(f"{name} wants 1, 2, 4 or 8 member codes k + 4 * fx in 0..7, got {codes}")
+    if X != Y and any(c & 1 for c in codes):
+        raise ValueError(f"{name}: a member with an odd number of quarter turns needs a square domain, "
+                         f"not X = {X}, Y = {Y}")
+    return (C.c_int32 * len(codes))(*codes), len(codes)
+
+
+def dihedral_members(src: Tensor, codes, is_vector: bool) -> Tensor:
+    """The ``K = len(codes)`` transformed copies of ``src`` fp32 (B, C, X, Y, NZ) in ONE launch -> (K, B, C, X', Y', NZ).
+    A code is ``k + 4 * fx``: ``k`` quarter turns as ``process_data._rotate_wind`` does them, then, if ``fx``, a mirror
+    along x.  ``is_vector``: channels 0 and 1 are the horizontal wind (they turn with the grid, the mirror negates u);
+    otherwise every channel is only permuted.  Bit-identical to the CPU rules (``wsr_dihedral_members``)."""
+    _need_cuda(src)
+    _planar5("dihedral_members", "src", src, 2 if is_vector else 1)
+    B, Cn, X, Y, NZ = src.shape
+    arr, K = _member_codes("dihedral_members", codes, X, Y)
+    odd = any(int(c) & 1 for c in codes)
+    out = torch.empty((K, B, Cn, Y if odd else X, X if odd else Y, NZ), dtype=torch.float32, device=src.device)
+    check(_lib.lib().wsr_dihedral_members(_p(src), B, Cn, X, Y, NZ, arr, K, 1 if is_vector else 0, _p(out), _stream()),
+          "dihedral_members")
+    return out
+
+
+def ensemble_reduce(members: Tensor, codes, with_var: bool = False):
+    """``members`` fp32 (K, B, 3, X', Y', NZ), member ``m`` transformed by ``codes[m]`` -> the mean (B, 3, X, Y, NZ) of
+    the members mapped back through their inverses, as the pairwise tree sum in member order times ``1 / K``; with
+    ``with_var`` also the population variance per component, ``(mean, var)``.  One pass, no atomics: the same bits on
+    every call (``wsr_ensemble_reduce``)."""
+    _need_cuda(members)
+    if members.dtype != torch.float32 or members.dim() != 6 or not members.is_contiguous() or members.shape[2] != 3 \
+            or members.numel() == 0:
+        raise ValueError(f"ensemble_reduce wants members as a contiguous fp32 (K, B, 3, X, Y, NZ) tensor, got "
+                         f"{members.dtype} {tuple(members.shape)}")
+    K, B, _, X, Y, NZ = members.shape
+    arr, n = _member_codes("ensemble_reduce", codes, X, Y)
+    if n != K:
+        raise ValueError(f"ensemble_reduce: {n} codes for {K} members")
+    # (odd quarter turns only on a square plane: the members' shape is the output's)
+    mean = torch.empty((B, 3, X, Y, NZ), dtype=torch.float32, device=members.device)
+    var = torch.empty_like(mean) if with_var else None
+    check(_lib.lib().wsr_ensemble_reduce(_p(members), arr, K, B, X, Y, NZ, _p(mean), _p(var), _stream()),
+          "ensemble_reduce")
+    return (mean, var) if with_var else mean

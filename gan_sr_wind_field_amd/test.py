@@ -17,9 +17,16 @@ for the pickled fields (``log_period`` counts batches: every ``log_period``-th b
 set than without the section).  With ``reverse_interpolate`` the re-levelling is ``hip_ops.column_interp``.  Same CSV files,
 headers and row order; the values differ in their low digits (another summation order).  On a CPU device the section keeps the
 composed torch path below.
+
+With an ``[ENSEMBLE]`` section on a GPU both loops take SR from ``gan.G_ensemble`` (the generator averaged over
+``members`` symmetries of the square, ``ensemble.py``); everything downstream is as without it.  ``write_spread`` adds
+    ./test_output/<cfg.name>____ensemble_spread.csv               one row ``field,mean_spread`` per field
+(the mean over voxels of ``sqrt(var_u + var_v + var_w) * UVW_MAX``, var the variance between the members) and the key
+``SR_spread`` (the standard deviation per component, normalised units) in the pickled fields.
 """
 from __future__ import annotations
 
+import contextlib
 import logging
 import math
 import os
@@ -78,8 +85,11 @@ def write_metrics(HR, SR, trilinear, field_name, dest_file, UVW_MAX):
     return tuple(m[k] for k in METRIC_NAMES)
 
 
-def write_fields(LR, HR, SR, interpolated_LR, Z, folder_path, field_name, rawHR=None, Z_raw=None, SR_orig=None):
+def write_fields(LR, HR, SR, interpolated_LR, Z, folder_path, field_name, rawHR=None, Z_raw=None, SR_orig=None,
+                 SR_spread=None):
     fields = {"HR": HR, "SR": SR, "TL": interpolated_LR, "LR": LR, "Z": Z}
+    if SR_spread is not None:
+        fields["SR_spread"] = SR_spread
     if rawHR is not None and torch.is_tensor(rawHR) and rawHR.numel() > 0:
         fields.update({"HR_orig": rawHR, "Z_orig": Z_raw, "SR_orig": SR_orig})
     fields = {k: (v.squeeze().cpu().numpy() if torch.is_tensor(v) else v) for k, v in fields.items() if v is not None}
@@ -94,15 +104,34 @@ def _header(path: str, line: str) -> None:
             f.write(line + "\n")
 
 
-def _host_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev):
+def _generate(cfg, gan, LR_d, Z_d):
+    """SR of a device batch and the variance between the ensemble members (None unless ``[ENSEMBLE] write_spread``);
+    without the section, or on a CPU device, the plain generator forward"""
+    ens = cfg.ensemble
+    if not (ens.present and torch.device(cfg.device).type == "cuda"):
+        with torch.no_grad():
+            return gan.G(LR_d, Z_d), None
+    if ens.write_spread:
+        return gan.G_ensemble(LR_d, Z_d, with_var=True)
+    return gan.G_ensemble(LR_d, Z_d), None
+
+
+def _mean_spread(var: torch.Tensor, uvw: float) -> torch.Tensor:
+    """per field: the mean over voxels of sqrt(var_u + var_v + var_w) in m/s -> (B,)"""
+    return torch.sqrt(var.sum(dim=1)).flatten(1).mean(dim=1) * uvw
+
+
+def _host_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread=None):
     """one field at a time; baseline, re-levelling and metrics on the host (the reference's loop)"""
     dev = cfg.device
     for j, (LR, HR, Z, names, HR_raw, Z_raw) in enumerate(loader):
         TL = nn.functional.interpolate(LR[:, :3], scale_factor=(cfg.scale, cfg.scale, 1), mode="trilinear",
                                        align_corners=True)
         for i in range(LR.shape[0]):
-            with torch.no_grad():
-                SR_i = gan.G(LR[i:i + 1].to(dev, non_blocking=True), Z[i:i + 1].to(dev, non_blocking=True)).cpu()
+            SR_i, var_i = _generate(cfg, gan, LR[i:i + 1].to(dev, non_blocking=True), Z[i:i + 1].to(dev, non_blocking=True))
+            SR_i = SR_i.cpu()
+            if var_i is not None:
+                spread.write(f"{names[i]},{float(_mean_spread(var_i, uvw)[0])}\n")
             HR_i, TL_i = HR[i:i + 1, :3], TL[i:i + 1]
             if rev:  # back onto the raw terrain-following levels of every column
                 SR_r = reverse_interpolate_z_axis(SR_i.numpy(), Z_raw[i:i + 1].numpy(), Z[i:i + 1].numpy())
@@ -115,16 +144,18 @@ def _host_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev):
                 avg[k] += v / n
             if j % cfg.training.log_period == 0:
                 write_fields(LR[i], HR[i], SR_i[0], TL[i], Z[i], cfg.env.this_runs_folder, names[i],
-                             HR_raw[i] if rev else None, Z_raw[i] if rev else None, None)
+                             HR_raw[i] if rev else None, Z_raw[i] if rev else None, None,
+                             None if var_i is None else torch.sqrt(var_i[0]))
 
 
-def _device_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev):
+def _device_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread=None):
     """[EVAL] device_metrics: one generator forward and one metrics launch per batch; the (B, 7) rows wait in a device
     table and are read once per ``log_period`` batches and at the end"""
     from . import hip_ops
 
     dev, s = cfg.device, cfg.scale
     pending = []  # (names, nvox, sums (B, 7), sums on the raw levels (B, 7) or None) of the batches not yet written
+    spreads = []  # ([ENSEMBLE] write_spread) (names, mean spread (B,)) of the batches not yet written
 
     def flush():
         if not pending:
@@ -142,11 +173,18 @@ def _device_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev):
                     for k in METRIC_NAMES:
                         acc[k] += m[k] / n
         pending.clear()
+        if spreads:
+            vals = torch.cat([t for _, t in spreads]).cpu().tolist()
+            for name, v in zip([nm for names, _ in spreads for nm in names], vals):
+                spread.write(f"{name},{v}\n")
+            spreads.clear()
 
     for j, (LR, HR, Z, names, HR_raw, Z_raw) in enumerate(loader):
         LR_d, HR_d, Z_d = (t.to(dev, non_blocking=True).contiguous() for t in (LR, HR, Z))
-        with torch.no_grad():
-            SR_d = gan.G(LR_d, Z_d).float().contiguous()
+        SR_d, var_d = _generate(cfg, gan, LR_d, Z_d)
+        SR_d = SR_d.float().contiguous()
+        if var_d is not None:
+            spreads.append((list(names), _mean_spread(var_d, uvw)))
         nvox = HR.shape[2] * HR.shape[3] * HR.shape[4]
         sums = hip_ops.field_metrics(HR_d, SR_d, LR=LR_d, scale=s)  # (the baseline is blended inside, never stored)
         keep = j % cfg.training.log_period == 0
@@ -160,9 +198,11 @@ def _device_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev):
         pending.append((list(names), nvox, sums, sums_raw))
         if keep:
             SR_h, TL_h = SR_d.cpu(), TL_d.cpu()
+            sd_h = None if var_d is None else torch.sqrt(var_d).cpu()
             for i in range(LR.shape[0]):
                 write_fields(LR[i], HR[i], SR_h[i], TL_h[i], Z[i], cfg.env.this_runs_folder, names[i],
-                             HR_raw[i] if rev else None, Z_raw[i] if rev else None, None)
+                             HR_raw[i] if rev else None, Z_raw[i] if rev else None, None,
+                             None if sd_h is None else sd_h[i])
             flush()
     flush()
 
@@ -198,13 +238,19 @@ def test(cfg, dataset_test, reverse_interpolate: bool = False):
     avg_rev = {k: 0.0 for k in METRIC_NAMES}
     dev = cfg.device
     log.info("beginning test")
-    with open(metrics_path, "w") as out, (open(rev_path, "w") if rev else open(os.devnull, "w")) as out_rev:
+    # ([ENSEMBLE] write_spread on a GPU: one more CSV, the spread between the members per field)
+    with_spread = cfg.ensemble.present and cfg.ensemble.write_spread and torch.device(dev).type == "cuda"
+    spread_path = os.path.join("./test_output", cfg.name + "____ensemble_spread.csv")
+    with open(metrics_path, "w") as out, (open(rev_path, "w") if rev else open(os.devnull, "w")) as out_rev, \
+            (open(spread_path, "w") if with_spread else contextlib.nullcontext()) as spread:
         out.write(cols + "\n")
         out_rev.write(cols + "\n")
+        if with_spread:
+            spread.write("field,mean_spread\n")
         if cfg.eval.on and torch.device(dev).type == "cuda":
-            _device_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev)
+            _device_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread)
         else:
-            _host_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev)
+            _host_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread)
     with open("./test_output/averages.csv", "a") as f:
         f.write(cfg.name + "," + ",".join(str(avg[k]) for k in METRIC_NAMES) + "\n")
     for k in METRIC_NAMES:

@@ -564,6 +564,27 @@ int wsr_field_metrics(const float* hr, int32_t hr_c, const float* sr, int32_t sr
 int wsr_column_interp(const float* vals, const float* z_src, const float* z_dst, int32_t B, int32_t C, int64_t ncols,
                       int32_t NZ, float* out, void* stream);
 
+/* ---- geometric self-ensemble ([ENSEMBLE]; csrc/ensemble.hip) ------------------------------------------
+ * The eight symmetries of the square on fp32 planar tensors (B, C, X, Y, NZ).  A member is (k, fx), code k + 4 * fx:
+ * k quarter turns as process_data._rotate_wind does them, then, if fx, a mirror along x with u negated (the order of
+ * CustomizedDataset.__getitem__: rotate, then flip).  Its inverse: undo the mirror, then _rotate_wind by (4 - k) % 4.
+ * codes: a HOST array of K codes, K = 1, 2, 4 or 8 (passed to the kernel by value).  A code with odd k needs X == Y
+ * (WSR_EINVAL otherwise, nothing is written).  Only sign bits change: bit-identical to the CPU rules.
+ *
+ * wsr_dihedral_members: dst (K, B, C, X', Y', NZ) = the K transformed copies of src (B, C, X, Y, NZ) in ONE launch
+ * ((X', Y') = (Y, X) for odd k).  is_vector: channels 0 and 1 are the horizontal wind and turn with the grid
+ * (C >= 2); 0: every channel is a scalar and is only permuted.
+ *
+ * wsr_ensemble_reduce: members (K, B, 3, X', Y', NZ), member m transformed by codes[m] -> mean (B, 3, X, Y, NZ) of the
+ * members mapped back through their inverses: the pairwise tree sum in member order ((m0 + m1) + (m2 + m3)) + ...
+ * times 1 / K, so K identical members give the member back bit for bit.  var (B, 3, X, Y, NZ) or NULL: the population
+ * variance per component, the same tree over (m_k - mean)^2.  One pass, no atomics: the same bits on every call.  */
+#define WSR_ENSEMBLE_MAX_MEMBERS 8
+int wsr_dihedral_members(const float* src, int32_t B, int32_t C, int32_t X, int32_t Y, int32_t NZ,
+                         const int32_t* codes, int32_t K, int32_t is_vector, float* dst, void* stream);
+int wsr_ensemble_reduce(const float* members, const int32_t* codes, int32_t K, int32_t B, int32_t X, int32_t Y,
+                        int32_t NZ, float* mean, float* var, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
