@@ -636,6 +636,41 @@ class wind_field_GAN_3D(BaseGAN):
         with torch.no_grad():
             return self_ensemble(self.G, LR.contiguous(), Z.contiguous(), members=members, with_var=with_var)
 
+    # ------------------------------------------------------------------ tiled whole-domain inference ([TILE])
+    def G_tiled(self, LR, Z, tile=None, overlap=None, tiles_per_forward=None, members=1, with_seam: bool = False,
+                with_var: bool = False):
+        """The generator on overlapping (x, y) tiles of ``tile`` LR voxels, blended into one field
+        (``tiling.tiled_forward``; None: the value of ``[TILE]``): one generator forward per ``tiles_per_forward`` stacked
+        tiles under ``no_grad``, with the weights the generator holds (inside ``ema_scope()`` the averaged ones) and in
+        the mode it is in.  ``members`` > 1 sends every chunk through ``ensemble.self_ensemble``; ``with_var`` then also
+        blends the per-tile variances between the members (a blend of per-tile variances, not the variance of blended
+        members).  -> fp32 ``SR`` (B, 3, X, Y, NZ), followed - as a tuple - by ``var`` (``with_var``) and by the seam
+        map ``sum alpha_T (x_T - SR)^2`` (``with_seam``)."""
+        from ..ensemble import self_ensemble
+        from ..tiling import tiled_forward
+
+        t = self.cfg.tile
+        tile = t.tile if tile is None else tile
+        overlap = t.overlap if overlap is None else overlap
+        tiles_per_forward = t.tiles_per_forward if tiles_per_forward is None else tiles_per_forward
+        if tile is None:
+            raise ValueError("G_tiled needs a tile size: pass tile or give [TILE] tile")
+        fn = self.G
+        if members != 1 or with_var:
+            tx, ty = min(tile, LR.shape[2]), min(tile, LR.shape[3])
+            if members == 8 and tx != ty:
+                raise ValueError(f"members = 8 turns every tile by quarter turns and needs square tiles, not {tx} x {ty} "
+                                 f"(tile = {tile} on a domain of {LR.shape[2]} x {LR.shape[3]}; members = 4 works)")
+
+            def fn(lr, z):
+                return self_ensemble(self.G, lr, z, members=members, with_var=with_var)
+        with torch.no_grad():
+            res = tiled_forward(fn, LR.contiguous(), Z.contiguous(), self.cfg.scale, tile, overlap, tiles_per_forward,
+                                with_seam=with_seam)
+        SR, seam = res if with_seam else (res, None)
+        out = (tuple(SR) if with_var else (SR,)) + ((seam,) if with_seam else ())
+        return out[0] if len(out) == 1 else out
+
     def make_new_labels(self, it):
         """Real / fake label vectors of this iteration (reference :627-678)."""
         t = self.cfg.training

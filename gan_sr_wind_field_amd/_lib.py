@@ -25,6 +25,7 @@ EXPORTS = [
     "wsr_adam_multi_clip", "wsr_adam_multi_ema", "wsr_adam_multi_clip_ema",
     "wsr_trilinear_xy", "wsr_field_metrics", "wsr_column_interp",
     "wsr_dihedral_members", "wsr_ensemble_reduce",
+    "wsr_tile_gather", "wsr_tile_stitch",
 ]
 
 
@@ -150,6 +151,10 @@ def lib() -> C.CDLL:
         "wsr_column_interp": [vp, vp, vp, i32, i32, i64, i32, vp, vp],   # additive export
         "wsr_dihedral_members": [vp, i32, i32, i32, i32, i32, C.POINTER(C.c_int32), i32, i32, vp, vp],   # additive export
         "wsr_ensemble_reduce": [vp, C.POINTER(C.c_int32), i32, i32, i32, i32, i32, vp, vp, vp],   # additive export
+        "wsr_tile_gather": [vp, i32, i32, i32, i32, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), i32, i32, i32, vp,
+                            vp],   # additive export
+        "wsr_tile_stitch": [vp, C.POINTER(C.c_int32), i32, C.POINTER(C.c_int32), i32, i32, i32, i32, i32, i32, i32, i32,
+                            i32, i32, vp, vp, vp],   # additive export
     }
     for name, argtypes in sig.items():
         fn = getattr(L, name)

@@ -22,6 +22,10 @@ Extension (optional keys, defaults keep reference behaviour):
   [ENSEMBLE] members / write_spread
             --test averages the generator over 1, 2, 4 or 8 symmetries of the square (ensemble.py,
             csrc/ensemble.hip) and can write the spread between the members
+  [TILE] tile / overlap / tiles_per_forward / write_seam
+            --test runs the generator on overlapping tiles of ``tile`` LR voxels in x and y and blends the outputs
+            (tiling.py, csrc/tiling.hip): the whole domain at the geometry of training, memory following
+            tiles_per_forward instead of the domain; can write how far the tiles disagree in their overlaps
 """
 from __future__ import annotations
 
@@ -417,6 +421,47 @@ class EnsembleConfig(IniConfig):
         return "[ENSEMBLE]\n" + "".join(f"{k} = {getattr(self, k)}\n" for k, _ in self._schema)
 
 
+class TileConfig(IniConfig):
+    """[TILE] (extension): tiled whole-domain inference of ``run.py --test`` (tiling.py, csrc/tiling.hip); absent section =
+    off, and not printed by ``asINI``.  ``tile`` (required): LR voxels per tile side in x and y, an axis shorter than
+    this is one tile; ``overlap``: LR voxels neighbouring tiles share at least, 0 .. tile // 2; ``tiles_per_forward``:
+    tiles stacked into one generator forward; ``write_seam``: ``--test`` also writes ``<name>____tile_seam.csv`` and
+    pickles ``SR_seam``."""
+
+    present: bool = False
+    tile: int = None
+    overlap: int = 4
+    tiles_per_forward: int = 8
+    write_seam: bool = False
+    _schema = (("tile", _I), ("overlap", _I), ("tiles_per_forward", _I), ("write_seam", _B))
+
+    def setTileConfig(self, section):
+        """``section`` None (no [TILE] in the file) restores the defaults and switches the section off."""
+        self.present = section is not None
+        for key, kind in self._schema:
+            try:
+                val = None if section is None else _read(section, key, kind)
+            except ValueError:
+                raise ValueError(f"[TILE] {key} must be {'True or False' if kind == _B else 'an integer'}, not "
+                                 f"{section.get(key)!r}") from None
+            setattr(self, key, getattr(TileConfig, key) if val is None else val)
+
+    def validate(self) -> None:
+        if not self.present:
+            return
+        if self.tile is None:
+            raise ValueError("[TILE] tile is required: LR voxels per tile side")
+        if self.tile < 1:
+            raise ValueError(f"[TILE] tile must be >= 1, not {self.tile}")
+        if not 0 <= self.overlap <= self.tile // 2:
+            raise ValueError(f"[TILE] overlap must be in 0 .. tile // 2 = {self.tile // 2}, not {self.overlap}")
+        if self.tiles_per_forward < 1:
+            raise ValueError(f"[TILE] tiles_per_forward must be >= 1, not {self.tiles_per_forward}")
+
+    def __str__(self) -> str:
+        return "[TILE]\n" + "".join(f"{k} = {getattr(self, k)}\n" for k, _ in self._schema)
+
+
 class Config(IniConfig):
     name: str = "default_name"
     model: str = "default_model"
@@ -443,6 +488,7 @@ class Config(IniConfig):
     ema: EmaConfig = EmaConfig()
     eval: EvalConfig = EvalConfig()
     ensemble: EnsembleConfig = EnsembleConfig()
+    tile: TileConfig = TileConfig()
     compute_dtype: str = "fp32"
     is_train: bool
     is_use: bool
@@ -477,6 +523,8 @@ class Config(IniConfig):
         self.eval.validate(self.gan_config.interpolate_z)
         self.ensemble.setEnsembleConfig(parser["ENSEMBLE"] if parser.has_section("ENSEMBLE") else None)
         self.ensemble.validate()
+        self.tile.setTileConfig(parser["TILE"] if parser.has_section("TILE") else None)
+        self.tile.validate()
 
     def setBaseConfig(self, base):
         self.name = base.get("name")
@@ -512,4 +560,6 @@ class Config(IniConfig):
             out += "\n" + str(self.eval)
         if getattr(self.ensemble, "present", False):
             out += "\n" + str(self.ensemble)
+        if getattr(self.tile, "present", False):
+            out += "\n" + str(self.tile)
         return out

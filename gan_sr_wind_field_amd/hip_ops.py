@@ -1169,3 +1169,79 @@ def ensemble_reduce(members: Tensor, codes, with_var: bool = False):
     check(_lib.lib().wsr_ensemble_reduce(_p(members), arr, K, B, X, Y, NZ, _p(mean), _p(var), _stream()),
           "ensemble_reduce")
     return (mean, var) if with_var else mean
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# tiled whole-domain inference ([TILE]; csrc/tiling.hip)
+# ---------------------------------------------------------------------------------------------------------------------
+#: WSR_TILE_MAX_PER_AXIS of include/windsr_hip.h: the origins of an axis travel by value in the stitch launch
+TILE_MAX_PER_AXIS = 128
+
+
+def _origins(name: str, what: str, vals):
+    vals = [int(v) for v in vals]
+    if not vals:
+        raise ValueError(f"{name} wants at least one origin in {what}")
+    return (C.c_int32 * len(vals))(*vals), vals
+
+
+def tile_gather(src: Tensor, x0, y0, tx: int, ty: int) -> Tensor:
+    """The ``n = len(x0)`` tiles ``src[:, :, x0[k]:x0[k] + tx, y0[k]:y0[k] + ty, :]`` of ``src`` fp32 (B, C, X, Y, NZ) in
+    ONE launch -> (n, B, C, tx, ty, NZ); a pure copy, the bits of torch slicing (``wsr_tile_gather``)."""
+    _need_cuda(src)
+    _planar5("tile_gather", "src", src)
+    B, Cn, X, Y, NZ = src.shape
+    tx, ty = int(tx), int(ty)
+    ax, xl = _origins("tile_gather", "x0", x0)
+    ay, yl = _origins("tile_gather", "y0", y0)
+    if len(xl) != len(yl):
+        raise ValueError(f"tile_gather: {len(xl)} origins in x0 for {len(yl)} in y0")
+    if not (1 <= tx <= X and 1 <= ty <= Y):
+        raise ValueError(f"tile_gather wants tiles inside the domain, not tx = {tx}, ty = {ty} for X = {X}, Y = {Y}")
+    for k, (a, b) in enumerate(zip(xl, yl)):
+        if a < 0 or b < 0 or a + tx > X or b + ty > Y:
+            raise ValueError(f"tile_gather: tile {k} at ({a}, {b}) of {tx} x {ty} leaves the domain X = {X}, Y = {Y}")
+    out = torch.empty((len(xl), B, Cn, tx, ty, NZ), dtype=torch.float32, device=src.device)
+    check(_lib.lib().wsr_tile_gather(_p(src), B, Cn, X, Y, NZ, ax, ay, len(xl), tx, ty, _p(out), _stream()),
+          "tile_gather")
+    return out
+
+
+def _tile_axis(name: str, axis: str, s, T: int, N: int, R: int) -> None:
+    if not 1 <= T <= N:
+        raise ValueError(f"{name} wants 1 <= T{axis} <= {axis.upper()}, not T{axis} = {T}, {axis.upper()} = {N}")
+    if not 0 <= R <= 32768:
+        raise ValueError(f"{name} wants 0 <= R{axis} <= 32768, not {R}")
+    if s[0] != 0 or s[-1] + T != N:
+        raise ValueError(f"{name}: the {axis} origins must start at 0 and end at {axis.upper()} - T{axis} = {N - T}, "
+                         f"got {s[0]} .. {s[-1]}")
+    for a, b in zip(s, s[1:]):
+        if not 0 < b - a <= T:
+            raise ValueError(f"{name}: the {axis} origins must increase by 1 .. T{axis} = {T}, got {a} -> {b}")
+    if len(s) > TILE_MAX_PER_AXIS:
+        raise ValueError(f"{name}: {len(s)} tiles along {axis}, at most {TILE_MAX_PER_AXIS}")
+
+
+def tile_stitch(tiles: Tensor, xs, ys, X: int, Y: int, Rx: int, Ry: int, with_seam: bool = False):
+    """``tiles`` fp32 (nx * ny, B, C, Tx, Ty, NZ), tile ``ix * ny + iy`` at origin ``(xs[ix], ys[iy])`` -> their blend
+    (B, C, X, Y, NZ): ``sum alpha_T x_T`` with the separable integer ramps of include/windsr_hip.h (``Rx``, ``Ry`` the
+    ramp lengths, no ramp at a domain border), every output voxel written once; with ``with_seam`` also
+    ``sum alpha_T (x_T - out)^2``, ``(out, seam)``.  Where one tile covers a voxel its value comes back bit for bit.  No
+    atomics: the same bits on every call (``wsr_tile_stitch``)."""
+    _need_cuda(tiles)
+    if tiles.dtype != torch.float32 or tiles.dim() != 6 or not tiles.is_contiguous() or tiles.numel() == 0:
+        raise ValueError(f"tile_stitch wants tiles as a contiguous fp32 (nx * ny, B, C, Tx, Ty, NZ) tensor, got "
+                         f"{tiles.dtype} {tuple(tiles.shape)}")
+    n, B, Cn, Tx, Ty, NZ = tiles.shape
+    X, Y, Rx, Ry = int(X), int(Y), int(Rx), int(Ry)
+    ax, xl = _origins("tile_stitch", "xs", xs)
+    ay, yl = _origins("tile_stitch", "ys", ys)
+    if len(xl) * len(yl) != n:
+        raise ValueError(f"tile_stitch: {len(xl)} x {len(yl)} origins for {n} tiles")
+    _tile_axis("tile_stitch", "x", xl, Tx, X, Rx)
+    _tile_axis("tile_stitch", "y", yl, Ty, Y, Ry)
+    out = torch.empty((B, Cn, X, Y, NZ), dtype=torch.float32, device=tiles.device)
+    seam = torch.empty_like(out) if with_seam else None
+    check(_lib.lib().wsr_tile_stitch(_p(tiles), ax, len(xl), ay, len(yl), B, Cn, X, Y, NZ, Tx, Ty, Rx, Ry, _p(out),
+                                     _p(seam), _stream()), "tile_stitch")
+    return (out, seam) if with_seam else out

@@ -23,6 +23,14 @@ With an ``[ENSEMBLE]`` section on a GPU both loops take SR from ``gan.G_ensemble
     ./test_output/<cfg.name>____ensemble_spread.csv               one row ``field,mean_spread`` per field
 (the mean over voxels of ``sqrt(var_u + var_v + var_w) * UVW_MAX``, var the variance between the members) and the key
 ``SR_spread`` (the standard deviation per component, normalised units) in the pickled fields.
+
+With a ``[TILE]`` section on a GPU both loops take SR from ``gan.G_tiled`` (the generator on overlapping tiles of the
+size it was trained on, blended; ``tiling.py``), with ``[ENSEMBLE]`` as well every tile averaged over its ``members``;
+``write_spread`` then blends the per-tile variances with the tiles' weights (a blend of per-tile variances, not the
+variance of blended members).  ``write_seam`` adds
+    ./test_output/<cfg.name>____tile_seam.csv                     one row ``field,mean_seam`` per field
+(the mean over voxels of ``sqrt(seam_u + seam_v + seam_w) * UVW_MAX``, seam the weighted squared distance of the tiles
+from their blend) and the key ``SR_seam`` (``sqrt(seam)`` per component) in the pickled fields.
 """
 from __future__ import annotations
 
@@ -86,10 +94,12 @@ def write_metrics(HR, SR, trilinear, field_name, dest_file, UVW_MAX):
 
 
 def write_fields(LR, HR, SR, interpolated_LR, Z, folder_path, field_name, rawHR=None, Z_raw=None, SR_orig=None,
-                 SR_spread=None):
+                 SR_spread=None, SR_seam=None):
     fields = {"HR": HR, "SR": SR, "TL": interpolated_LR, "LR": LR, "Z": Z}
     if SR_spread is not None:
         fields["SR_spread"] = SR_spread
+    if SR_seam is not None:
+        fields["SR_seam"] = SR_seam
     if rawHR is not None and torch.is_tensor(rawHR) and rawHR.numel() > 0:
         fields.update({"HR_orig": rawHR, "Z_orig": Z_raw, "SR_orig": SR_orig})
     fields = {k: (v.squeeze().cpu().numpy() if torch.is_tensor(v) else v) for k, v in fields.items() if v is not None}
@@ -104,16 +114,29 @@ def _header(path: str, line: str) -> None:
             f.write(line + "\n")
 
 
-def _generate(cfg, gan, LR_d, Z_d):
-    """SR of a device batch and the variance between the ensemble members (None unless ``[ENSEMBLE] write_spread``);
-    without the section, or on a CPU device, the plain generator forward"""
-    ens = cfg.ensemble
-    if not (ens.present and torch.device(cfg.device).type == "cuda"):
+def _generate_fields(cfg, gan, LR_d, Z_d):
+    """-> (SR, var, seam) of a device batch - the single point where both loops obtain SR: the variance between the
+    ensemble members (None unless ``[ENSEMBLE] write_spread``) and the seam map of the tiles (None unless ``[TILE]
+    write_seam``); without either section, or on a CPU device, the plain generator forward"""
+    ens, tile = cfg.ensemble, getattr(cfg, "tile", None)
+    on_gpu = torch.device(cfg.device).type == "cuda"
+    if tile is not None and tile.present and on_gpu:
+        with_var = bool(ens.present and ens.write_spread)
+        res = gan.G_tiled(LR_d, Z_d, members=ens.members if ens.present else 1, with_var=with_var,
+                          with_seam=tile.write_seam)
+        res = list(res) if isinstance(res, tuple) else [res]
+        return res[0], (res[1] if with_var else None), (res[-1] if tile.write_seam else None)
+    if not (ens.present and on_gpu):
         with torch.no_grad():
-            return gan.G(LR_d, Z_d), None
+            return gan.G(LR_d, Z_d), None, None
     if ens.write_spread:
-        return gan.G_ensemble(LR_d, Z_d, with_var=True)
-    return gan.G_ensemble(LR_d, Z_d), None
+        return gan.G_ensemble(LR_d, Z_d, with_var=True) + (None,)
+    return gan.G_ensemble(LR_d, Z_d), None, None
+
+
+def _generate(cfg, gan, LR_d, Z_d):
+    """SR and the variance between the ensemble members of ``_generate_fields``"""
+    return _generate_fields(cfg, gan, LR_d, Z_d)[:2]
 
 
 def _mean_spread(var: torch.Tensor, uvw: float) -> torch.Tensor:
@@ -121,17 +144,20 @@ def _mean_spread(var: torch.Tensor, uvw: float) -> torch.Tensor:
     return torch.sqrt(var.sum(dim=1)).flatten(1).mean(dim=1) * uvw
 
 
-def _host_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread=None):
+def _host_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread=None, seam=None):
     """one field at a time; baseline, re-levelling and metrics on the host (the reference's loop)"""
     dev = cfg.device
     for j, (LR, HR, Z, names, HR_raw, Z_raw) in enumerate(loader):
         TL = nn.functional.interpolate(LR[:, :3], scale_factor=(cfg.scale, cfg.scale, 1), mode="trilinear",
                                        align_corners=True)
         for i in range(LR.shape[0]):
-            SR_i, var_i = _generate(cfg, gan, LR[i:i + 1].to(dev, non_blocking=True), Z[i:i + 1].to(dev, non_blocking=True))
+            SR_i, var_i, seam_i = _generate_fields(cfg, gan, LR[i:i + 1].to(dev, non_blocking=True),
+                                                   Z[i:i + 1].to(dev, non_blocking=True))
             SR_i = SR_i.cpu()
             if var_i is not None:
                 spread.write(f"{names[i]},{float(_mean_spread(var_i, uvw)[0])}\n")
+            if seam_i is not None:  # (the same reduction: sqrt of the sum over components, mean over voxels)
+                seam.write(f"{names[i]},{float(_mean_spread(seam_i, uvw)[0])}\n")
             HR_i, TL_i = HR[i:i + 1, :3], TL[i:i + 1]
             if rev:  # back onto the raw terrain-following levels of every column
                 SR_r = reverse_interpolate_z_axis(SR_i.numpy(), Z_raw[i:i + 1].numpy(), Z[i:i + 1].numpy())
@@ -145,10 +171,11 @@ def _host_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread
             if j % cfg.training.log_period == 0:
                 write_fields(LR[i], HR[i], SR_i[0], TL[i], Z[i], cfg.env.this_runs_folder, names[i],
                              HR_raw[i] if rev else None, Z_raw[i] if rev else None, None,
-                             None if var_i is None else torch.sqrt(var_i[0]))
+                             None if var_i is None else torch.sqrt(var_i[0]),
+                             None if seam_i is None else torch.sqrt(seam_i[0]))
 
 
-def _device_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread=None):
+def _device_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread=None, seam=None):
     """[EVAL] device_metrics: one generator forward and one metrics launch per batch; the (B, 7) rows wait in a device
     table and are read once per ``log_period`` batches and at the end"""
     from . import hip_ops
@@ -156,6 +183,7 @@ def _device_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spre
     dev, s = cfg.device, cfg.scale
     pending = []  # (names, nvox, sums (B, 7), sums on the raw levels (B, 7) or None) of the batches not yet written
     spreads = []  # ([ENSEMBLE] write_spread) (names, mean spread (B,)) of the batches not yet written
+    seams = []  # ([TILE] write_seam) (names, mean seam (B,)) of the batches not yet written
 
     def flush():
         if not pending:
@@ -173,18 +201,21 @@ def _device_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spre
                     for k in METRIC_NAMES:
                         acc[k] += m[k] / n
         pending.clear()
-        if spreads:
-            vals = torch.cat([t for _, t in spreads]).cpu().tolist()
-            for name, v in zip([nm for names, _ in spreads for nm in names], vals):
-                spread.write(f"{name},{v}\n")
-            spreads.clear()
+        for rows, dest in ((spreads, spread), (seams, seam)):
+            if rows:
+                vals = torch.cat([t for _, t in rows]).cpu().tolist()
+                for name, v in zip([nm for names, _ in rows for nm in names], vals):
+                    dest.write(f"{name},{v}\n")
+                rows.clear()
 
     for j, (LR, HR, Z, names, HR_raw, Z_raw) in enumerate(loader):
         LR_d, HR_d, Z_d = (t.to(dev, non_blocking=True).contiguous() for t in (LR, HR, Z))
-        SR_d, var_d = _generate(cfg, gan, LR_d, Z_d)
+        SR_d, var_d, seam_d = _generate_fields(cfg, gan, LR_d, Z_d)
         SR_d = SR_d.float().contiguous()
         if var_d is not None:
             spreads.append((list(names), _mean_spread(var_d, uvw)))
+        if seam_d is not None:
+            seams.append((list(names), _mean_spread(seam_d, uvw)))
         nvox = HR.shape[2] * HR.shape[3] * HR.shape[4]
         sums = hip_ops.field_metrics(HR_d, SR_d, LR=LR_d, scale=s)  # (the baseline is blended inside, never stored)
         keep = j % cfg.training.log_period == 0
@@ -199,10 +230,11 @@ def _device_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spre
         if keep:
             SR_h, TL_h = SR_d.cpu(), TL_d.cpu()
             sd_h = None if var_d is None else torch.sqrt(var_d).cpu()
+            seam_h = None if seam_d is None else torch.sqrt(seam_d).cpu()
             for i in range(LR.shape[0]):
                 write_fields(LR[i], HR[i], SR_h[i], TL_h[i], Z[i], cfg.env.this_runs_folder, names[i],
                              HR_raw[i] if rev else None, Z_raw[i] if rev else None, None,
-                             None if sd_h is None else sd_h[i])
+                             None if sd_h is None else sd_h[i], None if seam_h is None else seam_h[i])
             flush()
     flush()
 
@@ -241,16 +273,22 @@ def test(cfg, dataset_test, reverse_interpolate: bool = False):
     # ([ENSEMBLE] write_spread on a GPU: one more CSV, the spread between the members per field)
     with_spread = cfg.ensemble.present and cfg.ensemble.write_spread and torch.device(dev).type == "cuda"
     spread_path = os.path.join("./test_output", cfg.name + "____ensemble_spread.csv")
+    # ([TILE] write_seam on a GPU: one more CSV, the disagreement of the tiles in their overlaps per field)
+    with_seam = cfg.tile.present and cfg.tile.write_seam and torch.device(dev).type == "cuda"
+    seam_path = os.path.join("./test_output", cfg.name + "____tile_seam.csv")
     with open(metrics_path, "w") as out, (open(rev_path, "w") if rev else open(os.devnull, "w")) as out_rev, \
-            (open(spread_path, "w") if with_spread else contextlib.nullcontext()) as spread:
+            (open(spread_path, "w") if with_spread else contextlib.nullcontext()) as spread, \
+            (open(seam_path, "w") if with_seam else contextlib.nullcontext()) as seam:
         out.write(cols + "\n")
         out_rev.write(cols + "\n")
         if with_spread:
             spread.write("field,mean_spread\n")
+        if with_seam:
+            seam.write("field,mean_seam\n")
         if cfg.eval.on and torch.device(dev).type == "cuda":
-            _device_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread)
+            _device_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread, seam)
         else:
-            _host_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread)
+            _host_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread, seam)
     with open("./test_output/averages.csv", "a") as f:
         f.write(cfg.name + "," + ",".join(str(avg[k]) for k in METRIC_NAMES) + "\n")
     for k in METRIC_NAMES:

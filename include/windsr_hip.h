@@ -585,6 +585,31 @@ int wsr_dihedral_members(const float* src, int32_t B, int32_t C, int32_t X, int3
 int wsr_ensemble_reduce(const float* members, const int32_t* codes, int32_t K, int32_t B, int32_t X, int32_t Y,
                         int32_t NZ, float* mean, float* var, void* stream);
 
+/* ---- tiled whole-domain inference ([TILE]; csrc/tiling.hip) --------------------------------------------
+ * Overlapping (x, y) tiles of fp32 planar tensors (B, C, X, Y, NZ) and the blend of per-tile results back into one
+ * field; z is never tiled.  Origin lists are HOST arrays.
+ *
+ * wsr_tile_gather: dst (n, B, C, tx, ty, NZ) = the n tiles src[:, :, x0[k]:x0[k]+tx, y0[k]:y0[k]+ty, :], a pure copy,
+ * in one launch (per 256 tiles).  WSR_EINVAL, and nothing is written, if any tile leaves the domain.
+ *
+ * wsr_tile_stitch: tiles (nx * ny, B, C, Tx, Ty, NZ), tile ix * ny + iy at origin (xs[ix], ys[iy]) of out
+ * (B, C, X, Y, NZ); every size in voxels of out.  On one axis, for a tile at origin a of side T on an axis of length N
+ * with ramp R, the weight at p = i - a is w(p) = min(L(p), Rr(p)), L(p) = R + 1 if a == 0 else min(p + 1, R + 1),
+ * Rr(p) = R + 1 if a + T == N else min(T - p, R + 1): integers >= 1 inside the tile, no ramp at a domain border.
+ * The share of tile (ix, iy) at (i, j) is alpha = (wx / Wx(i)) * (wy / Wy(j)), Wx the sum of wx over the tiles of the
+ * x axis that cover i; out = sum alpha x_T in tile order, seam (same shape, or NULL) = sum alpha (x_T - out)^2.
+ * Where one tile covers a voxel alpha is 1.0f: its value comes back bit for bit and seam is exactly 0.  Every output
+ * voxel gathers its tiles and is written once: no atomics, no zero fill, the same bits on every call and with or
+ * without seam.  Each origin list must start at 0, increase strictly, leave no gap wider than the tile and end at
+ * N - T; 0 <= R <= 32768 (WSR_EINVAL otherwise, nothing is written).  The origins travel by value: more than
+ * WSR_TILE_MAX_PER_AXIS of an axis, X or Y > 32768 or X * Y * NZ >= 2^31 return WSR_EUNSUPPORTED.                 */
+#define WSR_TILE_MAX_PER_AXIS 128
+int wsr_tile_gather(const float* src, int32_t B, int32_t C, int32_t X, int32_t Y, int32_t NZ, const int32_t* x0,
+                    const int32_t* y0, int32_t n, int32_t tx, int32_t ty, float* dst, void* stream);
+int wsr_tile_stitch(const float* tiles, const int32_t* xs, int32_t nx, const int32_t* ys, int32_t ny, int32_t B,
+                    int32_t C, int32_t X, int32_t Y, int32_t NZ, int32_t Tx, int32_t Ty, int32_t Rx, int32_t Ry,
+                    float* out, float* seam, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

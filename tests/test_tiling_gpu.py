@@ -1,0 +1,625 @@
+"""[TILE] on the GPU: the two kernels of csrc/tiling.hip against torch slicing and the float64 blend of
+tests/test_tiling.py, their assembly in ``tiling.tiled_forward``, ``wind_field_GAN_3D.G_tiled`` against one generator
+call per tile, both loops of test.py, and ``run.py --train --test`` without the section, with tiles smaller than the
+domain and with one tile over the whole domain.  Outputs of the kernels go in ``Guarded`` buffers.
+
+Bounds (kernel_bounds.py's convention, LAMBDA = 16 untouched), per element, ``n_cov`` the number of tiles over the voxel.
+
+* ``wsr_tile_gather``: ``torch.equal`` and equal int32 bit patterns with torch slicing - a pure copy.
+* ``wsr_tile_stitch``, blend: ``LAMBDA * (n_cov + 3) * 2^-24 * sum alpha |x_T| + 2^-100`` against float64: n_cov
+  products and their sum, the two share quotients and their product.
+* ``wsr_tile_stitch``, seam: ``LAMBDA * (n_cov + 5) * 2^-24 * sum alpha (|x_T| + |out|)^2 + 2^-100``.
+  The tiles are independent random fields, and tiles cut from one field plus noise of relative size 1e-3 (the
+  cancellation in x_T - out).
+* where one tile covers a voxel: that tile's value under ``torch.equal`` and a seam of exactly 0.
+* generator: rel-L2 <= 2e-5 (the fp32 output tolerance) against one ``gan.G`` call per tile on torch-sliced
+  inputs and the float64 blend: another batch size may take other conv tile shapes, so this one is not bit-equality.
+
+Refused origin lists return WSR_EINVAL (-1) with nothing written; a valid list with more origins than
+WSR_TILE_MAX_PER_AXIS returns WSR_EUNSUPPORTED (-2), the code the header states for it, with nothing written either.
+
+Measured on an MI355X when the kernels were written: worst |err| / bound 0.034 for the blend and 0.031 for the seam (both
+at 40 x 40 x 8 / 24 x 20 x 6 with independent random tiles; 0.007 for the seam of one field's tiles plus 1e-3 noise).  The
+same formula evaluated in fp32 on the CPU gives the same ratios to the printed digits, far below half a bound.
+``G_tiled`` against one call per tile: rel-L2 3.7e-8, the same with ``members = 4``.  The whole file ran in 10.3 s, 8.1 s of
+it the end-to-end test.
+"""
+import csv
+import ctypes
+import math
+import os
+import pickle
+import time
+
+import numpy as np
+import pytest
+import torch
+
+from kernel_bounds import LAMBDA, TINY, U_FP32, Guarded, assert_guards_intact, assert_within
+from test_tiling import cut_tiles, ref_stitch, shares
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda")
+T0 = time.time()
+
+
+def _carr(vals):
+    return (ctypes.c_int32 * len(vals))(*vals)
+
+
+def _field(shape, seed):
+    return torch.randn(shape, generator=torch.Generator().manual_seed(seed))
+
+
+def _starts(N, tile, overlap):
+    from gan_sr_wind_field_amd.tiling import tile_starts
+
+    return tile_starts(N, tile, overlap)
+
+
+def _bits(t):
+    return t.contiguous().view(torch.int32)
+
+
+# ---------------------------------------------------------------------------------------------------- wsr_tile_gather
+# (B, C, X, Y, NZ), tile, overlap: NZ 5 / 6 / 8 -> pieces of 1 / 2 / 4 floats; C = 1: the terrain; 24 x 24 x 8 at tile 8:
+# a tile plane of 128 pieces - with B * C = 9 planes per tile; 13 x 6 at tile 8: the y axis one tile shorter than `tile`
+GATHER_CASES = [((1, 4, 7, 9, 5), 4, 1), ((2, 1, 16, 12, 6), 8, 2), ((3, 3, 24, 24, 8), 8, 4), ((1, 4, 13, 6, 5), 8, 4),
+                ((1, 2, 40, 36, 8), 32, 4)]  # (the last: 32 x 32 x 8 / 4 = 2048 pieces, more than one workgroup moves)
+
+
+@pytest.mark.parametrize("shape,tile,overlap", GATHER_CASES, ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else str(v))
+def test_gather_equals_torch_slicing(hip, shape, tile, overlap):
+    from gan_sr_wind_field_amd import hip_ops
+    from gan_sr_wind_field_amd._lib import check
+
+    B, C, X, Y, NZ = shape
+    tx, ty = min(tile, X), min(tile, Y)
+    origins = [(a, b) for a in _starts(X, tile, overlap) for b in _starts(Y, tile, overlap)]
+    x0, y0 = [a for a, _ in origins], [b for _, b in origins]
+    src = _field(shape, 11 + NZ + X)
+    src[0, 0, 0, 0, 0] = -0.0
+    src_d = src.to(DEV)
+    out = Guarded((len(origins), B, C, tx, ty, NZ), torch.float32, DEV)
+    check(hip.wsr_tile_gather(hip_ops._p(src_d), B, C, X, Y, NZ, _carr(x0), _carr(y0), len(origins), tx, ty,
+                              hip_ops._p(out.t), hip_ops._stream()))
+    torch.cuda.synchronize()
+    assert_guards_intact(out, label=f"tile_gather {shape} {tile}")
+    got = out.t.cpu()
+    for k, (a, b) in enumerate(origins):
+        want = src[:, :, a:a + tx, b:b + ty].contiguous()
+        assert torch.equal(got[k], want), (shape, k, a, b)
+        assert _bits(got[k]).equal(_bits(want)), (shape, k, "sign of zero / bits")
+    assert _bits(hip_ops.tile_gather(src_d, x0, y0, tx, ty)).equal(_bits(out.t))  # the wrapper: same launch
+
+
+def test_gather_refuses_a_tile_that_leaves_the_domain(hip):
+    from gan_sr_wind_field_amd import hip_ops
+
+    B, C, X, Y, NZ, tx, ty = 2, 3, 12, 10, 6, 8, 8
+    src_d = _field((B, C, X, Y, NZ), 3).to(DEV)
+    for x0, y0 in (([0, 5], [0, 0]), ([0, 4], [0, 3]), ([-1, 0], [0, 0]), ([0, 0], [0, -2]), ([0, 12], [0, 0])):
+        out = Guarded((2, B, C, tx, ty, NZ), torch.float32, DEV)
+        before = out.base.view(torch.int32).clone()
+        rc = hip.wsr_tile_gather(hip_ops._p(src_d), B, C, X, Y, NZ, _carr(x0), _carr(y0), 2, tx, ty, hip_ops._p(out.t),
+                                 hip_ops._stream())
+        torch.cuda.synchronize()
+        assert rc == -1, (x0, y0, rc)  # WSR_EINVAL
+        assert torch.equal(out.base.view(torch.int32), before), (x0, y0)  # nothing written
+        with pytest.raises(ValueError, match="X = 12, Y = 10"):
+            hip_ops.tile_gather(src_d, x0, y0, tx, ty)
+    with pytest.raises(ValueError, match="tx = 13"):
+        hip_ops.tile_gather(src_d, [0], [0], 13, 8)
+    with pytest.raises(ValueError, match="2 origins in x0 for 1"):
+        hip_ops.tile_gather(src_d, [0, 1], [0], 8, 8)
+    with pytest.raises(ValueError):
+        hip_ops.tile_gather(src_d, [], [], 8, 8)
+    with pytest.raises(ValueError):
+        hip_ops.tile_gather(src_d[:, :, ::2], [0], [0], 4, 4)  # not contiguous
+    with pytest.raises(ValueError):
+        hip_ops.tile_gather(src_d.double(), [0], [0], 4, 4)
+
+
+# ---------------------------------------------------------------------------------------------------- wsr_tile_stitch
+# (B, X, Y, NZ), (Tx, Ty), (Rx, Ry); C = 3; the origins are tile_starts(N, T, R): 13 / 8 / 4 -> [0, 3, 5], triple coverage
+STITCH_CASES = [((1, 13, 8, 5), (8, 8), (4, 4)), ((2, 24, 20, 6), (8, 8), (2, 2)), ((1, 40, 40, 8), (16, 16), (8, 8)),
+                ((2, 24, 20, 6), (8, 8), (0, 0)), ((3, 8, 8, 5), (8, 8), (4, 4))]
+STITCH_IDS = ["x".join(map(str, d)) + f"-T{T[0]}-R{R[0]}" for d, T, R in STITCH_CASES]
+_REF = {}
+
+
+def _case(dims, T, R, kind):
+    """tiles (fp32, host), origins and the float64 reference of one case; computed once and shared (never modified).
+    ``kind``: "random" independent fields, "near" one field's tiles + 1e-3 noise, "same" one field's tiles"""
+    key = (dims, T, R, kind)
+    if key not in _REF:
+        B, X, Y, NZ = dims
+        xs, ys = _starts(X, T[0], R[0]), _starts(Y, T[1], R[1])
+        gen = torch.Generator().manual_seed(1000 + X + 7 * NZ + R[0])
+        n = len(xs) * len(ys)
+        F = torch.randn((B, 3, X, Y, NZ), generator=gen)
+        cut = torch.from_numpy(cut_tiles(F.numpy(), xs, ys, T[0], T[1]))
+        if kind == "random":
+            tiles = torch.randn((n, B, 3, T[0], T[1], NZ), generator=gen)
+        elif kind == "near":
+            tiles = cut + 1e-3 * torch.randn((n, B, 3, T[0], T[1], NZ), generator=gen)
+        else:
+            tiles = cut
+        tiles = tiles.contiguous()
+        ref = ref_stitch(tiles.numpy(), xs, ys, X, Y, R[0], R[1])
+        ref = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in ref.items()}
+        _REF[key] = (tiles, xs, ys, ref, F)
+    return _REF[key]
+
+
+def _stitch(hip, tiles_d, xs, ys, dims, T, R, with_seam, label):
+    """the raw entry point into Guarded buffers -> (out, seam or None) on the device, guards checked"""
+    from gan_sr_wind_field_amd import hip_ops
+    from gan_sr_wind_field_amd._lib import check
+
+    B, X, Y, NZ = dims
+    out = Guarded((B, 3, X, Y, NZ), torch.float32, DEV)
+    seam = Guarded((B, 3, X, Y, NZ), torch.float32, DEV) if with_seam else None
+    check(hip.wsr_tile_stitch(hip_ops._p(tiles_d), _carr(xs), len(xs), _carr(ys), len(ys), B, 3, X, Y, NZ, T[0], T[1],
+                              R[0], R[1], hip_ops._p(out.t), hip_ops._p(seam.t) if with_seam else None,
+                              hip_ops._stream()))
+    torch.cuda.synchronize()
+    assert_guards_intact(*([out, seam] if with_seam else [out]), label=label)
+    return out.t, (seam.t if with_seam else None)
+
+
+def _bounds(ref):
+    ncov = ref["ncov"].double()[None, None, :, :, None]
+    return (LAMBDA * (ncov + 3) * U_FP32 * ref["A_out"] + TINY, LAMBDA * (ncov + 5) * U_FP32 * ref["A_seam"] + TINY)
+
+
+@pytest.mark.parametrize("kind", ["random", "near"])
+@pytest.mark.parametrize("dims,T,R", STITCH_CASES, ids=STITCH_IDS)
+def test_stitch_blend_and_seam_within_the_bounds_of_float64(hip, dims, T, R, kind):
+    tiles, xs, ys, ref, _ = _case(dims, T, R, kind)
+    out, seam = _stitch(hip, tiles.to(DEV), xs, ys, dims, T, R, True, f"stitch {dims} {T} {R}")
+    b_out, b_seam = _bounds(ref)
+    assert_within(out, ref["out"], b_out, f"tile blend vs float64[{dims} T={T} R={R} {kind}]")
+    assert_within(seam, ref["seam"], b_seam, f"tile seam vs float64[{dims} T={T} R={R} {kind}]")
+    assert bool((seam >= 0).all())
+    # one tile over a voxel: its value, and no seam (alpha is 1 there, so the float64 blend IS the fp32 value)
+    single = (ref["ncov"] == 1)[None, None, :, :, None].expand_as(ref["out"])
+    if len(xs) * len(ys) == 1:
+        assert bool(single.all())
+    assert torch.equal(out.cpu()[single], ref["out"].float()[single]), (dims, T, R)
+    assert bool((seam.cpu()[single] == 0).all())
+    assert bool((ref["out"].float().double()[single] == ref["out"][single]).all())
+
+
+@pytest.mark.parametrize("dims,T,R", STITCH_CASES, ids=STITCH_IDS)
+def test_stitch_of_one_fields_tiles_gives_the_field_back(hip, dims, T, R):
+    tiles, xs, ys, ref, F = _case(dims, T, R, "same")
+    out, seam = _stitch(hip, tiles.to(DEV), xs, ys, dims, T, R, True, f"stitch same {dims} {T} {R}")
+    b_out, b_seam = _bounds(ref)
+    assert_within(out, F.double(), b_out, f"tile blend of one field[{dims} T={T} R={R}]")
+    assert_within(seam, torch.zeros_like(ref["seam"]), b_seam, f"tile seam of one field[{dims} T={T} R={R}]")
+    single = (ref["ncov"] == 1)[None, None, :, :, None].expand_as(F)
+    assert _bits(out.cpu()[single]).equal(_bits(F[single])), (dims, T, R)  # bit for bit
+    assert bool((seam.cpu()[single] == 0).all())
+
+
+@pytest.mark.parametrize("dims,T,R", STITCH_CASES, ids=STITCH_IDS)
+def test_stitch_is_reproducible_and_a_null_seam_leaves_the_blend(hip, dims, T, R):
+    from gan_sr_wind_field_amd import hip_ops
+
+    tiles, xs, ys, _, _ = _case(dims, T, R, "random")
+    B, X, Y, NZ = dims
+    tiles_d = tiles.to(DEV)
+    o1, s1 = _stitch(hip, tiles_d, xs, ys, dims, T, R, True, "first call")
+    o2, s2 = _stitch(hip, tiles_d, xs, ys, dims, T, R, True, "second call")
+    assert _bits(o1).equal(_bits(o2)) and _bits(s1).equal(_bits(s2))
+    o3, none = _stitch(hip, tiles_d, xs, ys, dims, T, R, False, "seam = NULL")
+    assert none is None and _bits(o3).equal(_bits(o1))
+    # the wrapper: same launches
+    assert torch.equal(hip_ops.tile_stitch(tiles_d, xs, ys, X, Y, R[0], R[1]), o1)
+    wo, ws = hip_ops.tile_stitch(tiles_d, xs, ys, X, Y, R[0], R[1], with_seam=True)
+    assert torch.equal(wo, o1) and torch.equal(ws, s1)
+
+
+def test_stitch_takes_any_covering_origin_list(hip):
+    """not only tile_starts' lists: unevenly spread origins with up to four tiles over a coordinate"""
+    dims, T, R = (1, 12, 9, 6), (6, 4), (2, 1)
+    xs, ys = [0, 1, 2, 3, 6], [0, 4, 5]
+    tiles = _field((15, 1, 3, 6, 4, 6), 77)
+    ref = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in
+           ref_stitch(tiles.numpy(), xs, ys, 12, 9, R[0], R[1]).items()}
+    assert int(ref["ncov"].max()) == 8
+    out, seam = _stitch(hip, tiles.to(DEV), xs, ys, dims, T, R, True, "uneven origins")
+    b_out, b_seam = _bounds(ref)
+    assert_within(out, ref["out"], b_out, "tile blend vs float64[uneven origins]")
+    assert_within(seam, ref["seam"], b_seam, "tile seam vs float64[uneven origins]")
+
+
+def test_stitch_refuses_bad_origin_lists(hip):
+    from gan_sr_wind_field_amd import hip_ops
+    from gan_sr_wind_field_amd.hip_ops import TILE_MAX_PER_AXIS as CAP
+
+    B, X, Y, NZ, T = 1, 24, 8, 6, 8
+    tiles_d = torch.zeros((4, B, 3, T, T, NZ), device=DEV)
+    bad = {"first origin not 0": [1, 8, 16], "last origin + T is not X": [0, 8, 15], "not increasing": [0, 8, 8, 16],
+           "decreasing": [0, 10, 8, 16], "a gap larger than T": [0, 7, 16], "past the domain": [0, 8, 16, 24]}
+    for why, xs in bad.items():
+        out, seam = (Guarded((B, 3, X, Y, NZ), torch.float32, DEV) for _ in range(2))
+        before = [g.base.view(torch.int32).clone() for g in (out, seam)]
+        for axes in ((xs, [0], X, Y), ([0], xs, Y, X)):  # the same list on either axis
+            rc = hip.wsr_tile_stitch(hip_ops._p(tiles_d), _carr(axes[0]), len(axes[0]), _carr(axes[1]), len(axes[1]), B, 3,
+                                     axes[2], axes[3], NZ, T, T, 2, 2, hip_ops._p(out.t), hip_ops._p(seam.t),
+                                     hip_ops._stream())
+            torch.cuda.synchronize()
+            assert rc == -1, (why, rc)  # WSR_EINVAL
+            assert all(torch.equal(g.base.view(torch.int32), b) for g, b in zip((out, seam), before)), why
+        with pytest.raises(ValueError, match="origins"):
+            hip_ops.tile_stitch(torch.zeros((len(xs), B, 3, T, T, NZ), device=DEV), xs, [0], X, Y, 2, 2)
+    # more tiles than the cap of an axis, the list itself in order: WSR_EUNSUPPORTED, nothing written
+    xs = list(range(CAP + 1))
+    Xc = CAP + T
+    out = Guarded((B, 3, Xc, Y, NZ), torch.float32, DEV)
+    before = out.base.view(torch.int32).clone()
+    rc = hip.wsr_tile_stitch(hip_ops._p(tiles_d), _carr(xs), len(xs), _carr([0]), 1, B, 3, Xc, Y, NZ, T, T, 2, 2,
+                             hip_ops._p(out.t), None, hip_ops._stream())
+    torch.cuda.synchronize()
+    assert rc == -2 and torch.equal(out.base.view(torch.int32), before)
+    rc = hip.wsr_tile_stitch(hip_ops._p(tiles_d), _carr(xs[:-1] + [CAP + 3]), len(xs), _carr([0]), 1, B, 3, Xc, Y, NZ, T, T,
+                             2, 2, hip_ops._p(out.t), None, hip_ops._stream())
+    assert rc == -1  # ... and out of order as well: WSR_EINVAL
+    torch.cuda.synchronize()
+    assert torch.equal(out.base.view(torch.int32), before)
+    with pytest.raises(ValueError, match=f"at most {CAP}"):
+        hip_ops.tile_stitch(torch.zeros((CAP + 1, B, 3, T, T, 1), device=DEV), xs, [0], Xc, T, 2, 2)
+    with pytest.raises(ValueError, match="3 x 1 origins for 4 tiles"):
+        hip_ops.tile_stitch(tiles_d, [0, 8, 16], [0], X, Y, 2, 2)
+    with pytest.raises(ValueError):
+        hip_ops.tile_stitch(tiles_d[:3].double(), [0, 8, 16], [0], X, Y, 2, 2)
+    with pytest.raises(ValueError):
+        hip_ops.tile_stitch(tiles_d[:3, :, :, ::2], [0, 8, 16], [0], X, Y, 2, 2)  # not contiguous
+    with pytest.raises(ValueError, match="Rx"):
+        hip_ops.tile_stitch(tiles_d[:3], [0, 8, 16], [0], X, Y, -1, 2)
+
+
+# ---------------------------------------------------------------------------------------------------------- assembly
+def _analytic(s):
+    def fn(lr, z):
+        return lr[:, :3].repeat_interleave(s, dim=2).repeat_interleave(s, dim=3) + z
+
+    return fn
+
+
+def test_tiled_forward_of_a_per_voxel_map_is_the_map_on_the_whole_domain(hip):
+    """nearest up-sampling of the first three LR channels plus the terrain is voxel-local: every tile computes the value
+    the whole domain would, so the blend is that value within the blend's bound and the seam within its bound of 0 - an
+    origin at the wrong resolution, a wrong tile order or a chunk stored in the wrong place does not"""
+    from gan_sr_wind_field_amd.tiling import tiled_forward
+
+    B, C, Xl, Yl, NZ, s, tile, overlap = 2, 4, 13, 11, 5, 4, 8, 4
+    xs, ys = _starts(Xl, tile, overlap), _starts(Yl, tile, overlap)
+    assert (xs, ys) == ([0, 3, 5], [0, 3])
+    n_tiles = len(xs) * len(ys)
+    LR, Z = _field((B, C, Xl, Yl, NZ), 5).to(DEV), _field((B, 1, Xl * s, Yl * s, NZ), 6).to(DEV)
+    want = _analytic(s)(LR, Z).double().cpu()
+    _, ncov = shares([a * s for a in xs], [b * s for b in ys], Xl * s, Yl * s, tile * s, tile * s, overlap * s, overlap * s)
+    ncov = torch.from_numpy(ncov).double()[None, None, :, :, None]
+    results = {}
+    for tpf in (1, 3, 4, n_tiles, 100):
+        calls = []
+
+        def fn(lr, z):
+            calls.append((tuple(lr.shape), tuple(z.shape)))
+            return _analytic(s)(lr, z)
+
+        SR, seam = tiled_forward(fn, LR, Z, s, tile, overlap, tpf, with_seam=True)
+        sizes = [min(tpf, n_tiles - k) for k in range(0, n_tiles, tpf)]
+        assert len(calls) == math.ceil(n_tiles / tpf)
+        assert calls == [((n * B, C, tile, tile, NZ), (n * B, 1, tile * s, tile * s, NZ)) for n in sizes], (tpf, calls)
+        assert SR.dtype == torch.float32 and tuple(SR.shape) == (B, 3, Xl * s, Yl * s, NZ)
+        results[tpf] = (SR, seam)
+        only = tiled_forward(_analytic(s), LR, Z, s, tile, overlap, tpf)
+        assert torch.is_tensor(only) and _bits(only).equal(_bits(SR))
+    SR, seam = results[1]
+    assert_within(SR, want, LAMBDA * (ncov + 3) * U_FP32 * want.abs() + TINY, "tiled_forward of a per-voxel map[blend]")
+    assert_within(seam, torch.zeros_like(want), LAMBDA * (ncov + 5) * U_FP32 * 4 * want ** 2 + TINY,
+                  "tiled_forward of a per-voxel map[seam]")
+    for tpf, (o, sm) in results.items():  # the chunking changes nothing
+        assert _bits(o).equal(_bits(SR)) and _bits(sm).equal(_bits(seam)), tpf
+    # a tuple from fn: every member stitched by the same kernel
+    (a, b), sm = tiled_forward(lambda lr, z: (_analytic(s)(lr, z), 2 * _analytic(s)(lr, z)), LR, Z, s, tile, overlap, 4,
+                               with_seam=True)
+    assert _bits(a).equal(_bits(SR)) and _bits(sm).equal(_bits(seam)) and _bits(b).equal(_bits(2 * SR))
+    # the terrain tiles are cut at HR resolution, the LR tiles at LR resolution
+    seen = {}
+
+    def spy(lr, z):
+        seen["lr"], seen["z"] = lr.cpu(), z.cpu()
+        return _analytic(s)(lr, z)
+
+    tiled_forward(spy, LR, Z, s, tile, overlap, 100)
+    for k, (a, b) in enumerate((a, b) for a in xs for b in ys):
+        assert torch.equal(seen["lr"][k * B:(k + 1) * B], LR[:, :, a:a + tile, b:b + tile].cpu()), k
+        assert torch.equal(seen["z"][k * B:(k + 1) * B], Z[:, :, a * s:(a + tile) * s, b * s:(b + tile) * s].cpu()), k
+    with pytest.raises(ValueError, match=r"\(4, 3, 8, 8, 5\).*wanted \(4, 3, 32, 32, 5\)"):
+        tiled_forward(lambda lr, z: lr[:, :3], LR, Z, s, tile, overlap, 2)
+
+
+# --------------------------------------------------------------------------------------------------------- generator
+def _reset_config():
+    from gan_sr_wind_field_amd.config.config import Config
+
+    Config(os.path.join(os.path.dirname(__import__("gan_sr_wind_field_amd").__file__), "config",
+                        "wind_field_GAN_3D_config_local.ini"))  # (the section objects are singletons: reset)
+
+
+def _inputs(B=2):
+    from oracle import gan as ogan
+
+    LR, HR, Z, _, _ = ogan.synthetic_batch(B, 12, 5, 4, seed=2001)
+    return LR[:, :, :, :10].contiguous(), HR[:, :, :, :40].contiguous(), Z[:, :, :, :40].contiguous()
+
+
+def _per_tile_reference(call, LR, Z, tile, overlap, s=4):
+    """one ``call`` per tile on torch-sliced inputs, blended in float64"""
+    xs, ys = _starts(LR.shape[2], tile, overlap), _starts(LR.shape[3], tile, overlap)
+    tx, ty = min(tile, LR.shape[2]), min(tile, LR.shape[3])
+    outs = [call(LR[:, :, a:a + tx, b:b + ty].contiguous().to(DEV),
+                 Z[:, :, a * s:(a + tx) * s, b * s:(b + ty) * s].contiguous().to(DEV)).float().cpu() for a in xs for b in ys]
+    ref = ref_stitch(torch.stack(outs).numpy(), [a * s for a in xs], [b * s for b in ys], LR.shape[2] * s, LR.shape[3] * s,
+                     overlap * s, overlap * s)
+    return torch.from_numpy(ref["out"]), torch.from_numpy(ref["seam"]), outs
+
+
+def test_G_tiled_against_one_generator_call_per_tile(hip):
+    from conftest import rel_l2
+    from test_ensemble_gpu import _gan
+
+    try:
+        gan, cfg = _gan(nz=5)
+        cfg.tile.present, cfg.tile.tile, cfg.tile.overlap, cfg.tile.tiles_per_forward = True, 8, 2, 3
+        gan.G.eval()
+        LR, _, Z = _inputs()
+        assert tuple(LR.shape) == (2, 4, 12, 10, 5) and tuple(Z.shape) == (2, 1, 48, 40, 5)
+        LR_d, Z_d = LR.to(DEV), Z.to(DEV)
+
+        def plain(lr, z):
+            with torch.no_grad():
+                return gan.G(lr, z)
+
+        want, want_seam, outs = _per_tile_reference(plain, LR, Z, 8, 2)
+        assert len(outs) == 4 and rel_l2(outs[1][:, :, :, :24], outs[0][:, :, :, 8:]) > 1e-3, "the tiles must disagree"
+        batches = []
+        hook = gan.G.register_forward_pre_hook(lambda mod, args: batches.append(args[0].shape[0]))
+        rng_cpu, rng_dev = torch.get_rng_state(), torch.cuda.get_rng_state()
+        for training in (False, True):  # (dropout probability 0: both modes compute the same)
+            gan.G.train(training)
+            SR = gan.G_tiled(LR_d, Z_d)  # everything from the config: 4 tiles -> chunks of 3 + 1
+            assert gan.G.training is training
+            assert torch.is_tensor(SR) and SR.dtype == torch.float32 and tuple(SR.shape) == (2, 3, 48, 40, 5)
+            assert not SR.requires_grad
+            err = rel_l2(SR, want)
+            print(f"[tiling] G_tiled vs one call per tile (training={training}): rel-L2 {err:.3g}")
+            assert err <= 2e-5, err
+        gan.G.eval()
+        hook.remove()
+        assert batches == [6, 2, 6, 2], batches
+        assert torch.equal(torch.get_rng_state(), rng_cpu) and torch.equal(torch.cuda.get_rng_state(), rng_dev)
+        SR2, seam = gan.G_tiled(LR_d, Z_d, tile=8, overlap=2, tiles_per_forward=3, with_seam=True)
+        assert torch.equal(SR2, SR) and tuple(seam.shape) == tuple(SR.shape)
+        assert bool((seam >= 0).all()) and float(seam.max()) > 0
+        # sqrt(seam) is, per voxel, a weighted 2-norm (weights alpha, sum 1) of the tiles' distances from their blend:
+        # 1-Lipschitz in them, and they move by at most twice what a tile's output moves (eps = 2e-5 of its norm)
+        tiles_norm = math.sqrt(sum(float(o.double().norm()) ** 2 for o in outs))
+        d_seam = float((torch.sqrt(seam.double().cpu()) - torch.sqrt(want_seam)).norm())
+        print(f"[tiling] sqrt(seam) vs float64 blend of separate calls: {d_seam:.3g}, allowed {2 * 2e-5 * tiles_norm:.3g}")
+        assert d_seam <= 2 * 2e-5 * tiles_norm
+        assert rel_l2(gan.G_tiled(LR_d, Z_d, overlap=0), _per_tile_reference(plain, LR, Z, 8, 0)[0]) <= 2e-5  # an argument overrides
+
+        # members = 4: every chunk through the self-ensemble, against G_ensemble per tile
+        want4, _, _ = _per_tile_reference(lambda lr, z: gan.G_ensemble(lr, z, members=4), LR, Z, 8, 2)
+        SR4 = gan.G_tiled(LR_d, Z_d, members=4)
+        err = rel_l2(SR4, want4)
+        print(f"[tiling] G_tiled(members=4) vs G_ensemble per tile: rel-L2 {err:.3g}")
+        assert err <= 2e-5 and rel_l2(SR4, SR) > 1e-3
+        SR4b, var4, seam4 = gan.G_tiled(LR_d, Z_d, members=4, with_var=True, with_seam=True)
+        assert torch.equal(SR4b, SR4) and tuple(var4.shape) == tuple(seam4.shape) == tuple(SR4.shape)
+        assert bool((var4 >= 0).all()) and float(var4.max()) > 0 and bool(torch.isfinite(var4).all())
+        # a blend of per-tile variances: sqrt of it is a weighted 2-norm over tiles and members of their deviations,
+        # 1-Lipschitz as above; sum_k ||m_k||^2 = K (||mean||^2 + ||sd||^2) per tile
+        wantv, _, vars4 = _per_tile_reference(lambda lr, z: gan.G_ensemble(lr, z, members=4, with_var=True)[1], LR, Z, 8, 2)
+        _, _, means4 = _per_tile_reference(lambda lr, z: gan.G_ensemble(lr, z, members=4), LR, Z, 8, 2)
+        members_norm = math.sqrt(4 * sum(float(m.double().norm()) ** 2 + float(v.double().sum()) for m, v in zip(means4, vars4)))
+        assert float((torch.sqrt(var4.double().cpu()) - torch.sqrt(wantv)).norm()) <= 2 * 2e-5 * members_norm
+        with pytest.raises(ValueError, match="square tiles, not 8 x 6"):
+            gan.G_tiled(LR_d[:, :, :, :6].contiguous(), Z_d[:, :, :, :24].contiguous(), members=8)
+
+        # tile >= domain: the same batch and the same launches, and the stitch copies
+        with torch.no_grad():
+            whole = gan.G(LR_d, Z_d).float()
+        one = gan.G_tiled(LR_d, Z_d, tile=12, overlap=6)
+        assert _bits(one).equal(_bits(whole))
+        one, seam1 = gan.G_tiled(LR_d, Z_d, tile=64, overlap=0, with_seam=True)
+        assert _bits(one).equal(_bits(whole)) and bool((seam1 == 0).all())
+        assert rel_l2(SR, whole) > 1e-4  # (tiles are not the whole-domain forward)
+
+        # inside ema_scope(): the averaged weights
+        gan.init_ema()
+        with torch.no_grad():
+            for e in gan.ema_shadows:
+                e.mul_(0.5)
+        with gan.ema_scope():
+            with torch.no_grad():
+                whole_ema = gan.G(LR_d, Z_d).float()
+            assert _bits(gan.G_tiled(LR_d, Z_d, tile=64)).equal(_bits(whole_ema))
+            SR_ema = gan.G_tiled(LR_d, Z_d)
+        assert rel_l2(SR_ema, SR) > 1e-3
+        assert _bits(gan.G_tiled(LR_d, Z_d)).equal(_bits(SR))  # ... and the generator's own again
+    finally:
+        _reset_config()
+
+
+# ----------------------------------------------------------------------------------------------- test.py, both loops
+def test_host_and_device_loops_take_sr_from_g_tiled(hip, tmp_path):
+    """the loop of ``[EVAL] device_metrics`` (batches of two fields) and the host loop (one field at a time), both with
+    ``[TILE] tile = 8, overlap = 2, write_seam = True``: every SR comes from ``G_tiled`` (a counting wrapper), SR and seam
+    are the tiled ones in both"""
+    import io
+
+    from conftest import rel_l2
+    from gan_sr_wind_field_amd import test as tmod
+    from test_ensemble_gpu import _gan
+
+    try:
+        gan, cfg = _gan(nz=5)
+        t = cfg.tile
+        t.present, t.tile, t.overlap, t.tiles_per_forward, t.write_seam = True, 8, 2, 3, True
+        cfg.training.log_period = 1
+        gan.G.eval()
+        n, uvw = 4, 30.0
+        LR, HR, Z = _inputs(n)
+        empty = torch.zeros(0)
+        fields = [(LR[i], HR[i], Z[i], f"f{i}", empty, empty) for i in range(n)]
+        sumsq = []  # per field: the sum over its tiles of ||x_T||^2
+        hook = gan.G.register_forward_hook(lambda mod, args, out: sumsq.append(float(out.double().norm()) ** 2))
+        want = []
+        for i in range(n):
+            at = len(sumsq)
+            want.append(gan.G_tiled(LR[i:i + 1].to(DEV), Z[i:i + 1].to(DEV), with_seam=True))
+            sumsq[at:] = [sum(sumsq[at:])]
+        hook.remove()
+        assert len(sumsq) == n
+        counted = {"n": 0}
+        orig = gan.G_tiled
+
+        def counting(*a, **kw):
+            counted["n"] += 1
+            return orig(*a, **kw)
+
+        gan.G_tiled = counting
+        for name, loop, bs in (("host", tmod._host_loop, 1), ("device", tmod._device_loop, 2)):
+            cfg.env.this_runs_folder = str(tmp_path / name)
+            cfg.eval.present, cfg.eval.device_metrics, cfg.eval.batch_size = name == "device", True, bs
+            loader = torch.utils.data.DataLoader(fields, batch_size=bs, shuffle=False)
+            out, seam = io.StringIO(), io.StringIO()
+            avg, avg_rev = ({k: 0.0 for k in tmod.METRIC_NAMES} for _ in range(2))
+            counted["n"] = 0
+            with open(os.devnull, "w") as out_rev:
+                loop(cfg, gan, loader, False, uvw, n, out, out_rev, avg, avg_rev, None, seam)
+            assert counted["n"] == n // bs, (name, counted)
+            rows = [r.split(",") for r in seam.getvalue().strip().splitlines()]
+            assert [r[0] for r in rows] == [f"f{i}" for i in range(n)] == [r.split(",")[0] for r in out.getvalue().strip().splitlines()]
+            for i in range(n):
+                p = pickle.load(open(os.path.join(cfg.env.this_runs_folder, "fields", f"test_fields_f{i}.pkl"), "rb"))
+                SR_i, seam_i = want[i]
+                assert p["SR"].shape == p["SR_seam"].shape == (3, 48, 40, 5) and "SR_spread" not in p
+                assert rel_l2(torch.from_numpy(p["SR"]), SR_i[0]) <= 2e-5, (name, i)
+                # the CSV value is uvw times the mean over V voxels of the length of sqrt(seam), which is 1-Lipschitz in
+                # the tiles' distances from their blend; those move by at most 2 eps ||x_T|| (eps = 2e-5, another batch
+                # size may take other conv tiles): |d value| <= uvw 2 eps sqrt(sum ||x_T||^2) / sqrt(V), + the fp32 mean
+                mean_seam = float(torch.sqrt(seam_i.double().sum(dim=1)).mean()) * uvw
+                allowed = uvw * 2 * 2e-5 * math.sqrt(sumsq[i]) / math.sqrt(48 * 40 * 5) + 2.0 ** -20 * mean_seam
+                assert mean_seam > 0 and abs(float(rows[i][1]) - mean_seam) <= allowed, (name, i, rows[i][1], mean_seam)
+                if name == "host":  # one field per forward there too: the very bits of G_tiled
+                    assert np.array_equal(p["SR"], SR_i[0].cpu().numpy())
+                    assert np.array_equal(p["SR_seam"], torch.sqrt(seam_i[0]).cpu().numpy())
+    finally:
+        _reset_config()
+
+
+# ------------------------------------------------------------------------------------------------------------ run.py
+def _rows(name, suffix="metrics"):
+    with open(os.path.join("test_output", f"{name}____{suffix}.csv")) as f:
+        return list(csv.reader(f))
+
+
+def test_run_train_and_test_without_with_tiles_and_with_one_tile(hip, tmp_path, monkeypatch):
+    from test_hip_train_e2e import _write_ini
+
+    from gan_sr_wind_field_amd import hip_ops
+    from gan_sr_wind_field_amd import process_data as pd
+    from gan_sr_wind_field_amd import run as runmod
+    from gan_sr_wind_field_amd.GAN_models import wind_field_GAN_3D as gmod
+    from gan_sr_wind_field_amd.test import METRIC_NAMES
+
+    monkeypatch.chdir(tmp_path)
+    monkeypatch.setattr(pd, "DATA_ROOT", str(tmp_path / "data"))
+    calls = {"tile_gather": 0, "tile_stitch": 0, "G_tiled": 0}
+
+    def counted(owner, name):
+        orig = getattr(owner, name)
+
+        def f(*a, **kw):
+            calls[name] += 1
+            return orig(*a, **kw)
+        return f
+
+    for owner, name in ((hip_ops, "tile_gather"), (hip_ops, "tile_stitch"), (gmod.wind_field_GAN_3D, "G_tiled")):
+        monkeypatch.setattr(owner, name, counted(owner, name))
+
+    def run(name, section):
+        ini = str(tmp_path / f"{name}.ini")
+        cfg = _write_ini(ini)
+        cfg.name = name
+        with open(ini, "w") as f:
+            f.write(cfg.asINI() + section)
+        runmod.main(["--train", "--test", "--cfg", ini])
+        return os.path.join(str(tmp_path), "runs", name)
+
+    dir_a = run("plain", "")
+    assert calls == {"tile_gather": 0, "tile_stitch": 0, "G_tiled": 0}  # the section absent: no new launch
+    assert not os.path.exists(os.path.join("test_output", "plain____tile_seam.csv"))
+    # the test domain is 32 x 32 LR voxels: 3 x 3 tiles of 16, chunks of 4 + 4 + 1
+    dir_b = run("tiled", "\n[TILE]\ntile = 16\noverlap = 4\ntiles_per_forward = 4\nwrite_seam = True\n")
+    rows_a, rows_b = _rows("plain"), _rows("tiled")
+    n_test = len(rows_a) - 1
+    assert n_test > 0 and calls == {"tile_gather": 6 * n_test, "tile_stitch": n_test, "G_tiled": n_test}, calls
+    dir_c = run("one_tile", "\n[TILE]\ntile = 32\noverlap = 8\n")
+    assert calls == {"tile_gather": 8 * n_test, "tile_stitch": 2 * n_test, "G_tiled": 2 * n_test}, calls
+    with open(os.path.join(dir_b, "config.ini")) as f:
+        assert f.read().endswith("\n[TILE]\ntile = 16\noverlap = 4\ntiles_per_forward = 4\nwrite_seam = True\n")
+
+    # the section touches nothing in training: the same weights, bit for bit
+    ga, gb, gc = (torch.load(os.path.join(d, "G_6.pth"), map_location="cpu") for d in (dir_a, dir_b, dir_c))
+    assert list(ga) == list(gb) == list(gc) and all(torch.equal(ga[k], gb[k]) and torch.equal(ga[k], gc[k]) for k in ga)
+
+    # tiles: same header, names and row order in every run, other values where SR enters, finite
+    rows_c = _rows("one_tile")
+    for rows in (rows_b, rows_c):
+        assert rows[0] == rows_a[0] == ["field"] + list(METRIC_NAMES)
+        assert [r[0] for r in rows] == [r[0] for r in rows_a]
+    assert all(ra[1:] != rb[1:] for ra, rb in zip(rows_a[1:], rows_b[1:]))
+    for k in ("PSNR_trilinear", "trilinear_pix", "average_wind_speed"):  # nothing that does not involve SR moved
+        i = 1 + METRIC_NAMES.index(k)
+        assert [r[i] for r in rows_a] == [r[i] for r in rows_b], k
+    assert all(math.isfinite(float(v)) for r in rows_b[1:] for v in r[1:])
+    seam = _rows("tiled", "tile_seam")
+    assert seam[0] == ["field", "mean_seam"] and [r[0] for r in seam[1:]] == [r[0] for r in rows_a[1:]]
+    vals = [float(r[1]) for r in seam[1:]]
+    assert all(len(r) == 2 for r in seam) and all(math.isfinite(v) and v >= 0 for v in vals) and max(vals) > 0
+    fields = sorted(f for f in os.listdir(os.path.join(dir_b, "fields")) if f.startswith("test_fields_"))
+    assert fields and fields == sorted(f for f in os.listdir(os.path.join(dir_a, "fields")) if f.startswith("test_fields_"))
+    _, te, _, _, _ = runmod.prepare_data(_write_ini(str(tmp_path / "again.ini")))
+    uvw = float(te.UVW_MAX)
+    by_name = dict((r[0], float(r[1])) for r in seam[1:])
+    for f in fields:
+        pa, pb = (pickle.load(open(os.path.join(d, "fields", f), "rb")) for d in (dir_a, dir_b))
+        assert set(pb) == set(pa) | {"SR_seam"}
+        assert pb["SR_seam"].shape == pb["SR"].shape == pa["SR"].shape and pb["SR_seam"].dtype == np.float32
+        assert np.isfinite(pb["SR_seam"]).all() and (pb["SR_seam"] >= 0).all() and pb["SR_seam"].max() > 0
+        assert (pb["SR_seam"][:, :32, :32] == 0).all()  # (origins 0, 8, 16: the first 8 LR voxels are the first tile's alone)
+        for k in ("HR", "LR", "TL", "Z"):
+            assert np.array_equal(pa[k], pb[k]), k
+        assert not np.array_equal(pa["SR"], pb["SR"])
+        # the CSV value is the mean over voxels of the pickled seam's length, in m/s
+        want = float(np.sqrt((pb["SR_seam"].astype(np.float64) ** 2).sum(0)).mean()) * uvw
+        assert by_name[f[len("test_fields_"):-4]] == pytest.approx(want, rel=1e-4)
+
+    # one tile over the whole domain: the plain run's file, character for character; no seam file
+    with open(os.path.join("test_output", "plain____metrics.csv")) as fa, \
+            open(os.path.join("test_output", "one_tile____metrics.csv")) as fc:
+        assert fa.read() == fc.read()
+    assert not os.path.exists(os.path.join("test_output", "one_tile____tile_seam.csv"))
+    for f in fields:
+        pa, pc = (pickle.load(open(os.path.join(d, "fields", f), "rb")) for d in (dir_a, dir_c))
+        assert set(pa) == set(pc) and all(np.array_equal(pa[k], pc[k]) for k in pa)
+    print(f"[time] tests/test_tiling_gpu.py up to here: {time.time() - T0:.1f} s")
