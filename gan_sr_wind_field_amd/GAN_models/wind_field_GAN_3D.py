@@ -671,6 +671,28 @@ class wind_field_GAN_3D(BaseGAN):
         out = (tuple(SR) if with_var else (SR,)) + ((seam,) if with_seam else ())
         return out[0] if len(out) == 1 else out
 
+    # ------------------------------------------------------------------ per-level diagnostics ([DIAGNOSTICS])
+    def level_diagnostics(self, HR, SR, LR, Z):
+        """The fifteen per-level sums of ``diagnostics.SUM_NAMES`` of a batch -> float64 (B, NZ, 15) on the tensors'
+        device: the trilinear baseline of ``LR`` is built here (``wsr_trilinear_xy`` on a GPU, ``F.interpolate`` on a
+        CPU), the sums come from ``hip_ops.level_diagnostics`` on a GPU and from ``diagnostics.level_sums_reference`` on
+        a CPU.  ``Z`` is the raw altitude (B, 1, X, Y, NZ); the coordinates are those of ``feed_xy_niter``."""
+        from ..diagnostics import level_sums_reference
+
+        x, y = getattr(self, "x", None), getattr(self, "y", None)
+        if x is None or y is None:
+            raise ValueError("level_diagnostics needs the grid coordinates: call feed_xy_niter(x, y, ...) first")
+        if not HR.is_cuda:
+            return level_sums_reference(HR, SR.detach(), _trilinear(LR, self.cfg.scale), x.to(HR.device),
+                                        y.to(HR.device), Z)
+        from .. import hip_ops
+
+        def f(t):
+            return t.detach().float().contiguous()
+
+        TL = hip_ops.trilinear_xy(f(LR), self.cfg.scale)
+        return hip_ops.level_diagnostics(f(HR), f(SR), TL, f(x.to(HR.device)), f(y.to(HR.device)), f(Z))
+
     def make_new_labels(self, it):
         """Real / fake label vectors of this iteration (reference :627-678)."""
         t = self.cfg.training

@@ -26,6 +26,7 @@ EXPORTS = [
     "wsr_trilinear_xy", "wsr_field_metrics", "wsr_column_interp",
     "wsr_dihedral_members", "wsr_ensemble_reduce",
     "wsr_tile_gather", "wsr_tile_stitch",
+    "wsr_level_diagnostics_workspace_floats", "wsr_level_diagnostics",
 ]
 
 
@@ -155,6 +156,7 @@ def lib() -> C.CDLL:
                             vp],   # additive export
         "wsr_tile_stitch": [vp, C.POINTER(C.c_int32), i32, C.POINTER(C.c_int32), i32, i32, i32, i32, i32, i32, i32, i32,
                             i32, i32, vp, vp, vp],   # additive export
+        "wsr_level_diagnostics": [vp, i32, vp, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp],   # additive export
     }
     for name, argtypes in sig.items():
         fn = getattr(L, name)
@@ -164,6 +166,8 @@ def lib() -> C.CDLL:
     L.wsr_frag_filter_elems.restype = C.c_int64
     L.wsr_physics_loss_workspace_floats.argtypes = []
     L.wsr_physics_loss_workspace_floats.restype = C.c_int64
+    L.wsr_level_diagnostics_workspace_floats.argtypes = [i32, i32, i32, i32]
+    L.wsr_level_diagnostics_workspace_floats.restype = C.c_int64
     if L.wsr_abi_version() != 9:
         raise RuntimeError("libwindsr_hip.so ABI version mismatch")
     _lib = L

@@ -26,6 +26,10 @@ Extension (optional keys, defaults keep reference behaviour):
             --test runs the generator on overlapping tiles of ``tile`` LR voxels in x and y and blends the outputs
             (tiling.py, csrc/tiling.hip): the whole domain at the geometry of training, memory following
             tiles_per_forward instead of the domain; can write how far the tiles disagree in their overlaps
+  [DIAGNOSTICS] level_profile / per_field
+            --test also writes, per z level, wind speed, error-vector length, speed bias, direction error and the rms
+            divergence of truth, network and baseline (diagnostics.py, csrc/diagnostics.hip), for the whole test set
+            and per field
 """
 from __future__ import annotations
 
@@ -462,6 +466,43 @@ class TileConfig(IniConfig):
         return "[TILE]\n" + "".join(f"{k} = {getattr(self, k)}\n" for k, _ in self._schema)
 
 
+class DiagnosticsConfig(IniConfig):
+    """[DIAGNOSTICS] (extension): per-level evaluation diagnostics of ``run.py --test`` (diagnostics.py,
+    csrc/diagnostics.hip); absent section = off, and not printed by ``asINI``.  ``level_profile``: ``--test`` also writes
+    ``<name>____level_profile.csv``, one row per z level; ``per_field``: ... and ``<name>____level_profile_fields.csv``,
+    one row per field and level."""
+
+    present: bool = False
+    level_profile: bool = True
+    per_field: bool = False
+    _schema = (("level_profile", _B), ("per_field", _B))
+
+    def setDiagnosticsConfig(self, section):
+        """``section`` None (no [DIAGNOSTICS] in the file) restores the defaults and switches the section off."""
+        self.present = section is not None
+        for key, kind in self._schema:
+            try:
+                val = None if section is None else _read(section, key, kind)
+            except ValueError:
+                raise ValueError(f"[DIAGNOSTICS] {key} must be True or False, not {section.get(key)!r}") from None
+            setattr(self, key, getattr(DiagnosticsConfig, key) if val is None else val)
+
+    def validate(self) -> None:
+        if not self.present:
+            return
+        if self.per_field and not self.level_profile:
+            raise ValueError("[DIAGNOSTICS] per_field = True needs level_profile = True: the per-field rows are the "
+                             "terms of the level profile")
+
+    @property
+    def on(self) -> bool:
+        """``--test`` takes the per-level sums and writes the profile"""
+        return bool(self.present and self.level_profile)
+
+    def __str__(self) -> str:
+        return "[DIAGNOSTICS]\n" + "".join(f"{k} = {getattr(self, k)}\n" for k, _ in self._schema)
+
+
 class Config(IniConfig):
     name: str = "default_name"
     model: str = "default_model"
@@ -489,6 +530,7 @@ class Config(IniConfig):
     eval: EvalConfig = EvalConfig()
     ensemble: EnsembleConfig = EnsembleConfig()
     tile: TileConfig = TileConfig()
+    diagnostics: DiagnosticsConfig = DiagnosticsConfig()
     compute_dtype: str = "fp32"
     is_train: bool
     is_use: bool
@@ -525,6 +567,8 @@ class Config(IniConfig):
         self.ensemble.validate()
         self.tile.setTileConfig(parser["TILE"] if parser.has_section("TILE") else None)
         self.tile.validate()
+        self.diagnostics.setDiagnosticsConfig(parser["DIAGNOSTICS"] if parser.has_section("DIAGNOSTICS") else None)
+        self.diagnostics.validate()
 
     def setBaseConfig(self, base):
         self.name = base.get("name")
@@ -562,4 +606,6 @@ class Config(IniConfig):
             out += "\n" + str(self.ensemble)
         if getattr(self.tile, "present", False):
             out += "\n" + str(self.tile)
+        if getattr(self.diagnostics, "present", False):
+            out += "\n" + str(self.diagnostics)
         return out

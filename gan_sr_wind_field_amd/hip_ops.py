@@ -1245,3 +1245,48 @@ def tile_stitch(tiles: Tensor, xs, ys, X: int, Y: int, Rx: int, Ry: int, with_se
     check(_lib.lib().wsr_tile_stitch(_p(tiles), ax, len(xl), ay, len(yl), B, Cn, X, Y, NZ, Tx, Ty, Rx, Ry, _p(out),
                                      _p(seam), _stream()), "tile_stitch")
     return (out, seam) if with_seam else out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# per-level evaluation diagnostics ([DIAGNOSTICS]; csrc/diagnostics.hip)
+# ---------------------------------------------------------------------------------------------------------------------
+LEVEL_DIAG_SUMS = 15  # WSR_LEVEL_DIAG_SUMS
+LEVEL_DIAG_MAX_NZ = 256
+
+
+def level_diagnostics(HR: Tensor, SR: Tensor, TL: Tensor, x: Tensor, y: Tensor, Z: Tensor,
+                      out: Optional[Tensor] = None) -> Tensor:
+    """Fifteen sums per sample and z level over the X * Y columns of the level -> float64 (B, NZ, 15), in the order of
+    ``diagnostics.SUM_NAMES``: wind speed, error-vector lengths, signed and absolute speed errors, the speed-weighted
+    direction errors, squared divergences and altitudes of ``HR``, ``SR`` and the baseline ``TL`` (B, C >= 3, X, Y, NZ;
+    channels 0..2 are read) with the raw altitude ``Z`` (B, 1, X, Y, NZ) and the coordinates ``x`` (X), ``y`` (Y).  One
+    pass, no atomics: the same bits on every call.  ``out``: a float64 (B, NZ, 15) slice to write into
+    (``wsr_level_diagnostics``)."""
+    _need_cuda(HR, SR, TL, x, y, Z, out)
+    _planar5("level_diagnostics", "HR", HR, 3)
+    _planar5("level_diagnostics", "SR", SR, 3)
+    _planar5("level_diagnostics", "TL", TL, 3)
+    _planar5("level_diagnostics", "Z", Z)
+    B, _, X, Y, NZ = HR.shape
+    for name, t in (("SR", SR), ("TL", TL)):
+        if (t.shape[0],) + tuple(t.shape[2:]) != (B, X, Y, NZ):
+            raise ValueError(f"level_diagnostics: {name} {tuple(t.shape)} does not match HR {tuple(HR.shape)}")
+    if tuple(Z.shape) != (B, 1, X, Y, NZ):
+        raise ValueError(f"level_diagnostics wants Z ({B}, 1, {X}, {Y}, {NZ}), got {tuple(Z.shape)}")
+    for name, t, n in (("x", x, X), ("y", y, Y)):
+        if t.dtype != torch.float32 or t.dim() != 1 or t.numel() != n or not t.is_contiguous():
+            raise ValueError(f"level_diagnostics wants {name} as a contiguous fp32 ({n},) tensor, got {t.dtype} "
+                             f"{tuple(t.shape)}")
+    if NZ > LEVEL_DIAG_MAX_NZ or B > 65535 or X > 32768 or Y > 32768 or X * Y * NZ >= 2 ** 31:
+        raise ValueError(f"level_diagnostics: at most {LEVEL_DIAG_MAX_NZ} levels, 65535 samples, 32768 points in x and y "
+                         f"and 2^31 - 1 voxels per sample, not B = {B}, X = {X}, Y = {Y}, NZ = {NZ}")
+    if out is None:
+        out = torch.empty((B, NZ, LEVEL_DIAG_SUMS), dtype=torch.float64, device=HR.device)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (B, NZ, LEVEL_DIAG_SUMS) or not out.is_contiguous():
+        raise ValueError(f"level_diagnostics wants out as a contiguous float64 ({B}, {NZ}, {LEVEL_DIAG_SUMS}) tensor, got "
+                         f"{out.dtype} {tuple(out.shape)}")
+    L = _lib.lib()
+    ws = torch.empty(int(L.wsr_level_diagnostics_workspace_floats(B, X, Y, NZ)), dtype=torch.float32, device=HR.device)
+    check(L.wsr_level_diagnostics(_p(HR), HR.shape[1], _p(SR), SR.shape[1], _p(TL), TL.shape[1], _p(Z), _p(x), _p(y), B,
+                                  X, Y, NZ, _p(ws), _p(out), _stream()), "level_diagnostics")
+    return out

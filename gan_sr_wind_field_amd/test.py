@@ -31,6 +31,15 @@ variance of blended members).  ``write_seam`` adds
     ./test_output/<cfg.name>____tile_seam.csv                     one row ``field,mean_seam`` per field
 (the mean over voxels of ``sqrt(seam_u + seam_v + seam_w) * UVW_MAX``, seam the weighted squared distance of the tiles
 from their blend) and the key ``SR_seam`` (``sqrt(seam)`` per component) in the pickled fields.
+
+With a ``[DIAGNOSTICS]`` section both loops also add the fifteen per-level sums of every batch (``diagnostics.py``) into
+one (NZ, 15) table - the device loop with ONE ``hip_ops.level_diagnostics`` launch per batch on the stored baseline
+(which it then builds for every batch), its table a device tensor read once after the last batch; the host loop with
+``diagnostics.level_sums_reference`` on the host tensors - and write
+    ./test_output/<cfg.name>____level_profile.csv                 one row ``level,`` + ``PROFILE_COLUMNS`` per z level
+    ./test_output/<cfg.name>____level_profile_fields.csv          (``per_field``) one row ``field,level,...`` per field and level
+    ./test_output/<cfg.name>____level_profile_reverse_interpolate.csv   (+ ``..._fields_reverse_interpolate.csv``)
+        with ``reverse_interpolate``: the same on the raw truth, the re-levelled SR and baseline and the raw altitudes
 """
 from __future__ import annotations
 
@@ -40,10 +49,12 @@ import math
 import os
 import pickle as pkl
 
+import numpy as np
 import torch
 import torch.nn as nn
 
 from .GAN_models.wind_field_GAN_3D import calculate_PSNR, wind_field_GAN_3D
+from .diagnostics import PROFILE_COLUMNS, level_sums_reference, profile_from_sums
 from .process_data import reverse_interpolate_z_axis
 
 METRIC_NAMES = ("PSNR", "PSNR_trilinear", "relative_error", "pix", "trilinear_pix", "relative_error_trilinear",
@@ -144,7 +155,46 @@ def _mean_spread(var: torch.Tensor, uvw: float) -> torch.Tensor:
     return torch.sqrt(var.sum(dim=1)).flatten(1).mean(dim=1) * uvw
 
 
-def _host_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread=None, seam=None):
+class _LevelProfile:
+    """[DIAGNOSTICS]: the per-level sums of the whole test set, (NZ, 15) float64 on the device of the sums it is given,
+    and the two files made of them.  ``fields``: the open per-field file or None; its rows wait in ``pending`` until
+    ``flush`` (the flush points of the metrics)."""
+
+    def __init__(self, path, uvw, fields=None):
+        self.path, self.uvw, self.fields = path, uvw, fields
+        self.total, self.ncols, self.pending = None, 0, []
+        if fields is not None:
+            fields.write("field,level," + ",".join(PROFILE_COLUMNS) + "\n")
+
+    def add(self, names, sums, ncols_per_field):
+        """``sums`` (B, NZ, 15) of the fields ``names`` with ``ncols_per_field`` = X * Y columns each"""
+        t = sums.sum(dim=0)
+        self.total = t if self.total is None else self.total + t
+        self.ncols += ncols_per_field * len(names)
+        if self.fields is not None:
+            self.pending.append((list(names), sums, ncols_per_field))
+
+    def flush(self):
+        for names, sums, ncols in self.pending:
+            for name, table in zip(names, sums.cpu().tolist()):
+                _write_profile_rows(self.fields, profile_from_sums(table, ncols, self.uvw), name + ",")
+        self.pending.clear()
+
+    def close(self):
+        self.flush()
+        with open(self.path, "w") as f:
+            f.write("level," + ",".join(PROFILE_COLUMNS) + "\n")
+            if self.total is not None:
+                _write_profile_rows(f, profile_from_sums(self.total.cpu(), self.ncols, self.uvw), "")  # the ONE read
+
+
+def _write_profile_rows(f, prof, prefix):
+    for lvl in range(len(prof[PROFILE_COLUMNS[0]])):
+        f.write(f"{prefix}{lvl}," + ",".join(str(prof[k][lvl]) for k in PROFILE_COLUMNS) + "\n")
+
+
+def _host_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread=None, seam=None, diag=None,
+               diag_rev=None):
     """one field at a time; baseline, re-levelling and metrics on the host (the reference's loop)"""
     dev = cfg.device
     for j, (LR, HR, Z, names, HR_raw, Z_raw) in enumerate(loader):
@@ -165,9 +215,18 @@ def _host_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread
                 vals = write_metrics(HR_raw[i:i + 1, :3], SR_r, TL_r, names[i], out_rev, uvw)
                 for k, v in zip(METRIC_NAMES, vals):
                     avg_rev[k] += v / n
+                if diag_rev is not None:
+                    diag_rev.add(names[i:i + 1], level_sums_reference(HR_raw[i:i + 1], SR_r, TL_r, gan.x.cpu(),
+                                                                      gan.y.cpu(), Z_raw[i:i + 1]),
+                                 HR.shape[2] * HR.shape[3])
+                    diag_rev.flush()
             vals = write_metrics(HR_i, SR_i, TL_i, names[i], out, uvw)
             for k, v in zip(METRIC_NAMES, vals):
                 avg[k] += v / n
+            if diag is not None:
+                diag.add(names[i:i + 1], level_sums_reference(HR_i, SR_i, TL_i, gan.x.cpu(), gan.y.cpu(), Z[i:i + 1]),
+                         HR.shape[2] * HR.shape[3])
+                diag.flush()
             if j % cfg.training.log_period == 0:
                 write_fields(LR[i], HR[i], SR_i[0], TL[i], Z[i], cfg.env.this_runs_folder, names[i],
                              HR_raw[i] if rev else None, Z_raw[i] if rev else None, None,
@@ -175,7 +234,8 @@ def _host_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread
                              None if seam_i is None else torch.sqrt(seam_i[0]))
 
 
-def _device_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread=None, seam=None):
+def _device_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread=None, seam=None, diag=None,
+                 diag_rev=None):
     """[EVAL] device_metrics: one generator forward and one metrics launch per batch; the (B, 7) rows wait in a device
     table and are read once per ``log_period`` batches and at the end"""
     from . import hip_ops
@@ -207,6 +267,9 @@ def _device_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spre
                 for name, v in zip([nm for names, _ in rows for nm in names], vals):
                     dest.write(f"{name},{v}\n")
                 rows.clear()
+        for d in (diag, diag_rev):
+            if d is not None:
+                d.flush()
 
     for j, (LR, HR, Z, names, HR_raw, Z_raw) in enumerate(loader):
         LR_d, HR_d, Z_d = (t.to(dev, non_blocking=True).contiguous() for t in (LR, HR, Z))
@@ -219,12 +282,17 @@ def _device_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spre
         nvox = HR.shape[2] * HR.shape[3] * HR.shape[4]
         sums = hip_ops.field_metrics(HR_d, SR_d, LR=LR_d, scale=s)  # (the baseline is blended inside, never stored)
         keep = j % cfg.training.log_period == 0
-        TL_d = hip_ops.trilinear_xy(LR_d, s) if rev or keep else None
+        TL_d = hip_ops.trilinear_xy(LR_d, s) if rev or keep or diag is not None else None
+        ncols = HR.shape[2] * HR.shape[3]
+        if diag is not None:  # (the stored baseline: its divergence needs the neighbouring columns)
+            diag.add(names, hip_ops.level_diagnostics(HR_d, SR_d, TL_d, gan.x, gan.y, Z_d), ncols)
         sums_raw = None
         if rev:  # back onto the raw terrain-following levels of every column, metrics against the raw truth
             raw_d, zraw_d = (t.to(dev, non_blocking=True).contiguous() for t in (HR_raw, Z_raw))
-            sums_raw = hip_ops.field_metrics(raw_d, hip_ops.column_interp(SR_d, Z_d, zraw_d),
-                                             TL=hip_ops.column_interp(TL_d, Z_d, zraw_d))
+            SR_r, TL_r = hip_ops.column_interp(SR_d, Z_d, zraw_d), hip_ops.column_interp(TL_d, Z_d, zraw_d)
+            sums_raw = hip_ops.field_metrics(raw_d, SR_r, TL=TL_r)
+            if diag_rev is not None:
+                diag_rev.add(names, hip_ops.level_diagnostics(raw_d, SR_r, TL_r, gan.x, gan.y, zraw_d), ncols)
         # (per field: the sums in the order the rows are written - all of `out`, then all of `out_rev`, per batch)
         pending.append((list(names), nvox, sums, sums_raw))
         if keep:
@@ -276,9 +344,23 @@ def test(cfg, dataset_test, reverse_interpolate: bool = False):
     # ([TILE] write_seam on a GPU: one more CSV, the disagreement of the tiles in their overlaps per field)
     with_seam = cfg.tile.present and cfg.tile.write_seam and torch.device(dev).type == "cuda"
     seam_path = os.path.join("./test_output", cfg.name + "____tile_seam.csv")
+    # ([DIAGNOSTICS]: the per-level sums of every batch, one more CSV - two with per_field - per set of levels)
+    dg = getattr(cfg, "diagnostics", None)
+    with_diag = dg is not None and dg.on
+    if with_diag:
+        gan.x, gan.y = (torch.from_numpy(np.asarray(v)).float().contiguous().to(dev) for v in (dataset_test.x, dataset_test.y))
+
+    def profile_path(fields, suffix):
+        return os.path.join("./test_output", f"{cfg.name}____level_profile{'_fields' if fields else ''}{suffix}.csv")
+
     with open(metrics_path, "w") as out, (open(rev_path, "w") if rev else open(os.devnull, "w")) as out_rev, \
             (open(spread_path, "w") if with_spread else contextlib.nullcontext()) as spread, \
-            (open(seam_path, "w") if with_seam else contextlib.nullcontext()) as seam:
+            (open(seam_path, "w") if with_seam else contextlib.nullcontext()) as seam, \
+            (open(profile_path(True, ""), "w") if with_diag and dg.per_field else contextlib.nullcontext()) as pf, \
+            (open(profile_path(True, "_reverse_interpolate"), "w") if with_diag and dg.per_field and rev
+             else contextlib.nullcontext()) as pf_rev:
+        diag = _LevelProfile(profile_path(False, ""), uvw, pf) if with_diag else None
+        diag_rev = _LevelProfile(profile_path(False, "_reverse_interpolate"), uvw, pf_rev) if with_diag and rev else None
         out.write(cols + "\n")
         out_rev.write(cols + "\n")
         if with_spread:
@@ -286,9 +368,12 @@ def test(cfg, dataset_test, reverse_interpolate: bool = False):
         if with_seam:
             seam.write("field,mean_seam\n")
         if cfg.eval.on and torch.device(dev).type == "cuda":
-            _device_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread, seam)
+            _device_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread, seam, diag, diag_rev)
         else:
-            _host_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread, seam)
+            _host_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread, seam, diag, diag_rev)
+        for d in (diag, diag_rev):
+            if d is not None:
+                d.close()
     with open("./test_output/averages.csv", "a") as f:
         f.write(cfg.name + "," + ",".join(str(avg[k]) for k in METRIC_NAMES) + "\n")
     for k in METRIC_NAMES:

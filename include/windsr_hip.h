@@ -610,6 +610,33 @@ int wsr_tile_stitch(const float* tiles, const int32_t* xs, int32_t nx, const int
                     int32_t C, int32_t X, int32_t Y, int32_t NZ, int32_t Tx, int32_t Ty, int32_t Rx, int32_t Ry,
                     float* out, float* seam, void* stream);
 
+/* ---- per-level evaluation diagnostics ([DIAGNOSTICS]; csrc/diagnostics.hip) -----------------------------
+ * wsr_level_diagnostics: sums (B, NZ, WSR_LEVEL_DIAG_SUMS) doubles, each a sum over the X * Y columns of one z level of
+ * one sample, from one pass over channels 0..2 of hr (B, hr_c, X, Y, NZ), sr (B, sr_c, ...) and the baseline tl
+ * (B, tl_c, ...), the raw altitude zc (B, 1, X, Y, NZ) and the coordinate vectors xs (X), ys (Y); all fp32 planar:
+ *    0        ||hr||
+ *    1, 2     ||hr - sr||, ||hr - tl||
+ *    3, 4     ||sr|| - ||hr||, ||tl|| - ||hr||                      (signed speed bias)
+ *    5, 6     | ||sr|| - ||hr|| |, | ||tl|| - ||hr|| |
+ *    7        h = sqrt(hr_u^2 + hr_v^2)
+ *    8, 9     h * theta(hr, sr), h * theta(hr, tl),  theta(a, b) = atan2f(|a_u b_v - a_v b_u|, a_u b_u + a_v b_v) in
+ *             [0, pi], 0 when both arguments are 0
+ *    10..12   div(hr)^2, div(sr)^2, div(tl)^2,  div = du/dx + dv/dy + dw/dz with the stencils of wsr_wind_gradient
+ *             (three-point non-uniform inside, one-sided at the domain borders, zc of the own column for z, 0 along an
+ *             axis of length 1)
+ *    13, 14   zc, zc - zc at level 0 of the same column
+ * workspace: wsr_level_diagnostics_workspace_floats(B, X, Y, NZ) floats (0 for sizes the entry refuses): one partial
+ * row of NZ * WSR_LEVEL_DIAG_SUMS floats per workgroup, at most WSR_LEVEL_DIAG_MAX_ROWS rows per sample, added in a
+ * fixed order in double by a second kernel.  No atomics, no zero fill, evaluated without contraction: the same bits on
+ * every call.  A null pointer, a channel count < 3 or a non-positive size: WSR_EINVAL; NZ > 256, B > 65535, X or
+ * Y > 32768 or X * Y * NZ >= 2^31: WSR_EUNSUPPORTED; nothing is written in either case.                             */
+#define WSR_LEVEL_DIAG_SUMS 15
+#define WSR_LEVEL_DIAG_MAX_ROWS 1024
+int64_t wsr_level_diagnostics_workspace_floats(int32_t B, int32_t X, int32_t Y, int32_t NZ);
+int wsr_level_diagnostics(const float* hr, int32_t hr_c, const float* sr, int32_t sr_c, const float* tl, int32_t tl_c,
+                          const float* zc, const float* xs, const float* ys, int32_t B, int32_t X, int32_t Y, int32_t NZ,
+                          float* workspace, double* sums, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
