@@ -27,6 +27,7 @@ EXPORTS = [
     "wsr_dihedral_members", "wsr_ensemble_reduce",
     "wsr_tile_gather", "wsr_tile_stitch",
     "wsr_level_diagnostics_workspace_floats", "wsr_level_diagnostics",
+    "wsr_last_tile_plan",
 ]
 
 
@@ -157,6 +158,7 @@ def lib() -> C.CDLL:
         "wsr_tile_stitch": [vp, C.POINTER(C.c_int32), i32, C.POINTER(C.c_int32), i32, i32, i32, i32, i32, i32, i32, i32,
                             i32, i32, vp, vp, vp],   # additive export
         "wsr_level_diagnostics": [vp, i32, vp, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp],   # additive export
+        "wsr_last_tile_plan": [C.POINTER(C.c_int32)],   # additive export (diagnostic)
     }
     for name, argtypes in sig.items():
         fn = getattr(L, name)

@@ -354,6 +354,22 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ part, long part_s
 
 }  // namespace
 
+// ---- launch-plan witness (diagnostic) ---------------------------------------------------------
+// Plain host state, one record per thread (entry points may be called from the autograd thread and the main thread at
+// once).  launch_ct writes it just before every halo-tile launch; only wsr_last_tile_plan reads it.
+static thread_local int32_t t_last_plan[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+
+void wsr_ct_note_plan(const CtArgs& a, int ntw) {
+  const int32_t p[8] = {a.TX, a.TY, a.TZ, ntw, a.ngroups, a.ksplit, a.xbufs, a.TS};
+  for (int i = 0; i < 8; ++i) t_last_plan[i] = p[i];
+}
+
+extern "C" int wsr_last_tile_plan(int32_t* plan8) {
+  if (!plan8) return WSR_EINVAL;
+  for (int i = 0; i < 8; ++i) plan8[i] = t_last_plan[i];
+  return 0;
+}
+
 int wsr_ct_splitk_reduce(const CtArgs& a, hipStream_t st) {
   const long nvox = (long)a.B * a.Xo * a.Yo * a.Zo;
   const long total = nvox * (a.Cout >> 2);

@@ -110,6 +110,10 @@ struct CtArgs {
 // adds the ksplit partial images of a split-reduction launch in index order and applies the epilogue (conv_tile.hip)
 int wsr_ct_splitk_reduce(const CtArgs& a, hipStream_t st);
 
+// Diagnostic: records the plan of the launch that follows for wsr_last_tile_plan (conv_tile.hip: a thread-local copy of
+// eight integers).  Write-only as far as the library goes - no launch decision may read it back.
+void wsr_ct_note_plan(const CtArgs& a, int ntw);
+
 namespace {
 
 // LDS-DMA of 16 B per lane: LDS[lds_addr + 16*lane] <- *gsrc.  Issued as inline asm so that hipcc does
@@ -934,6 +938,7 @@ int launch_ct(CtArgs& a, hipStream_t st) {
       }
     }
   }
+  wsr_ct_note_plan(a, NTW);
   hipLaunchKernelGGL(kern, dim3((unsigned)(wg * a.ksplit)), dim3(WAVES * 64), lds, st, a);
   WSR_LAUNCH_CHECK();
   if (a.ksplit > 1) return wsr_ct_splitk_reduce(a, st);

@@ -9,8 +9,15 @@ static int run(CtArgs& a, hipStream_t st) {
   if (a.mask_y || a.ups) return WSR_EUNSUPPORTED;
   if constexpr (TPK == 2) {
     // the halo of a strided tile grows with the stride and the filter extent: fall back to flatter tiles
-    // until the image fits the per-wave DMA budget and LDS
-    static const int shapes[][3] = {{4, 4, 16}, {4, 8, 8}, {4, 4, 8}, {2, 4, 8}, {2, 2, 8}};
+    // until the image fits the per-wave DMA budget and LDS.
+    // With filters of <= 8 per axis and <= 125 taps (conv_geom_ok) and strides <= 2, {4,4,8} has a halo of at most
+    // 14 x 14 x 15 = 2 940 voxels (8x8x1 taps): 92 of the 104 DMA units, and 92 KB of LDS that leave >= 4 K-steps of
+    // weights at every width - launch_ct can only turn it away on its 32-bit offset test (the halo's x-planes hold
+    // >= 2^32 elements), which depends on TX alone, or on the range test of the workgroup index.  {2,4,8} halves TX for
+    // the former.  Its own halo (<= 10 x 14 x 22 = 3 080 voxels, 97 units) fits as well, so only those two tests can
+    // refuse it, and a {2,2,8} after it - the same TX, more tiles, the same channel-group width wherever the tile
+    // count matters - would fail them too: there is no fifth shape.
+    static const int shapes[][3] = {{4, 4, 16}, {4, 8, 8}, {4, 4, 8}, {2, 4, 8}};
     for (const auto& sh : shapes) {
       a.TX = sh[0]; a.TY = sh[1]; a.TZ = sh[2] < a.Zo ? sh[2] : a.Zo;
       int rc;

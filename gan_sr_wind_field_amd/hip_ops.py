@@ -224,6 +224,19 @@ def conv_fwd_tile(desc: ConvDesc, x: Tensor, wfrag: Tensor, y: Tensor, *, bias: 
     return True
 
 
+TILE_PLAN_FIELDS = ("TX", "TY", "TZ", "NTW", "ngroups", "ksplit", "xbufs", "TS")
+
+
+def last_tile_plan() -> dict:
+    """Diagnostic: the launch plan of this thread's most recent halo-tile launch (``wsr_last_tile_plan``) - spatial
+    tile, workgroup width in 16-channel n-tiles, channel groups, reduction splits, activation buffers, K-steps per
+    weight stage; all zero before the first one.  A declined call, or one served by another kernel, leaves it as it
+    was.  For tests that assert which instantiation a case reached: nothing in the product path reads it."""
+    buf = (C.c_int32 * len(TILE_PLAN_FIELDS))()
+    check(_lib.lib().wsr_last_tile_plan(buf), "last_tile_plan")
+    return dict(zip(TILE_PLAN_FIELDS, (int(v) for v in buf)))
+
+
 def conv1x1_covers(red: int, n_out: int, masked: bool) -> bool:
     """shapes the streaming 1x1x1 kernel is instantiated for (conv_1x1_v2.hip, ``wsr_conv1x1_bf16``): reduction
     channels x produced channels.  Only that kernel may run a 1x1x1 input gradient in place."""

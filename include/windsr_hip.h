@@ -215,6 +215,13 @@ typedef struct wsr_dgrad_opts {
 int wsr_conv3d_dgrad_tile(const wsr_conv_t* c, const void* dy, const void* wfrag_t, void* dx, float alpha,
                           int accumulate, int dx_planar, const wsr_lrelu_mask_t* mask, const wsr_dgrad_opts_t* opts,
                           void* stream);
+/* Diagnostic (additive export): the launch plan of the calling thread's most recent halo-tile launch through the two
+ * entry points above, as 8 values {TX, TY, TZ, NTW, ngroups, ksplit, xbufs, TS}: spatial tile, output-channel width of a
+ * workgroup in 16-wide n-tiles, channel groups, split count of the reduction (1 = single pass), activation buffers in
+ * LDS, K-steps per weight stage.  All zero before the first such launch; a call that was declined, or served by another
+ * kernel (streaming 1x1x1, sliding-window), leaves the record as it was.  For tests that assert which instantiation a
+ * case reached: no launch of the library reads the record.  Returns 0, WSR_EINVAL for a null pointer.           */
+int wsr_last_tile_plan(int32_t* plan8);
 /* ABI 6: `dtype` (wsr_dtype) of the fragment filter - bf16, or fp32 for the fp32 tile kernels (stride-1 convs in the
  * reference's own arithmetic; the 16-byte pieces then hold 4 channels instead of 8).                        */
 int64_t wsr_frag_filter_elems(int32_t rows, int32_t red, int32_t taps, int32_t dtype);

@@ -97,26 +97,28 @@ def _win(t, win):
     return t if win is None else t[:, win[0]:win[0] + win[1]]
 
 
-def _conv_slab(x, w, pad, xs):
-    """stride-1 conv3d of x (B, C, X, Y, Z) with zero padding ``pad``; ``xs`` = (x0, x1): only output x-planes
-    [x0, x1) (the input slab they read plus its halo)"""
+def _conv_slab(x, w, pad, xs, stride=(1, 1, 1)):
+    """conv3d of x (B, C, X, Y, Z) with zero padding ``pad`` and output stride ``stride``; ``xs`` = (x0, x1): only
+    output x-planes [x0, x1) (the input slab they read plus its halo)"""
+    stride = tuple(stride)
     if xs is None:
-        return F.conv3d(x, w, None, 1, tuple(pad))
+        return F.conv3d(x, w, None, stride, tuple(pad))
     kx = w.shape[2]
     xp = F.pad(x, (pad[2], pad[2], pad[1], pad[1], pad[0], pad[0]))
-    return F.conv3d(xp[:, :, xs[0]:xs[1] + kx - 1], w, None, 1, 0)
+    return F.conv3d(xp[:, :, xs[0] * stride[0]:(xs[1] - 1) * stride[0] + kx], w, None, stride, 0)
 
 
 def ref_fwd(x, w, pad, *, ups=False, bias=None, act=False, slope=0.2, chan_scale=None, alpha=1.0, res=None, beta=0.0,
-            in_win=None, xs=None):
+            in_win=None, xs=None, stride=(1, 1, 1)):
     """y = alpha * s * lrelu(conv(up?(x), w) + bias) + beta * res  (the forward epilogue order of ``wsr_epilogue_t``).
     ``in_win`` = (off, C): channels of x that enter; ``chan_scale`` (B, Cout); ``xs``: output x-planes [x0, x1) only
-    (``res`` then covers those planes).  Returns (ref, A)."""
+    (``res`` then covers those planes); ``stride``: the conv's output stride (the discriminator's down-sampling convs).
+    Returns (ref, A)."""
     x, w = _win(_d(x), in_win), _d(w)
     if ups:
         x = up2(x)
-    v = _conv_slab(x, w, pad, xs)
-    a = _conv_slab(x.abs(), w.abs(), pad, xs)
+    v = _conv_slab(x, w, pad, xs, stride)
+    a = _conv_slab(x.abs(), w.abs(), pad, xs, stride)
     if bias is not None:
         b = _d(bias).view(1, -1, 1, 1, 1)
         v, a = v + b, a + b.abs()

@@ -1070,17 +1070,26 @@ def test_fused_content_losses_vs_reference_fixture_and_oracle(golden, hip):
     assert rel_l2(srd.grad, 2 * (SR - HR) / (3 * nv)) < 1e-6
 
 
+# (TX, TY, TZ, NTW, ngroups, ksplit) of the launches below: all four run the first tile shape in 32-wide groups (few
+# tiles), and the two with Cin >= 64 split their reduction (the wrapper always passes a workspace)
+STRIDED_PLANS = {"d_down_s221": (4, 4, 9, 2, 2, 2), "d_down_s222": (4, 4, 11, 2, 1, 1),
+                 "d_down_n256": (4, 4, 6, 2, 8, 8), "d_down_k5": (4, 4, 6, 2, 1, 1)}
+
+
 @pytest.mark.parametrize("name,cin,cout,k,s,p,xyz,B", [
     ("d_down_s221", 64, 64, (4, 4, 3), (2, 2, 1), (1, 1, 1), (12, 10, 9), 1),     # blocks 1-3 of D
     ("d_down_s222", 32, 32, (4, 4, 3), (2, 2, 2), (1, 1, 1), (16, 12, 22), 2),    # first / last block (halved z)
-    ("d_down_n256", 256, 256, (4, 4, 3), (2, 2, 1), (1, 1, 1), (8, 8, 6), 1),     # two 128-channel groups
+    ("d_down_n256", 256, 256, (4, 4, 3), (2, 2, 1), (1, 1, 1), (8, 8, 6), 1),     # eight 32-channel groups
     ("d_down_k5", 32, 32, (4, 4, 5), (2, 2, 2), (1, 1, 2), (10, 12, 11), 1),      # feat_kern_size 5
 ])
 def test_conv_tile_strided_forward_vs_cpu(hip, name, cin, cout, k, s, p, xyz, B):
     """Stride-2 down-sampling convs of the discriminator (torch_blocks.py:138-142) through the halo-tile kernel:
-    forward with bias + LeakyReLU against an fp32 CPU conv of the same bf16-rounded operands."""
+    forward with bias + LeakyReLU against an fp32 CPU conv of the same bf16-rounded operands, and element-wise against
+    float64 (K = taps * Cin + the split count the launch reports); the output is guarded.  The instantiation matrix of
+    this path is test_conv_strided_matrix.py."""
     o = ops()
     dt = torch.bfloat16
+    plan = STRIDED_PLANS[name]
     gen = torch.Generator().manual_seed(cin + 3 * cout + sum(s))
     x = torch.randn((B, cin) + tuple(xyz), generator=gen).bfloat16().float()
     w = (torch.randn((cout, cin) + tuple(k), generator=gen) / math.sqrt(cin * k[0] * k[1] * k[2])).bfloat16().float()
@@ -1089,11 +1098,18 @@ def test_conv_tile_strided_forward_vs_cpu(hip, name, cin, cout, k, s, p, xyz, B)
     xb = to_ndhwc(x, cin, 0, dt)
     d = o.make_desc(geom, dt, B, xyz, cin, 0, cout, 0)
     oxyz = (d.Xo, d.Yo, d.Zo)
-    yb = torch.full((B,) + oxyz + (cout,), float("nan"), dtype=dt, device=DEV)
+    yg = kb.Guarded((B,) + oxyz + (cout,), dt, DEV, fill=float("nan"))
+    yb = yg.t
     assert o.conv_fwd_tile(d, xb, o.pack_filter_frag(packed_master(w)), yb, bias=bias.to(DEV), act=True, slope=0.2)
+    got_plan = o.last_tile_plan()
+    assert tuple(got_plan[f] for f in ("TX", "TY", "TZ", "NTW", "ngroups", "ksplit")) == plan, (name, got_plan)
     ref = F.leaky_relu(F.conv3d(x, w, bias, s, p), 0.2)
     assert tuple(ref.shape[2:]) == oxyz
     assert rel_l2(from_ndhwc(yb, 0, cout), ref) < 4e-3, name
+    kb.assert_guards_intact(yg, label=name)
+    r64, A = kb.ref_fwd(x, w, p, stride=s, bias=bias, act=True, slope=kb._f32(0.2))
+    kb.assert_within(from_ndhwc(yb, 0, cout), r64, kb.bound(r64, A, cin * k[0] * k[1] * k[2] + plan[5], kb.RHO_BF16),
+                     f"strided fwd[{name}]")
 
 
 @pytest.mark.parametrize("name,k,xyz,B,ctot,off,bias", [

@@ -63,6 +63,40 @@ def test_references_equal_float64_autograd(k, ups, B):
     assert bool((A >= got.abs() - 1e-12).all())
 
 
+@pytest.mark.parametrize("k,s,pad,xyz", [((4, 4, 3), (2, 2, 1), (1, 1, 1), (9, 8, 5)),
+                                         ((4, 4, 5), (2, 2, 2), (1, 1, 2), (8, 7, 9)),
+                                         ((3, 3, 3), (1, 1, 2), (1, 1, 1), (5, 4, 7)),
+                                         ((3, 4, 3), (1, 2, 1), (0, 0, 0), (6, 9, 4))])
+def test_strided_forward_reference_equals_a_direct_sum(k, s, pad, xyz):
+    """``ref_fwd(stride=...)``: every output voxel is the explicit sum over taps at input voxel o * s - pad + tap
+    (written out here, without conv3d), A the same over magnitudes, and an x slab is the slab of the whole"""
+    gen = torch.Generator().manual_seed(sum(k) + 7 * sum(s))
+    B, cin, cout = 2, 3, 4
+    x = torch.randn((B, cin) + xyz, generator=gen, dtype=f64)
+    w = torch.randn((cout, cin) + k, generator=gen, dtype=f64)
+    bias = torch.randn(cout, generator=gen, dtype=f64)
+    out = tuple((xyz[i] + 2 * pad[i] - k[i]) // s[i] + 1 for i in range(3))
+    xp = F.pad(x, (pad[2], pad[2], pad[1], pad[1], pad[0], pad[0]))
+    want, mag = torch.zeros((B, cout) + out, dtype=f64), torch.zeros((B, cout) + out, dtype=f64)
+    for kx in range(k[0]):
+        for ky in range(k[1]):
+            for kz in range(k[2]):
+                sl = xp[:, :, kx:kx + (out[0] - 1) * s[0] + 1:s[0], ky:ky + (out[1] - 1) * s[1] + 1:s[1],
+                        kz:kz + (out[2] - 1) * s[2] + 1:s[2]]
+                want += torch.einsum("bcxyz,nc->bnxyz", sl, w[:, :, kx, ky, kz])
+                mag += torch.einsum("bcxyz,nc->bnxyz", sl.abs(), w[:, :, kx, ky, kz].abs())
+    got, A = kb.ref_fwd(x, w, pad, stride=s)
+    assert tuple(got.shape[2:]) == out
+    torch.testing.assert_close(got, want, rtol=1e-12, atol=1e-12)
+    torch.testing.assert_close(A, mag, rtol=1e-12, atol=1e-12)
+    got_b, A_b = kb.ref_fwd(x, w, pad, stride=s, bias=bias, act=True)
+    torch.testing.assert_close(got_b, F.leaky_relu(want + bias.view(1, -1, 1, 1, 1), 0.2), rtol=1e-12, atol=1e-12)
+    torch.testing.assert_close(A_b, mag + bias.abs().view(1, -1, 1, 1, 1), rtol=1e-12, atol=1e-12)
+    got_s, A_s = kb.ref_fwd(x, w, pad, stride=s, xs=(1, out[0]))
+    torch.testing.assert_close(got_s, want[:, :, 1:], rtol=1e-12, atol=1e-12)
+    torch.testing.assert_close(A_s, mag[:, :, 1:], rtol=1e-12, atol=1e-12)
+
+
 # ---- CPU emulations of the kernels' arithmetic pass the bound ---------------------------------------------------------
 
 def _fp32_tap_order(x, w, pad):
