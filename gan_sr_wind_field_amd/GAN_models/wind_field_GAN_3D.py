@@ -693,6 +693,23 @@ class wind_field_GAN_3D(BaseGAN):
         TL = hip_ops.trilinear_xy(f(LR), self.cfg.scale)
         return hip_ops.level_diagnostics(f(HR), f(SR), TL, f(x.to(HR.device)), f(y.to(HR.device)), f(Z))
 
+    # ------------------------------------------------------------------ horizontal energy spectra ([SPECTRUM])
+    def level_spectra(self, HR, SR, LR, window="hann"):
+        """The five sums of ``spectra.SPECTRUM_SUMS`` per sample, z level and horizontal wavenumber bin of a batch ->
+        float64 (B, NZ, NK, 5) on the tensors' device: the trilinear baseline of ``LR`` is built here
+        (``wsr_trilinear_xy`` on a GPU, ``F.interpolate`` on a CPU), the sums come from ``hip_ops.level_spectra`` on a GPU
+        and from ``spectra.level_spectra_reference`` on a CPU.  Reads no weights: the same inside ``ema_scope()``."""
+        from ..spectra import level_spectra_reference
+
+        if not HR.is_cuda:
+            return level_spectra_reference(HR, SR.detach(), _trilinear(LR, self.cfg.scale), window)
+        from .. import hip_ops
+
+        def f(t):
+            return t.detach().float().contiguous()
+
+        return hip_ops.level_spectra(f(HR), f(SR), hip_ops.trilinear_xy(f(LR), self.cfg.scale), window)
+
     def make_new_labels(self, it):
         """Real / fake label vectors of this iteration (reference :627-678)."""
         t = self.cfg.training

@@ -27,6 +27,7 @@ EXPORTS = [
     "wsr_dihedral_members", "wsr_ensemble_reduce",
     "wsr_tile_gather", "wsr_tile_stitch",
     "wsr_level_diagnostics_workspace_floats", "wsr_level_diagnostics",
+    "wsr_level_spectra_bins", "wsr_level_spectra_workspace_floats", "wsr_level_spectra",
     "wsr_last_tile_plan",
 ]
 
@@ -158,6 +159,7 @@ def lib() -> C.CDLL:
         "wsr_tile_stitch": [vp, C.POINTER(C.c_int32), i32, C.POINTER(C.c_int32), i32, i32, i32, i32, i32, i32, i32, i32,
                             i32, i32, vp, vp, vp],   # additive export
         "wsr_level_diagnostics": [vp, i32, vp, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp],   # additive export
+        "wsr_level_spectra": [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp],   # additive export
         "wsr_last_tile_plan": [C.POINTER(C.c_int32)],   # additive export (diagnostic)
     }
     for name, argtypes in sig.items():
@@ -170,6 +172,10 @@ def lib() -> C.CDLL:
     L.wsr_physics_loss_workspace_floats.restype = C.c_int64
     L.wsr_level_diagnostics_workspace_floats.argtypes = [i32, i32, i32, i32]
     L.wsr_level_diagnostics_workspace_floats.restype = C.c_int64
+    L.wsr_level_spectra_bins.argtypes = [i32, i32]
+    L.wsr_level_spectra_bins.restype = C.c_int32
+    L.wsr_level_spectra_workspace_floats.argtypes = [i32, i32, i32, i32]
+    L.wsr_level_spectra_workspace_floats.restype = C.c_int64
     if L.wsr_abi_version() != 9:
         raise RuntimeError("libwindsr_hip.so ABI version mismatch")
     _lib = L

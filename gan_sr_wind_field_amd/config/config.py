@@ -30,6 +30,10 @@ Extension (optional keys, defaults keep reference behaviour):
             --test also writes, per z level, wind speed, error-vector length, speed bias, direction error and the rms
             divergence of truth, network and baseline (diagnostics.py, csrc/diagnostics.hip), for the whole test set
             and per field
+  [SPECTRUM] energy_spectrum / per_level / window
+            --test also writes the horizontal kinetic-energy spectrum of truth, network and baseline and their
+            coherence with the truth per wavenumber bin (spectra.py, csrc/spectra.hip), for the whole test set and
+            per z level
 """
 from __future__ import annotations
 
@@ -503,6 +507,50 @@ class DiagnosticsConfig(IniConfig):
         return "[DIAGNOSTICS]\n" + "".join(f"{k} = {getattr(self, k)}\n" for k, _ in self._schema)
 
 
+class SpectrumConfig(IniConfig):
+    """[SPECTRUM] (extension): horizontal energy spectra of ``run.py --test`` (spectra.py, csrc/spectra.hip); absent
+    section = off, and not printed by ``asINI``.  ``energy_spectrum``: ``--test`` also writes
+    ``<name>____energy_spectrum.csv``, one row per wavenumber bin; ``per_level``: ... and
+    ``<name>____energy_spectrum_levels.csv``, one row per z level and bin; ``window``: ``hann`` or ``none``, the taper
+    of the detrended planes."""
+
+    present: bool = False
+    energy_spectrum: bool = True
+    per_level: bool = False
+    window: str = "hann"
+    _schema = (("energy_spectrum", _B), ("per_level", _B))
+
+    def setSpectrumConfig(self, section):
+        """``section`` None (no [SPECTRUM] in the file) restores the defaults and switches the section off."""
+        self.present = section is not None
+        for key, kind in self._schema:
+            try:
+                val = None if section is None else _read(section, key, kind)
+            except ValueError:
+                raise ValueError(f"[SPECTRUM] {key} must be True or False, not {section.get(key)!r}") from None
+            setattr(self, key, getattr(SpectrumConfig, key) if val is None else val)
+        raw = None if section is None else section.get("window")
+        self.window = SpectrumConfig.window if raw is None else raw.strip().lower()
+
+    def validate(self) -> None:
+        if not self.present:
+            return
+        if self.window not in ("hann", "none"):
+            raise ValueError(f"[SPECTRUM] window must be hann or none, not {self.window!r}")
+        if self.per_level and not self.energy_spectrum:
+            raise ValueError("[SPECTRUM] per_level = True needs energy_spectrum = True: the per-level rows are the "
+                             "terms of the spectrum")
+
+    @property
+    def on(self) -> bool:
+        """``--test`` takes the spectral sums and writes the spectrum"""
+        return bool(self.present and self.energy_spectrum)
+
+    def __str__(self) -> str:
+        return ("[SPECTRUM]\n" + "".join(f"{k} = {getattr(self, k)}\n" for k, _ in self._schema)
+                + f"window = {self.window}\n")
+
+
 class Config(IniConfig):
     name: str = "default_name"
     model: str = "default_model"
@@ -531,6 +579,7 @@ class Config(IniConfig):
     ensemble: EnsembleConfig = EnsembleConfig()
     tile: TileConfig = TileConfig()
     diagnostics: DiagnosticsConfig = DiagnosticsConfig()
+    spectrum: SpectrumConfig = SpectrumConfig()
     compute_dtype: str = "fp32"
     is_train: bool
     is_use: bool
@@ -569,6 +618,8 @@ class Config(IniConfig):
         self.tile.validate()
         self.diagnostics.setDiagnosticsConfig(parser["DIAGNOSTICS"] if parser.has_section("DIAGNOSTICS") else None)
         self.diagnostics.validate()
+        self.spectrum.setSpectrumConfig(parser["SPECTRUM"] if parser.has_section("SPECTRUM") else None)
+        self.spectrum.validate()
 
     def setBaseConfig(self, base):
         self.name = base.get("name")
@@ -608,4 +659,6 @@ class Config(IniConfig):
             out += "\n" + str(self.tile)
         if getattr(self.diagnostics, "present", False):
             out += "\n" + str(self.diagnostics)
+        if getattr(self.spectrum, "present", False):
+            out += "\n" + str(self.spectrum)
         return out

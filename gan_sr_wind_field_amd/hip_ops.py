@@ -1303,3 +1303,43 @@ def level_diagnostics(HR: Tensor, SR: Tensor, TL: Tensor, x: Tensor, y: Tensor, 
     check(L.wsr_level_diagnostics(_p(HR), HR.shape[1], _p(SR), SR.shape[1], _p(TL), TL.shape[1], _p(Z), _p(x), _p(y), B,
                                   X, Y, NZ, _p(ws), _p(out), _stream()), "level_diagnostics")
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# horizontal energy spectra ([SPECTRUM]; csrc/spectra.hip)
+# ---------------------------------------------------------------------------------------------------------------------
+SPECTRUM_SUMS = 5  # WSR_SPECTRUM_SUMS
+SPECTRUM_MAX_XY = 1024  # WSR_SPECTRUM_MAX_XY
+SPECTRUM_WINDOWS = {"none": 0, "hann": 1}  # WSR_SPECTRUM_WINDOW_*
+
+
+def level_spectra(HR: Tensor, SR: Tensor, TL: Tensor, window: str = "hann", out: Optional[Tensor] = None) -> Tensor:
+    """Five sums per sample, z level and horizontal wavenumber bin -> float64 (B, NZ, NK, 5), in the order of
+    ``spectra.SPECTRUM_SUMS``: the kinetic energy of ``HR``, ``SR`` and the baseline ``TL`` (B, C >= 3, X, Y, NZ;
+    channels 0..2 are read) and the co-spectra of HR with SR and with TL, from a direct separable 2-D DFT over (X, Y) of
+    the detrended, windowed (``window``: ``hann`` or ``none``) planes; NK = ``spectra.n_bins(X, Y)``.  No atomics: the
+    same bits on every call.  ``out``: a float64 (B, NZ, NK, 5) slice to write into (``wsr_level_spectra``)."""
+    _need_cuda(HR, SR, TL, out)
+    _planar5("level_spectra", "HR", HR, 3)
+    _planar5("level_spectra", "SR", SR, 3)
+    _planar5("level_spectra", "TL", TL, 3)
+    B, _, X, Y, NZ = HR.shape
+    for name, t in (("SR", SR), ("TL", TL)):
+        if (t.shape[0],) + tuple(t.shape[2:]) != (B, X, Y, NZ):
+            raise ValueError(f"level_spectra: {name} {tuple(t.shape)} does not match HR {tuple(HR.shape)}")
+    if window not in SPECTRUM_WINDOWS:
+        raise ValueError(f"level_spectra: window must be one of {tuple(SPECTRUM_WINDOWS)} (codes 0, 1), not {window!r}")
+    if X > SPECTRUM_MAX_XY or Y > SPECTRUM_MAX_XY or B > 65535 or NZ > 65535 or X * Y * NZ >= 2 ** 31:
+        raise ValueError(f"level_spectra: at most {SPECTRUM_MAX_XY} points in x and y, 65535 samples, 65535 levels and "
+                         f"2^31 - 1 voxels per sample, not B = {B}, X = {X}, Y = {Y}, NZ = {NZ}")
+    L = _lib.lib()
+    NK = int(L.wsr_level_spectra_bins(X, Y))
+    if out is None:
+        out = torch.empty((B, NZ, NK, SPECTRUM_SUMS), dtype=torch.float64, device=HR.device)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (B, NZ, NK, SPECTRUM_SUMS) or not out.is_contiguous():
+        raise ValueError(f"level_spectra wants out as a contiguous float64 ({B}, {NZ}, {NK}, {SPECTRUM_SUMS}) tensor, got "
+                         f"{out.dtype} {tuple(out.shape)}")
+    ws = torch.empty(int(L.wsr_level_spectra_workspace_floats(B, X, Y, NZ)), dtype=torch.float32, device=HR.device)
+    check(L.wsr_level_spectra(_p(HR), HR.shape[1], _p(SR), SR.shape[1], _p(TL), TL.shape[1], B, X, Y, NZ,
+                              SPECTRUM_WINDOWS[window], _p(ws), _p(out), _stream()), "level_spectra")
+    return out

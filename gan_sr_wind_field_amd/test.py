@@ -40,6 +40,16 @@ one (NZ, 15) table - the device loop with ONE ``hip_ops.level_diagnostics`` laun
     ./test_output/<cfg.name>____level_profile_fields.csv          (``per_field``) one row ``field,level,...`` per field and level
     ./test_output/<cfg.name>____level_profile_reverse_interpolate.csv   (+ ``..._fields_reverse_interpolate.csv``)
         with ``reverse_interpolate``: the same on the raw truth, the re-levelled SR and baseline and the raw altitudes
+
+With a ``[SPECTRUM]`` section both loops also add the five spectral sums per level and horizontal wavenumber bin of every
+batch (``spectra.py``) into one (NZ, NK, 5) table - the device loop with ONE ``hip_ops.level_spectra`` launch per batch
+on the stored baseline (which it then builds for every batch), its table a device tensor read once after the last batch;
+the host loop with ``spectra.level_spectra_reference`` on the host tensors - and write
+    ./test_output/<cfg.name>____energy_spectrum.csv               one row ``bin,`` + ``SPECTRUM_COLUMNS`` per bin, summed
+                                                                   over fields and levels
+    ./test_output/<cfg.name>____energy_spectrum_levels.csv        (``per_level``) one row ``level,bin,...`` per level and bin
+    ./test_output/<cfg.name>____energy_spectrum_reverse_interpolate.csv   (+ ``..._levels_reverse_interpolate.csv``)
+        with ``reverse_interpolate``: the same on the raw truth and the re-levelled SR and baseline
 """
 from __future__ import annotations
 
@@ -56,6 +66,7 @@ import torch.nn as nn
 from .GAN_models.wind_field_GAN_3D import calculate_PSNR, wind_field_GAN_3D
 from .diagnostics import PROFILE_COLUMNS, level_sums_reference, profile_from_sums
 from .process_data import reverse_interpolate_z_axis
+from .spectra import SPECTRUM_COLUMNS, grid_spacing, level_spectra_reference, mode_counts, spectrum_from_sums
 
 METRIC_NAMES = ("PSNR", "PSNR_trilinear", "relative_error", "pix", "trilinear_pix", "relative_error_trilinear",
                 "average_wind_speed", "old_pix", "old_pix_trilinear")
@@ -193,8 +204,46 @@ def _write_profile_rows(f, prof, prefix):
         f.write(f"{prefix}{lvl}," + ",".join(str(prof[k][lvl]) for k in PROFILE_COLUMNS) + "\n")
 
 
+class _Spectrum:
+    """[SPECTRUM]: the spectral sums of the whole test set, (NZ, NK, 5) float64 on the device of the sums it is given,
+    and the files made of them: ``path`` (summed over the levels) and, unless None, ``levels_path`` (per level).
+    ``d``: the mean grid spacing in metres."""
+
+    def __init__(self, path, levels_path, uvw, d):
+        self.path, self.levels_path, self.uvw, self.d = path, levels_path, uvw, d
+        self.total, self.nfields, self.shape = None, 0, None
+
+    def add(self, sums, X, Y):
+        """``sums`` (B, NZ, NK, 5) of B fields of X x Y columns"""
+        t = sums.sum(dim=0)
+        self.total = t if self.total is None else self.total + t
+        self.nfields += sums.shape[0]
+        self.shape = (X, Y)
+
+    def close(self):
+        table = None if self.total is None else self.total.cpu()  # the ONE read
+        if table is not None:
+            N, counts = max(self.shape), mode_counts(*self.shape)
+        with open(self.path, "w") as f:
+            f.write("bin," + ",".join(SPECTRUM_COLUMNS) + "\n")
+            if table is not None:
+                spec = spectrum_from_sums(table.sum(dim=0), self.nfields * table.shape[0], self.uvw, N, self.d, counts)
+                _write_spectrum_rows(f, spec, "")
+        if self.levels_path is not None:
+            with open(self.levels_path, "w") as f:
+                f.write("level,bin," + ",".join(SPECTRUM_COLUMNS) + "\n")
+                for lvl in range(0 if table is None else table.shape[0]):
+                    _write_spectrum_rows(f, spectrum_from_sums(table[lvl], self.nfields, self.uvw, N, self.d, counts),
+                                         f"{lvl},")
+
+
+def _write_spectrum_rows(f, spec, prefix):
+    for k in range(len(spec[SPECTRUM_COLUMNS[0]])):
+        f.write(f"{prefix}{k}," + ",".join(str(spec[c][k]) for c in SPECTRUM_COLUMNS) + "\n")
+
+
 def _host_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread=None, seam=None, diag=None,
-               diag_rev=None):
+               diag_rev=None, spec=None, spec_rev=None):
     """one field at a time; baseline, re-levelling and metrics on the host (the reference's loop)"""
     dev = cfg.device
     for j, (LR, HR, Z, names, HR_raw, Z_raw) in enumerate(loader):
@@ -220,6 +269,9 @@ def _host_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread
                                                                       gan.y.cpu(), Z_raw[i:i + 1]),
                                  HR.shape[2] * HR.shape[3])
                     diag_rev.flush()
+                if spec_rev is not None:
+                    spec_rev.add(level_spectra_reference(HR_raw[i:i + 1], torch.as_tensor(SR_r), torch.as_tensor(TL_r),
+                                                         cfg.spectrum.window), HR.shape[2], HR.shape[3])
             vals = write_metrics(HR_i, SR_i, TL_i, names[i], out, uvw)
             for k, v in zip(METRIC_NAMES, vals):
                 avg[k] += v / n
@@ -227,6 +279,8 @@ def _host_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread
                 diag.add(names[i:i + 1], level_sums_reference(HR_i, SR_i, TL_i, gan.x.cpu(), gan.y.cpu(), Z[i:i + 1]),
                          HR.shape[2] * HR.shape[3])
                 diag.flush()
+            if spec is not None:
+                spec.add(level_spectra_reference(HR_i, SR_i, TL_i, cfg.spectrum.window), HR.shape[2], HR.shape[3])
             if j % cfg.training.log_period == 0:
                 write_fields(LR[i], HR[i], SR_i[0], TL[i], Z[i], cfg.env.this_runs_folder, names[i],
                              HR_raw[i] if rev else None, Z_raw[i] if rev else None, None,
@@ -235,7 +289,7 @@ def _host_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread
 
 
 def _device_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread=None, seam=None, diag=None,
-                 diag_rev=None):
+                 diag_rev=None, spec=None, spec_rev=None):
     """[EVAL] device_metrics: one generator forward and one metrics launch per batch; the (B, 7) rows wait in a device
     table and are read once per ``log_period`` batches and at the end"""
     from . import hip_ops
@@ -282,10 +336,12 @@ def _device_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spre
         nvox = HR.shape[2] * HR.shape[3] * HR.shape[4]
         sums = hip_ops.field_metrics(HR_d, SR_d, LR=LR_d, scale=s)  # (the baseline is blended inside, never stored)
         keep = j % cfg.training.log_period == 0
-        TL_d = hip_ops.trilinear_xy(LR_d, s) if rev or keep or diag is not None else None
+        TL_d = hip_ops.trilinear_xy(LR_d, s) if rev or keep or diag is not None or spec is not None else None
         ncols = HR.shape[2] * HR.shape[3]
         if diag is not None:  # (the stored baseline: its divergence needs the neighbouring columns)
             diag.add(names, hip_ops.level_diagnostics(HR_d, SR_d, TL_d, gan.x, gan.y, Z_d), ncols)
+        if spec is not None:  # (one launch per batch, on the stored baseline)
+            spec.add(hip_ops.level_spectra(HR_d, SR_d, TL_d, cfg.spectrum.window), HR.shape[2], HR.shape[3])
         sums_raw = None
         if rev:  # back onto the raw terrain-following levels of every column, metrics against the raw truth
             raw_d, zraw_d = (t.to(dev, non_blocking=True).contiguous() for t in (HR_raw, Z_raw))
@@ -293,6 +349,8 @@ def _device_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spre
             sums_raw = hip_ops.field_metrics(raw_d, SR_r, TL=TL_r)
             if diag_rev is not None:
                 diag_rev.add(names, hip_ops.level_diagnostics(raw_d, SR_r, TL_r, gan.x, gan.y, zraw_d), ncols)
+            if spec_rev is not None:
+                spec_rev.add(hip_ops.level_spectra(raw_d, SR_r, TL_r, cfg.spectrum.window), HR.shape[2], HR.shape[3])
         # (per field: the sums in the order the rows are written - all of `out`, then all of `out_rev`, per batch)
         pending.append((list(names), nvox, sums, sums_raw))
         if keep:
@@ -350,6 +408,17 @@ def test(cfg, dataset_test, reverse_interpolate: bool = False):
     if with_diag:
         gan.x, gan.y = (torch.from_numpy(np.asarray(v)).float().contiguous().to(dev) for v in (dataset_test.x, dataset_test.y))
 
+    # ([SPECTRUM]: the spectral sums of every batch, one more CSV - two with per_level - per set of levels)
+    sp = getattr(cfg, "spectrum", None)
+    with_spec = sp is not None and sp.on
+
+    def spectrum_acc(suffix):
+        def path(levels):
+            return os.path.join("./test_output", f"{cfg.name}____energy_spectrum{'_levels' if levels else ''}{suffix}.csv")
+
+        return _Spectrum(path(False), path(True) if sp.per_level else None, uvw,
+                         grid_spacing(np.asarray(dataset_test.x), np.asarray(dataset_test.y)))
+
     def profile_path(fields, suffix):
         return os.path.join("./test_output", f"{cfg.name}____level_profile{'_fields' if fields else ''}{suffix}.csv")
 
@@ -361,6 +430,8 @@ def test(cfg, dataset_test, reverse_interpolate: bool = False):
              else contextlib.nullcontext()) as pf_rev:
         diag = _LevelProfile(profile_path(False, ""), uvw, pf) if with_diag else None
         diag_rev = _LevelProfile(profile_path(False, "_reverse_interpolate"), uvw, pf_rev) if with_diag and rev else None
+        spec = spectrum_acc("") if with_spec else None
+        spec_rev = spectrum_acc("_reverse_interpolate") if with_spec and rev else None
         out.write(cols + "\n")
         out_rev.write(cols + "\n")
         if with_spread:
@@ -368,10 +439,12 @@ def test(cfg, dataset_test, reverse_interpolate: bool = False):
         if with_seam:
             seam.write("field,mean_seam\n")
         if cfg.eval.on and torch.device(dev).type == "cuda":
-            _device_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread, seam, diag, diag_rev)
+            _device_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread, seam, diag, diag_rev, spec,
+                         spec_rev)
         else:
-            _host_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread, seam, diag, diag_rev)
-        for d in (diag, diag_rev):
+            _host_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread, seam, diag, diag_rev, spec,
+                       spec_rev)
+        for d in (diag, diag_rev, spec, spec_rev):
             if d is not None:
                 d.close()
     with open("./test_output/averages.csv", "a") as f:

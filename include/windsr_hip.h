@@ -644,6 +644,39 @@ int wsr_level_diagnostics(const float* hr, int32_t hr_c, const float* sr, int32_
                           const float* zc, const float* xs, const float* ys, int32_t B, int32_t X, int32_t Y, int32_t NZ,
                           float* workspace, double* sums, void* stream);
 
+/* ---- horizontal energy spectra ([SPECTRUM]; csrc/spectra.hip) ---------------------------------------------
+ * wsr_level_spectra: out (B, NZ, NK, WSR_SPECTRUM_SUMS) doubles, NK = wsr_level_spectra_bins(X, Y): per sample, z level
+ * and wavenumber bin the kinetic energy of hr, sr and the baseline tl and the co-spectra of hr with sr and with tl
+ * (e_hr, e_sr, e_tl, c_sr, c_tl), from ONE 2-D DFT over (X, Y) per sample, field, component (channels 0..2 of
+ * hr (B, hr_c, X, Y, NZ), sr (B, sr_c, ...), tl (B, tl_c, ...), fp32 planar) and level:
+ *    g = (f - m) * wx(i) * wy(j)       m the plain mean of f over the plane; window WSR_SPECTRUM_WINDOW_HANN:
+ *                                      wx(i) = sin^2(pi (i + 1/2) / X), likewise wy, an axis of length 1 has weight 1;
+ *                                      WSR_SPECTRUM_WINDOW_NONE: 1
+ *    F(kx, ky) = sum g exp(-2 pi i (kx i / X + ky j / Y)),   ky = 0 .. Y / 2, Hermitian weight h(ky) = 1 for ky = 0
+ *                                      and, Y even, for ky = Y / 2, else 2
+ *    bin(kx, ky): with N = max(X, Y), kx' the signed frequency of kx and q = (kx' Y)^2 + (ky X)^2 the k >= 0 with
+ *                                      (2k - 1)^2 (XY)^2 <= 4 N^2 q < (2k + 1)^2 (XY)^2 (k = 0: the right half alone), that
+ *                                      is floor(N sqrt((kx'/X)^2 + (ky/Y)^2) + 1/2), decided in 64-bit integers;
+ *                                      NK = floor(N / sqrt(2) + 1/2) + 1
+ *    e_a = 1/2 sum_comp sum_modes-in-bin h |F_a|^2 / (X Y W2),     W2 = sum (wx wy)^2 in double
+ *    c_b = 1/2 sum_comp sum_modes-in-bin h Re(F_hr conj F_b) / (X Y W2)
+ * The transform is a direct separable DFT in fp32 (twiddles from a table of double-precision sincospi values, indexed by
+ * (k i) mod n in integers); the modes of a bin are added in ascending (ky, kx), per ky in fp32, over ky in double: no
+ * atomics, evaluated without contraction, the same bits on every call, and c_sr = e_hr bit for bit when sr = hr.
+ * workspace: wsr_level_spectra_workspace_floats(B, X, Y, NZ) floats (0 for sizes the entry refuses), 16-byte aligned:
+ * the bin table, the window, mean partials, the row transform (B * 9 * X * (Y/2 + 1) * NZ complex values) and one
+ * partial table per ky.  A null pointer, a channel count < 3, a non-positive size or an unknown window: WSR_EINVAL;
+ * X or Y > 1024, B > 65535, NZ > 65535 or X * Y * NZ >= 2^31: WSR_EUNSUPPORTED; nothing is written in either case. */
+#define WSR_SPECTRUM_SUMS 5
+#define WSR_SPECTRUM_MAX_XY 1024
+#define WSR_SPECTRUM_WINDOW_NONE 0
+#define WSR_SPECTRUM_WINDOW_HANN 1
+int32_t wsr_level_spectra_bins(int32_t X, int32_t Y);
+int64_t wsr_level_spectra_workspace_floats(int32_t B, int32_t X, int32_t Y, int32_t NZ);
+int wsr_level_spectra(const float* hr, int32_t hr_c, const float* sr, int32_t sr_c, const float* tl, int32_t tl_c,
+                      int32_t B, int32_t X, int32_t Y, int32_t NZ, int32_t window, float* workspace, double* out,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
