@@ -67,6 +67,9 @@ class wind_field_GAN_3D(BaseGAN):
         self.optimizers, self.schedulers = [], []
         self.train_G_loss_dict = _zeros_dict(_G_LOSS_KEYS)
         self.validation_G_loss_dict = _zeros_dict(_G_LOSS_KEYS)
+        if self._spectral_on():  # ([SPECTRAL_LOSS]: one more logged term; absent section, exactly the keys above)
+            self.train_G_loss_dict["spectral"] = torch.zeros(1)
+            self.validation_G_loss_dict["spectral"] = torch.zeros(1)
         self.D_loss_dict = _zeros_dict(("train_loss", "validation_loss"))
         self.hist_dict = {
             "val_grad_G_first_layer": torch.zeros(1), "val_grad_G_last_layer": torch.zeros(1),
@@ -321,10 +324,16 @@ class wind_field_GAN_3D(BaseGAN):
         return y_pred, fake_y_pred
 
     # ------------------------------------------------------------------ G losses
+    def _spectral_on(self) -> bool:
+        """``[SPECTRAL_LOSS]`` is in the configuration: the generator loss carries the energy-spectrum term"""
+        return bool(getattr(getattr(self.cfg, "spectral_loss", None), "on", False))
+
     def log_G_losses(self, fake_HR, losses: dict, training_iteration: bool):
         target = self.train_G_loss_dict if training_iteration else self.validation_G_loss_dict
         for k in _G_LOSS_KEYS:
             target[k] = losses[k]
+        if "spectral" in losses:
+            target["spectral"] = losses["spectral"]
         if not training_iteration:
             self.metrics_dict["pix_loss_unscaled"] = losses["pix"] / self.cfg.training.pixel_loss_weight
             self.hist_dict["SR_pix_distribution"] = fake_HR.detach().cpu().numpy()
@@ -363,6 +372,14 @@ class wind_field_GAN_3D(BaseGAN):
         keys = ("adversarial", "feature_D", "pix", "xy_gradient", "z_gradient", "divergence", "xy_divergence")
         wkey = (str(self.device), t.adversarial_loss_weight, t.feature_D_loss_weight, t.pixel_loss_weight, t.gradient_xy_loss_weight,
                 t.gradient_z_loss_weight, t.divergence_loss_weight, t.xy_divergence_loss_weight)
+        # [SPECTRAL_LOSS]: the energy-spectrum term (spectral_loss.py) is one more entry of the core vector - not finite, it
+        # makes the core total not finite and the Adam step is skipped, exactly like a non-finite pix; the guards of the
+        # physics terms and the speculative pass are as they were.  A plain mean over samples: no collective of its own.
+        spec = None
+        if self._spectral_on():
+            from ..spectral_loss import spectral_loss
+            spec = spectral_loss(HR, fake_HR, self.cfg.spectral_loss)
+            wkey = wkey + (self.cfg.spectral_loss.weight,)
         if getattr(self, "_loss_w", (None,))[0] != wkey:
             self._loss_w = (wkey, torch.tensor([float(v) for v in wkey[1:]], dtype=torch.float32).to(self.device))
         L = {}
@@ -372,8 +389,12 @@ class wind_field_GAN_3D(BaseGAN):
             # hang on their graph at all - a zero upstream gradient times a NaN derivative is a NaN in every filter gradient
             wv = self._loss_w[1]
             Lc = torch.stack([v.reshape(()) for v in unweighted[:3]]) * wv[:3]
-            Lp = torch.stack([v.reshape(()) for v in unweighted[3:]]) * wv[3:]
+            Lp = torch.stack([v.reshape(()) for v in unweighted[3:]]) * wv[3:7]
             L.update(zip(keys, Lc.unbind() + Lp.unbind()))
+            if spec is not None:
+                Ls = spec.reshape(1) * wv[7:]
+                L["spectral"] = Ls.reshape(())
+                Lc = torch.cat([Lc, Ls])
             L["feature_D"] = L["feature_D"].reshape(1)  # (the reference's placeholder is torch.zeros(1): totals are (1,))
             return Lc, Lp
 

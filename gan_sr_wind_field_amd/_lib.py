@@ -28,6 +28,8 @@ EXPORTS = [
     "wsr_tile_gather", "wsr_tile_stitch",
     "wsr_level_diagnostics_workspace_floats", "wsr_level_diagnostics",
     "wsr_level_spectra_bins", "wsr_level_spectra_workspace_floats", "wsr_level_spectra",
+    "wsr_spectral_energy_workspace_floats", "wsr_spectral_energy_saved_floats", "wsr_spectral_energy",
+    "wsr_spectral_energy_bwd",
     "wsr_last_tile_plan",
 ]
 
@@ -160,6 +162,8 @@ def lib() -> C.CDLL:
                             i32, i32, vp, vp, vp],   # additive export
         "wsr_level_diagnostics": [vp, i32, vp, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp],   # additive export
         "wsr_level_spectra": [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp],   # additive export
+        "wsr_spectral_energy": [vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp],   # additive export
+        "wsr_spectral_energy_bwd": [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp],   # additive export
         "wsr_last_tile_plan": [C.POINTER(C.c_int32)],   # additive export (diagnostic)
     }
     for name, argtypes in sig.items():
@@ -176,6 +180,9 @@ def lib() -> C.CDLL:
     L.wsr_level_spectra_bins.restype = C.c_int32
     L.wsr_level_spectra_workspace_floats.argtypes = [i32, i32, i32, i32]
     L.wsr_level_spectra_workspace_floats.restype = C.c_int64
+    for name in ("wsr_spectral_energy_workspace_floats", "wsr_spectral_energy_saved_floats"):
+        getattr(L, name).argtypes = [i32, i32, i32, i32]
+        getattr(L, name).restype = C.c_int64
     if L.wsr_abi_version() != 9:
         raise RuntimeError("libwindsr_hip.so ABI version mismatch")
     _lib = L

@@ -34,6 +34,9 @@ Extension (optional keys, defaults keep reference behaviour):
             --test also writes the horizontal kinetic-energy spectrum of truth, network and baseline and their
             coherence with the truth per wavenumber bin (spectra.py, csrc/spectra.hip), for the whole test set and
             per z level
+  [SPECTRAL_LOSS] weight / window / k_min / k_max / rel_floor
+            the generator loss gains an energy-spectrum term: the mean squared log ratio of the binned horizontal
+            kinetic-energy spectra of SR and HR (spectral_loss.py, csrc/spectral_loss.hip), logged as ``spectral``
 """
 from __future__ import annotations
 
@@ -551,6 +554,63 @@ class SpectrumConfig(IniConfig):
                 + f"window = {self.window}\n")
 
 
+class SpectralLossConfig(IniConfig):
+    """[SPECTRAL_LOSS] (extension): an energy-spectrum term of the generator loss (spectral_loss.py,
+    csrc/spectral_loss.hip); absent section = off, and not printed by ``asINI``.  ``weight`` (required, > 0: there is no
+    reference default to inherit) multiplies ``L_spec``, the mean over samples, levels and wavenumber bins of
+    log^2((e_sr + floor) / (e_hr + floor)); ``window``: ``hann`` or ``none``, the taper of the detrended planes;
+    ``k_min`` >= 1 (bin 0 is empty after the detrend, bar rounding) and ``k_max`` (0: the last bin; else
+    k_min <= k_max < NK of the training patch, checked at the first batch) select the bins; ``rel_floor`` >= 0: the floor
+    is that fraction of the level's total e_hr."""
+
+    present: bool = False
+    weight: float = None
+    window: str = "hann"
+    k_min: int = 1
+    k_max: int = 0
+    rel_floor: float = 1e-6
+    _schema = (("weight", _F), ("window", None), ("k_min", _I), ("k_max", _I), ("rel_floor", _F))
+
+    def setSpectralLossConfig(self, section):
+        """``section`` None (no [SPECTRAL_LOSS] in the file) restores the defaults and switches the section off."""
+        self.present = section is not None
+        for key, kind in self._schema:
+            if kind is None:
+                raw = None if section is None else section.get(key)
+                val = None if raw is None else raw.strip().lower()
+            else:
+                try:
+                    val = None if section is None else _read(section, key, kind)
+                except ValueError:
+                    raise ValueError(f"[SPECTRAL_LOSS] {key} must be {'an integer' if kind == _I else 'a number'}, not "
+                                     f"{section.get(key)!r}") from None
+            setattr(self, key, getattr(SpectralLossConfig, key) if val is None else val)
+
+    def validate(self) -> None:
+        if not self.present:
+            return
+        if self.weight is None:
+            raise ValueError("[SPECTRAL_LOSS] weight is required: the weight of the spectral term in the generator loss")
+        if not (self.weight > 0 and math.isfinite(self.weight)):
+            raise ValueError(f"[SPECTRAL_LOSS] weight must be a finite number > 0, not {self.weight}")
+        if self.window not in ("hann", "none"):
+            raise ValueError(f"[SPECTRAL_LOSS] window must be hann or none, not {self.window!r}")
+        if self.k_min < 1:
+            raise ValueError(f"[SPECTRAL_LOSS] k_min must be >= 1, not {self.k_min}")
+        if self.k_max != 0 and self.k_max < self.k_min:
+            raise ValueError(f"[SPECTRAL_LOSS] k_max must be 0 (the last bin) or >= k_min = {self.k_min}, not {self.k_max}")
+        if not (self.rel_floor >= 0 and math.isfinite(self.rel_floor)):
+            raise ValueError(f"[SPECTRAL_LOSS] rel_floor must be a finite number >= 0, not {self.rel_floor}")
+
+    @property
+    def on(self) -> bool:
+        """the generator loss carries the spectral term"""
+        return bool(self.present)
+
+    def __str__(self) -> str:
+        return "[SPECTRAL_LOSS]\n" + "".join(f"{k} = {getattr(self, k)}\n" for k, _ in self._schema)
+
+
 class Config(IniConfig):
     name: str = "default_name"
     model: str = "default_model"
@@ -580,6 +640,7 @@ class Config(IniConfig):
     tile: TileConfig = TileConfig()
     diagnostics: DiagnosticsConfig = DiagnosticsConfig()
     spectrum: SpectrumConfig = SpectrumConfig()
+    spectral_loss: SpectralLossConfig = SpectralLossConfig()
     compute_dtype: str = "fp32"
     is_train: bool
     is_use: bool
@@ -620,6 +681,8 @@ class Config(IniConfig):
         self.diagnostics.validate()
         self.spectrum.setSpectrumConfig(parser["SPECTRUM"] if parser.has_section("SPECTRUM") else None)
         self.spectrum.validate()
+        self.spectral_loss.setSpectralLossConfig(parser["SPECTRAL_LOSS"] if parser.has_section("SPECTRAL_LOSS") else None)
+        self.spectral_loss.validate()
 
     def setBaseConfig(self, base):
         self.name = base.get("name")
@@ -661,4 +724,6 @@ class Config(IniConfig):
             out += "\n" + str(self.diagnostics)
         if getattr(self.spectrum, "present", False):
             out += "\n" + str(self.spectrum)
+        if getattr(self.spectral_loss, "present", False):
+            out += "\n" + str(self.spectral_loss)
         return out

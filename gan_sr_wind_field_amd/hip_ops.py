@@ -1343,3 +1343,68 @@ def level_spectra(HR: Tensor, SR: Tensor, TL: Tensor, window: str = "hann", out:
     check(L.wsr_level_spectra(_p(HR), HR.shape[1], _p(SR), SR.shape[1], _p(TL), TL.shape[1], B, X, Y, NZ,
                               SPECTRUM_WINDOWS[window], _p(ws), _p(out), _stream()), "level_spectra")
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# energy-spectrum loss of generator training ([SPECTRAL_LOSS]; csrc/spectral_loss.hip)
+# ---------------------------------------------------------------------------------------------------------------------
+class _SpectralEnergy(torch.autograd.Function):
+    """``wsr_spectral_energy`` with ``wsr_spectral_energy_bwd`` as backward: E (B, NZ, NK, 2) = [e_hr, e_sr]; only e_sr
+    carries gradient, and only towards SR.  F_sr is saved by the forward's column pass only when SR requires grad."""
+
+    @staticmethod
+    def forward(ctx, hr: Tensor, sr: Tensor, window: int):
+        B, _, X, Y, NZ = sr.shape
+        L = _lib.lib()
+        NK = int(L.wsr_level_spectra_bins(X, Y))
+        out = torch.empty((B, NZ, NK, 2), dtype=torch.float64, device=sr.device)
+        ws = torch.empty(int(L.wsr_spectral_energy_workspace_floats(B, X, Y, NZ)), dtype=torch.float32, device=sr.device)
+        saved = None
+        if ctx.needs_input_grad[1]:
+            saved = torch.empty(int(L.wsr_spectral_energy_saved_floats(B, X, Y, NZ)), dtype=torch.float32, device=sr.device)
+        check(L.wsr_spectral_energy(_p(hr), hr.shape[1], _p(sr), sr.shape[1], B, X, Y, NZ, window, _p(ws), _p(saved),
+                                    _p(out), _stream()), "spectral_energy")
+        ctx.meta = (tuple(sr.shape), window)
+        ctx.save_for_backward(saved)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable  # (the kernel's result is no graph: a double backward is refused)
+    def backward(ctx, g: Tensor):
+        (saved,) = ctx.saved_tensors
+        if saved is None or not ctx.needs_input_grad[1]:
+            return None, None, None
+        (B, C_, X, Y, NZ), window = ctx.meta
+        L = _lib.lib()
+        gbin = g[..., 1].to(torch.float64).contiguous()
+        ws = torch.empty(int(L.wsr_spectral_energy_workspace_floats(B, X, Y, NZ)), dtype=torch.float32, device=g.device)
+        dsr = torch.empty((B, 3, X, Y, NZ), dtype=torch.float32, device=g.device)
+        check(L.wsr_spectral_energy_bwd(_p(saved), _p(gbin), B, X, Y, NZ, window, _p(ws), _p(dsr), _stream()),
+              "spectral_energy_bwd")
+        if C_ > 3:  # (surplus channels are never read: their gradient is zero)
+            full = torch.zeros((B, C_, X, Y, NZ), dtype=torch.float32, device=g.device)
+            full[:, :3] = dsr
+            dsr = full
+        return None, dsr, None
+
+
+def spectral_energy(HR: Tensor, SR: Tensor, window: str = "hann") -> Tensor:
+    """The binned horizontal kinetic-energy spectra of ``HR`` and ``SR`` (B, C >= 3, X, Y, NZ; channels 0..2 are read,
+    surplus ones never) -> float64 (B, NZ, NK, 2) = [e_hr, e_sr], the first two sums of ``level_spectra`` with the same
+    arithmetic (``wsr_spectral_energy``).  Differentiable: only e_sr carries gradient, and only towards SR
+    (``wsr_spectral_energy_bwd``: the inverse transform of the binned upstream gradient times the saved F_sr, minus its
+    plane mean).  No atomics: the same bits on every call, forward and backward."""
+    _need_cuda(HR, SR)
+    for name, t in (("HR", HR), ("SR", SR)):
+        if t.dim() != 5 or t.shape[1] < 3 or t.numel() == 0 or not t.is_floating_point():
+            raise ValueError(f"spectral_energy wants {name} as a floating-point (B, C >= 3, X, Y, NZ) tensor, got "
+                             f"{t.dtype} {tuple(t.shape)}")
+    B, _, X, Y, NZ = HR.shape
+    if (SR.shape[0],) + tuple(SR.shape[2:]) != (B, X, Y, NZ):
+        raise ValueError(f"spectral_energy: SR {tuple(SR.shape)} does not match HR {tuple(HR.shape)}")
+    if window not in SPECTRUM_WINDOWS:
+        raise ValueError(f"spectral_energy: window must be one of {tuple(SPECTRUM_WINDOWS)} (codes 0, 1), not {window!r}")
+    if X > SPECTRUM_MAX_XY or Y > SPECTRUM_MAX_XY or B > 65535 or NZ > 65535 or X * Y * NZ >= 2 ** 31:
+        raise ValueError(f"spectral_energy: at most {SPECTRUM_MAX_XY} points in x and y, 65535 samples, 65535 levels and "
+                         f"2^31 - 1 voxels per sample, not B = {B}, X = {X}, Y = {Y}, NZ = {NZ}")
+    return _SpectralEnergy.apply(HR.detach().contiguous().float(), SR.contiguous().float(), SPECTRUM_WINDOWS[window])

@@ -677,6 +677,33 @@ int wsr_level_spectra(const float* hr, int32_t hr_c, const float* sr, int32_t sr
                       int32_t B, int32_t X, int32_t Y, int32_t NZ, int32_t window, float* workspace, double* out,
                       void* stream);
 
+/* ---- energy-spectrum loss of generator training ([SPECTRAL_LOSS]; csrc/spectral_loss.hip) -------------------
+ * Everything of wsr_level_spectra above carries over unchanged: g = (f - m) w, F(kx, ky) for ky = 0 .. Y / 2, the Hermitian
+ * weight h, the integer-decided bin, NK = wsr_level_spectra_bins(X, Y), scale = 1 / (2 X Y W2) and
+ *    e_a(b, z, k) = scale * sum_comp sum_{modes in k} h |F_a|^2.
+ * wsr_spectral_energy: out (B, NZ, NK, 2) doubles = [e_hr, e_sr] from channels 0..2 of hr (B, hr_c, X, Y, NZ) and
+ * sr (B, sr_c, ...), fp32 planar (surplus channels are never read): the passes of wsr_level_spectra over six planes, the
+ * same arithmetic, so sr = hr gives e_sr = e_hr bit for bit.  saved, when not null: the column pass also writes
+ * F_sr (B, 3, X, Y / 2 + 1, NZ) complex fp32 (wsr_spectral_energy_saved_floats(B, X, Y, NZ) floats, 8-byte aligned), the
+ * operand of the backward.
+ * wsr_spectral_energy_bwd: the vector-Jacobian product of e_sr towards sr.  gbin (B, NZ, NK) doubles = dL/de_sr with the
+ * upstream gradient applied, rounded to fp32 once, G below; dsr (B, 3, X, Y, NZ) fp32 planar, every element written:
+ *    C(x, ky) = sum_kx G(bin(kx, ky)) F_sr(kx, ky) exp(+2 pi i kx x / X)
+ *    u(x, y)  = sum_{ky = 0 .. Y / 2} h(ky) Re( C(x, ky) exp(+2 pi i ky y / Y) )
+ *    v        = 2 scale w u,            dsr = v - mean_plane(v)        (the last term: the adjoint of the detrend)
+ * fp32 transforms as in the forward, the plane sums of v as fp32 partial rows added in double.  No atomics, evaluated
+ * without contraction: the same bits on every call.
+ * workspace: wsr_spectral_energy_workspace_floats(B, X, Y, NZ) floats (0 for sizes the entries refuse), 16-byte aligned,
+ * enough for either entry; nothing in it is carried from the forward to the backward.
+ * A null pointer (saved of the forward apart), a channel count < 3, a non-positive size or an unknown window: WSR_EINVAL;
+ * X or Y > 1024, B > 65535, NZ > 65535 or X * Y * NZ >= 2^31: WSR_EUNSUPPORTED; nothing is written in either case. */
+int64_t wsr_spectral_energy_workspace_floats(int32_t B, int32_t X, int32_t Y, int32_t NZ);
+int64_t wsr_spectral_energy_saved_floats(int32_t B, int32_t X, int32_t Y, int32_t NZ);
+int wsr_spectral_energy(const float* hr, int32_t hr_c, const float* sr, int32_t sr_c, int32_t B, int32_t X, int32_t Y,
+                        int32_t NZ, int32_t window, float* workspace, float* saved, double* out, void* stream);
+int wsr_spectral_energy_bwd(const float* saved, const double* gbin, int32_t B, int32_t X, int32_t Y, int32_t NZ,
+                            int32_t window, float* workspace, float* dsr, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
