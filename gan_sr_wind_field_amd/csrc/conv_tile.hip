@@ -370,6 +370,23 @@ extern "C" int wsr_last_tile_plan(int32_t* plan8) {
   return 0;
 }
 
+// The instantiation of that launch - launch_ct's template parameters - and the number of halo-tile launches this thread
+// has made so far: a test compares the count before and after a call to see that the halo-tile kernel served it (and not
+// the streaming 1x1x1, sliding-window or generic kernels) and that the record is its own.
+static thread_local int32_t t_last_inst[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
+void wsr_ct_note_inst(int wm, int wn, int tm, int tn, int tpk, int mask, int f32, int wk, int simple) {
+  const int32_t p[9] = {wm, wn, tm, tn, tpk, mask, f32, wk, simple};
+  for (int i = 0; i < 9; ++i) t_last_inst[i] = p[i];
+  t_last_inst[9] += 1;
+}
+
+extern "C" int wsr_last_tile_instantiation(int32_t* inst10) {
+  if (!inst10) return WSR_EINVAL;
+  for (int i = 0; i < 10; ++i) inst10[i] = t_last_inst[i];
+  return 0;
+}
+
 int wsr_ct_splitk_reduce(const CtArgs& a, hipStream_t st) {
   const long nvox = (long)a.B * a.Xo * a.Yo * a.Zo;
   const long total = nvox * (a.Cout >> 2);
@@ -465,7 +482,10 @@ static int run_conv_tile(CtArgs& a, int red, hipStream_t st) {
               (!a.res || (a.res_ctot % 4 == 0 && a.res_off % 4 == 0)))
                  ? 1
                  : 0;
-  if (a.act == 2 && !(a.vec_ok && (a.Cout & 3) == 0)) return WSR_EUNSUPPORTED;  // vector epilogue only
+  // act == 2 lives in the vector epilogue only, and without a mask: with a mask window that does not end on a 4-channel
+  // group the kernel leaves the vector epilogue (conv_tile_impl.h `fast`) and the scalar path would activate first and
+  // add the residual afterwards; with an aligned one the act == 2 branch stores before the mask is applied
+  if (a.act == 2 && (!(a.vec_ok && (a.Cout & 3) == 0) || a.mask_y)) return WSR_EUNSUPPORTED;
   // (a.ws / a.ws_bytes: the split-reduction workspace of THIS call, set by the entry points from their arguments)
   if (a.ws_bytes < 0 || (a.ws == nullptr) != (a.ws_bytes == 0)) return WSR_EINVAL;
   if (a.act_c1 != 0x7FFFFFFF && (a.act_c1 & 3)) return WSR_EINVAL;

@@ -113,6 +113,9 @@ int wsr_ct_splitk_reduce(const CtArgs& a, hipStream_t st);
 // Diagnostic: records the plan of the launch that follows for wsr_last_tile_plan (conv_tile.hip: a thread-local copy of
 // eight integers).  Write-only as far as the library goes - no launch decision may read it back.
 void wsr_ct_note_plan(const CtArgs& a, int ntw);
+// ... and which instantiation serves it, for wsr_last_tile_instantiation: launch_ct's template parameters (T as 0 / 1) and
+// a per-thread count of the launches made.  Write-only in the same sense.
+void wsr_ct_note_inst(int wm, int wn, int tm, int tn, int tpk, int mask, int f32, int wk, int simple);
 
 namespace {
 
@@ -939,6 +942,7 @@ int launch_ct(CtArgs& a, hipStream_t st) {
     }
   }
   wsr_ct_note_plan(a, NTW);
+  wsr_ct_note_inst(WM, WN, TM, TN, TPK, MASK ? 1 : 0, std::is_same<T, F32>::value ? 1 : 0, WK, SIMPLE);
   hipLaunchKernelGGL(kern, dim3((unsigned)(wg * a.ksplit)), dim3(WAVES * 64), lds, st, a);
   WSR_LAUNCH_CHECK();
   if (a.ksplit > 1) return wsr_ct_splitk_reduce(a, st);

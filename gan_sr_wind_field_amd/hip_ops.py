@@ -237,6 +237,19 @@ def last_tile_plan() -> dict:
     return dict(zip(TILE_PLAN_FIELDS, (int(v) for v in buf)))
 
 
+TILE_INST_FIELDS = ("WM", "WN", "TM", "TN", "TPK", "MASK", "F32", "WK", "SIMPLE", "seq")
+
+
+def last_tile_instantiation() -> dict:
+    """Diagnostic: which ``launch_ct<WM, WN, TM, TN, TPK, MASK, T, WK, SIMPLE>`` made this thread's most recent halo-tile
+    launch (``wsr_last_tile_instantiation``; ``F32`` = 1 for T = F32), and ``seq``, the number of such launches the thread
+    has made.  ``seq`` stands still across a call that was declined or served by the streaming 1x1x1, sliding-window or
+    generic kernels.  For tests only, like :func:`last_tile_plan`."""
+    buf = (C.c_int32 * len(TILE_INST_FIELDS))()
+    check(_lib.lib().wsr_last_tile_instantiation(buf), "last_tile_instantiation")
+    return dict(zip(TILE_INST_FIELDS, (int(v) for v in buf)))
+
+
 def conv1x1_covers(red: int, n_out: int, masked: bool) -> bool:
     """shapes the streaming 1x1x1 kernel is instantiated for (conv_1x1_v2.hip, ``wsr_conv1x1_bf16``): reduction
     channels x produced channels.  Only that kernel may run a 1x1x1 input gradient in place."""

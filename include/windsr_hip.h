@@ -222,6 +222,13 @@ int wsr_conv3d_dgrad_tile(const wsr_conv_t* c, const void* dy, const void* wfrag
  * kernel (streaming 1x1x1, sliding-window), leaves the record as it was.  For tests that assert which instantiation a
  * case reached: no launch of the library reads the record.  Returns 0, WSR_EINVAL for a null pointer.           */
 int wsr_last_tile_plan(int32_t* plan8);
+/* Diagnostic (additive export): which instantiation of the halo-tile kernel served that launch, as 10 values
+ * {WM, WN, TM, TN, TPK, MASK, F32, WK, SIMPLE, seq}: wave rows and columns of a workgroup, 16-row m-tiles and 16-channel
+ * n-tiles per wave, taps per K-step, LeakyReLU-backward mask compiled in, fp32 operands, waves that share the K-steps of a
+ * stage, the form with the general run-time switches folded away; `seq` counts the calling thread's halo-tile launches (a
+ * split-reduction launch counts once).  Same rules as wsr_last_tile_plan: a declined call or one served by another kernel
+ * changes nothing, no launch reads the record.  Returns 0, WSR_EINVAL for a null pointer.                       */
+int wsr_last_tile_instantiation(int32_t* inst10);
 /* ABI 6: `dtype` (wsr_dtype) of the fragment filter - bf16, or fp32 for the fp32 tile kernels (stride-1 convs in the
  * reference's own arithmetic; the 16-byte pieces then hold 4 channels instead of 8).                        */
 int64_t wsr_frag_filter_elems(int32_t rows, int32_t red, int32_t taps, int32_t dtype);

@@ -48,6 +48,15 @@ product are two more fp32 roundings of terms that A already contains, which is w
 and accumulating forms still store each element once - the accumulated values are read as exact bf16 operands, like
 any residual - so rho is paid once, on |ref|.
 
+The stride-1 halo-tile kernel (``ref_fwd`` / ``ref_dgrad`` with their further forms; K = taps * reduction channels) adds
+to K: ``WK`` where WK > 1 waves share the K-steps of a stage and their partial sums meet in LDS (WK - 1 more fp32
+additions of partial sums, each at most A), ``ksplit`` where the reduction is split over workgroups, and 1 where a
+residual joins the sum in front of the activation (``act2``) or an accumulated value comes from another tensor with its
+own weight (``acc_src`` / ``acc_beta``): one more product and one more addition of a term A already holds.  The mask
+and channel-scale factors are exact selections or single roundings inside the lambda term.  An accumulate that reads
+back a value the kernel itself stored earlier pays rho for it through ``rho_mag``; one that reads a test operand (exact
+in bf16, like any residual) does not.
+
 A kernel bug that drops one tap at one voxel, loses one split or misplaces one channel chunk changes the elements it
 touches by a sizable fraction of A / sqrt(K), far above the bound; a whole-tensor relative L2 check averages such an
 error over every element and can miss it.
@@ -108,12 +117,48 @@ def _conv_slab(x, w, pad, xs, stride=(1, 1, 1)):
     return F.conv3d(xp[:, :, xs[0] * stride[0]:(xs[1] - 1) * stride[0] + kx], w, None, stride, 0)
 
 
+def _lrelu_mask(mask_y, slope):
+    """(y > 0 ? 1 : slope) of a saved output in float64: -0.0, +0.0 and every negative value take ``slope``, every
+    positive value - subnormals included - takes 1"""
+    return torch.where(_d(mask_y) > 0, 1.0, float(slope)).to(torch.float64)
+
+
+def _apply_mask(v, a, mask_y, mask_win, mask_slope):
+    """columns ``mask_win`` = [c0, c1) (default: all) of v and a times ``_lrelu_mask(mask_y)``; mask_y has c1 - c0
+    channels"""
+    m = _lrelu_mask(mask_y, mask_slope)
+    c0, c1 = (0, v.shape[1]) if mask_win is None else mask_win
+    assert 0 <= c0 < c1 <= v.shape[1] and m.shape == v[:, c0:c1].shape, (tuple(m.shape), tuple(v.shape), mask_win)
+    v, a = v.clone(), a.clone()
+    v[:, c0:c1] *= m
+    a[:, c0:c1] *= m.abs()
+    return v, a
+
+
 def ref_fwd(x, w, pad, *, ups=False, bias=None, act=False, slope=0.2, chan_scale=None, alpha=1.0, res=None, beta=0.0,
-            in_win=None, xs=None, stride=(1, 1, 1)):
+            in_win=None, xs=None, stride=(1, 1, 1), act_c1=None, act2=False, mask_y=None, mask_win=None,
+            mask_slope=0.2):
     """y = alpha * s * lrelu(conv(up?(x), w) + bias) + beta * res  (the forward epilogue order of ``wsr_epilogue_t``).
     ``in_win`` = (off, C): channels of x that enter; ``chan_scale`` (B, Cout); ``xs``: output x-planes [x0, x1) only
     (``res`` then covers those planes); ``stride``: the conv's output stride (the discriminator's down-sampling convs).
-    Returns (ref, A)."""
+
+    The halo-tile kernel's further forms (its epilogue, conv_tile_impl.h :679-713, in the kernel's own order
+    ``(acc + bias) -> act -> * (chan_scale * alpha) -> + beta * res -> * mask``):
+
+    * ``act_c1``: bias and LeakyReLU on produced channels below ``act_c1`` only, raw conv sums on the rest (the first
+      stage of a split dense-block conv);
+    * ``act2=True`` (``wsr_epilogue_t.act = 2``, the second stage): the residual joins BEFORE the activation,
+      ``alpha * s * lrelu(conv + bias + beta * res)`` below ``act_c1`` and ``alpha * s * (conv + beta * res)`` from
+      ``act_c1`` on (:679-690);
+    * ``mask_y`` / ``mask_win`` = (c0, c1) / ``mask_slope``: the forward-form LeakyReLU-backward mask
+      (``wsr_epilogue_t.mask``), applied last: channels [c0, c1) times (mask_y > 0 ? 1 : mask_slope), ``mask_y`` holding
+      c1 - c0 channels.
+
+    With none of the three given the result is what it always was, bit for bit.  Returns (ref, A)."""
+    if act_c1 is not None or act2 or mask_y is not None:
+        return _ref_fwd_forms(x, w, pad, ups=ups, bias=bias, act=act, slope=slope, chan_scale=chan_scale, alpha=alpha,
+                              res=res, beta=beta, in_win=in_win, xs=xs, stride=stride, act_c1=act_c1, act2=act2,
+                              mask_y=mask_y, mask_win=mask_win, mask_slope=mask_slope)
     x, w = _win(_d(x), in_win), _d(w)
     if ups:
         x = up2(x)
@@ -134,21 +179,90 @@ def ref_fwd(x, w, pad, *, ups=False, bias=None, act=False, slope=0.2, chan_scale
     return v, a
 
 
+def _ref_fwd_forms(x, w, pad, *, ups, bias, act, slope, chan_scale, alpha, res, beta, in_win, xs, stride, act_c1, act2,
+                   mask_y, mask_win, mask_slope):
+    """``ref_fwd`` with ``act_c1`` / ``act2`` / a forward-form mask, step by step in the kernel's order"""
+    x, w = _win(_d(x), in_win), _d(w)
+    if ups:
+        x = up2(x)
+    v = _conv_slab(x, w, pad, xs, stride)
+    a = _conv_slab(x.abs(), w.abs(), pad, xs, stride)
+    n = v.shape[1]
+    c1 = n if act_c1 is None else min(int(act_c1), n)
+    if bias is not None:  # (acc + bias): the bias table holds zeros from act_c1 on
+        b = _d(bias).clone().view(1, -1, 1, 1, 1)
+        b[:, c1:] = 0.0
+        v, a = v + b, a + b.abs()
+    r = None if res is None else _d(res)
+    if act2:  # the residual joins in front of the activation
+        assert r is not None, "act2 needs the partial sums in res"
+        v, a = v + beta * r, a + abs(beta) * r.abs()
+    if act or act2:
+        v = torch.cat([F.leaky_relu(v[:, :c1], slope), v[:, c1:]], dim=1)
+    if chan_scale is not None:
+        s = _d(chan_scale).view(v.shape[0], n, 1, 1, 1)
+        v, a = v * s, a * s.abs()
+    v, a = alpha * v, abs(alpha) * a
+    if r is not None and not act2:
+        v, a = v + beta * r, a + abs(beta) * r.abs()
+    if mask_y is not None:
+        v, a = _apply_mask(v, a, mask_y, mask_win, mask_slope)
+    return v, a
+
+
 def dgrad_filter(w):
     """(Cout, Cin, KX, KY, KZ) -> the filter of the input gradient as a forward conv over dy: (Cin, Cout, flipped)"""
     return w.transpose(0, 1).flip(2, 3, 4)
 
 
-def ref_dgrad(gy, w, pad, *, ups=False, alpha=1.0, mask_y=None, slope=0.2, keep=None, acc=None, xs=None):
+def ref_dgrad(gy, w, pad, *, ups=False, alpha=1.0, mask_y=None, slope=0.2, keep=None, acc=None, xs=None, acc_c1=None,
+              acc_beta=1.0, mask_win=None):
     """dx = (alpha * conv^T(gy, w) [+ acc]) * lrelu'(mask_y) * keep  for a stride-1 conv with padding ``pad``.
     ``ups``: the conv read up2(x) - dx is then at x's (coarse) resolution, the 2 x 2 fold of the fine gradient;
     ``mask_y`` (B, Cin, ...) the saved output whose sign selects 1 or ``slope``, ``keep`` (B, Cin) the Dropout3d
     channel scale; ``acc`` a value added before the mask (accumulate launches); ``xs`` dx x-planes [x0, x1) only
-    (not with ``ups``).  Returns (ref, A)."""
+    (not with ``ups``).
+
+    The halo-tile kernel's epilogue (conv_tile_impl.h :692-713) runs
+    ``(acc + bias) -> act -> * (chan_scale * alpha) -> + beta * res -> * mask``, which for the input gradient - no bias,
+    no activation, chan_scale = ``keep``, res = the accumulated tensor - is
+
+        dx = (keep * alpha * conv^T(gy, w) + acc_beta * acc[below acc_c1]) * lrelu'(mask_y)[mask window].
+
+    The line at the top multiplies ``keep`` after the mask instead; without ``acc`` that is the same product in another
+    order, and every caller from before these forms gets the result it always got, bit for bit.  With any of the
+    following given, the reference takes the kernel's order literally:
+
+    * ``acc_c1`` (``accumulate = n``): only produced channels below ``acc_c1`` accumulate;
+    * ``acc_beta`` (``wsr_dgrad_opts_t.acc_beta``): the weight of the accumulated value;
+    * ``mask_win`` = (c0, c1): the mask covers produced channels [c0, c1) only, ``mask_y`` holding c1 - c0 channels
+      (``mask_win=(0, Cin)`` with a whole-width ``mask_y`` is the production form, in the kernel's order).
+
+    ``keep`` with ``acc`` is refused there: the kernel scales the fresh sums only, the generic route (conv_dgrad +
+    lrelu_bwd_) scales the accumulated value as well, and no caller combines them.  Returns (ref, A)."""
     gy, w = _d(gy), _d(w)
     k = w.shape[2:]
     tp = tuple(kk - 1 - p for kk, p in zip(k, pad))
     wt = dgrad_filter(w)
+    if acc_c1 is not None or acc_beta != 1.0 or mask_win is not None:
+        assert keep is None or acc is None, "keep together with an accumulate: the routes disagree, see the docstring"
+        v, a = _conv_slab(gy, wt, tp, xs), _conv_slab(gy.abs(), wt.abs(), tp, xs)
+        if ups:
+            v, a = fold2(v), fold2(a)
+        if keep is not None:  # (chan_scale * alpha), one factor per sample and channel
+            s = _d(keep).view(v.shape[0], v.shape[1], 1, 1, 1) * alpha
+            v, a = v * s, a * s.abs()
+        else:
+            v, a = alpha * v, abs(alpha) * a
+        if acc is not None:
+            c1 = v.shape[1] if acc_c1 is None else min(int(acc_c1), v.shape[1])
+            r = _d(acc)[:, :c1]
+            v, a = v.clone(), a.clone()
+            v[:, :c1] += acc_beta * r
+            a[:, :c1] += abs(acc_beta) * r.abs()
+        if mask_y is not None:
+            v, a = _apply_mask(v, a, mask_y, mask_win, slope)
+        return v, a
     v = alpha * _conv_slab(gy, wt, tp, xs)
     a = abs(alpha) * _conv_slab(gy.abs(), wt.abs(), tp, xs)
     if ups:

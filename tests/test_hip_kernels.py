@@ -805,35 +805,71 @@ def test_conv_tile_kernels_vs_golden(golden, hip, case, dt):
     kb.assert_within(dxp.cpu(), r64, kb.bound(r64, A, taps * cout, 0.0), f"tile dgrad planar[golden {name} {dt_name(dt)}]")
 
 
+# Which launch_ct<WM, WN, TM, TN, TPK, MASK, F32, WK, SIMPLE> serves the forward / the input gradient of each case below
+# (asserted through hip_ops.last_tile_instantiation(); None: another kernel).  These volumes are small, so with nothing
+# forced they take the 128-voxel tiles of conv_tile_small.hip; the SIMPLE forms step aside wherever the call's workspace
+# might split the reduction (<= 128 workgroups and >= 4 chunks, conv_tile_impl.h launch_ct).
+SHAPES_WITNESS = {
+    "rdb_n32": ((2, 1, 4, 2, 2, 0, 0, 4, 0), (2, 2, 4, 2, 2, 0, 0, 2, 1)),
+    "hr0_n144": ((2, 2, 4, 2, 2, 0, 0, 2, 0), (2, 2, 4, 2, 2, 0, 0, 2, 0)),
+    "up_n128": ((2, 2, 4, 2, 2, 0, 0, 2, 0), (2, 2, 4, 2, 2, 0, 0, 2, 0)),
+    "lff_1x1": (None, None),
+    "dg_n224": ((2, 2, 4, 2, 2, 0, 0, 2, 1), (2, 1, 4, 2, 2, 0, 0, 4, 0)),
+    "n64_c24": ((4, 1, 4, 4, 4, 0, 0, 1, 0), (2, 1, 4, 2, 2, 0, 0, 4, 0)),
+    "n3_k5": ((2, 1, 4, 2, 2, 0, 0, 4, 0), (4, 2, 4, 5, 4, 0, 0, 1, 0)),
+}
+
+
 @pytest.mark.parametrize("name,cin,cout,k,xyz,B,ups", [
-    ("rdb_n32", 160, 32, (3, 3, 3), (9, 10, 19), 1, False),    # <4,1,8,2>: 512-row tiles, ragged in x/y/z
-    ("hr0_n144", 144, 144, (5, 5, 5), (9, 7, 10), 1, False),   # <8,1,4,9>, TPK=2 with an odd tap count (125)
-    ("up_n128", 128, 128, (3, 3, 3), (5, 6, 8), 1, True),      # nearest x(2,2,1) folded into the halo load
-    ("lff_1x1", 256, 128, (1, 1, 1), (7, 9, 11), 2, False),    # TPK=1 (32-channel K-steps)
-    ("dg_n224", 32, 224, (3, 3, 3), (6, 9, 17), 1, False),     # <4,2,4,7>: two n-tile wave columns
-    ("n64_c24", 24, 64, (3, 3, 3), (8, 5, 6), 2, False),       # TPK=4 (24 channels), N=64
-    ("n3_k5", 144, 3, (5, 5, 5), (8, 8, 10), 1, False),        # N=3 (one 16-tile), planar-style narrow output
+    ("rdb_n32", 160, 32, (3, 3, 3), (9, 10, 19), 1, False),    # <2,1,4,2> with four K-step shares; dgrad <2,2,4,2>, two
+    ("hr0_n144", 144, 144, (5, 5, 5), (9, 7, 10), 1, False),   # <2,2,4,2>, two shares: TPK=2 with an odd tap count (125)
+    ("up_n128", 128, 128, (3, 3, 3), (5, 6, 8), 1, True),      # nearest x(2,2,1) folded into the halo load, <2,2,4,2>
+    ("lff_1x1", 256, 128, (1, 1, 1), (7, 9, 11), 2, False),    # 256 <-> 128: the streaming 1x1x1 kernel, not the tile one
+    ("dg_n224", 32, 224, (3, 3, 3), (6, 9, 17), 1, False),     # <2,2,4,2>: 224 outputs as four 64-channel groups
+    ("n64_c24", 24, 64, (3, 3, 3), (8, 5, 6), 2, False),       # TPK=4 (24 channels), N=64: <4,1,4,4,4>
+    ("n3_k5", 144, 3, (5, 5, 5), (8, 8, 10), 1, False),        # N=3 (one 16-tile); dgrad <4,2,4,5> with TPK=4 (8 channels)
 ])
 def test_conv_tile_shapes_vs_cpu(hip, name, cin, cout, k, xyz, B, ups):
-    """Every tile-kernel configuration against an fp32 CPU conv of the same bf16-rounded operands,
-    forward and input gradient (with residual epilogue on the forward pass)."""
-    _check_tile_conv(name, cin, cout, k, xyz, B, ups)
+    """Tile-kernel configurations at small volumes against an fp32 CPU conv of the same bf16-rounded operands,
+    forward and input gradient (with residual epilogue on the forward pass).  (Every instantiation, the 512- and
+    256-voxel ones included: test_conv_tile_matrix.py.)"""
+    _check_tile_conv(name, cin, cout, k, xyz, B, ups, want=SHAPES_WITNESS[name])
+
+
+SHAPES_FP32_WITNESS = {  # (as SHAPES_WITNESS: forward, input gradient)
+    "rdb_n32": ((8, 1, 4, 2, 2, 0, 1, 1, 0), (4, 2, 4, 6, 2, 0, 1, 1, 0)),
+    "hr0_n144": ((8, 1, 4, 9, 2, 0, 1, 1, 0), (8, 1, 4, 9, 2, 0, 1, 1, 0)),
+    "up_n128": ((8, 1, 4, 8, 2, 0, 1, 1, 0), (8, 1, 4, 8, 2, 0, 1, 1, 0)),
+    "pre_n128": ((8, 1, 4, 8, 2, 0, 1, 1, 0), (8, 1, 4, 8, 2, 0, 1, 1, 0)),
+    "dg_n224": ((4, 2, 4, 8, 2, 0, 1, 1, 0), (8, 1, 4, 2, 2, 0, 1, 1, 0)),
+    "n64_c20": ((4, 1, 4, 4, 4, 0, 1, 1, 0), (8, 1, 4, 2, 2, 0, 1, 1, 0)),
+    "n15_k551": ((8, 1, 4, 1, 2, 0, 1, 1, 0), (8, 1, 4, 9, 2, 0, 1, 1, 0)),
+    "t0_c4": ((8, 1, 4, 1, 4, 0, 1, 1, 0), (8, 1, 4, 1, 2, 0, 1, 1, 0)),
+}
 
 
 @pytest.mark.parametrize("name,cin,cout,k,xyz,B,ups", [
-    ("rdb_n32", 160, 32, (3, 3, 3), (9, 10, 19), 1, False),    # <8,1,4,2,*,F32>: 20 chunks of 8 channels
+    ("rdb_n32", 160, 32, (3, 3, 3), (9, 10, 19), 1, False),    # <8,1,4,2,2,F32>: 20 chunks of 8 channels; dgrad <4,2,4,6>
     ("hr0_n144", 144, 144, (5, 5, 5), (9, 7, 10), 1, False),   # <8,1,4,9,2,F32>, odd tap count
-    ("up_n128", 128, 128, (3, 3, 3), (5, 6, 8), 1, True),      # nearest x(2,2,1) folded into the halo load
-    ("pre_n128", 128, 128, (3, 3, 3), (8, 16, 16), 1, False),  # production tile 4x8x16
-    ("dg_n224", 32, 224, (3, 3, 3), (6, 9, 17), 1, False),     # <4,2,4,8,2,F32>: two n-tile wave columns
-    ("n64_c20", 20, 64, (3, 3, 3), (8, 5, 6), 2, False),       # TPK=4 (20 channels = 5 pieces), N=64
-    ("n15_k551", 144, 15, (5, 5, 1), (8, 8, 10), 1, False),    # the z-folded last conv: one n-tile, flat tiles
-    ("t0_c4", 4, 16, (3, 3, 3), (8, 8, 16), 1, False),         # 1 / 3 / 4-channel inputs padded to one piece
+    ("up_n128", 128, 128, (3, 3, 3), (5, 6, 8), 1, True),      # nearest x(2,2,1) folded into the halo load, <8,1,4,8>
+    ("pre_n128", 128, 128, (3, 3, 3), (8, 16, 16), 1, False),  # production tile 4x8x16, <8,1,4,8,2,F32>
+    ("dg_n224", 32, 224, (3, 3, 3), (6, 9, 17), 1, False),     # <4,2,4,8,2,F32>: two n-tile wave columns; dgrad <8,1,4,2>
+    ("n64_c20", 20, 64, (3, 3, 3), (8, 5, 6), 2, False),       # TPK=4 (20 channels = 5 pieces), N=64: <4,1,4,4,4>
+    ("n15_k551", 144, 15, (5, 5, 1), (8, 8, 10), 1, False),    # the z-folded last conv: one n-tile, flat tiles; dgrad <8,1,4,9>
+    ("t0_c4", 4, 16, (3, 3, 3), (8, 8, 16), 1, False),         # 1 / 3 / 4-channel inputs padded to one piece: <8,1,4,1,4>
 ])
 def test_conv_tile_shapes_fp32_vs_cpu(hip, name, cin, cout, k, xyz, B, ups):
     """the fp32 instantiations of the halo-tile kernel (ABI 6; the reference's own arithmetic, AMP is commented out in
     Generator_3D_Resnet_ESRGAN.py:65): exact fp32 products and sums - 2e-5 against the fp32 CPU conv."""
-    _check_tile_conv(name, cin, cout, k, xyz, B, ups, dt=torch.float32)
+    _check_tile_conv(name, cin, cout, k, xyz, B, ups, dt=torch.float32, want=SHAPES_FP32_WITNESS[name])
+
+
+THIN_WITNESS = {  # (forward, input gradient)
+    "needle_x": ((8, 1, 3, 2, 2, 0, 0, 1, 1), (8, 1, 3, 2, 2, 0, 0, 1, 1)),
+    "needle_y": ((8, 1, 3, 2, 2, 0, 0, 1, 1), (8, 1, 3, 2, 2, 0, 0, 1, 1)),
+    "thin_slab": ((8, 1, 3, 8, 2, 0, 0, 1, 0), (8, 1, 3, 8, 2, 0, 0, 1, 0)),
+    "k5_needle": ((8, 1, 4, 9, 2, 0, 0, 1, 0), (8, 1, 4, 9, 2, 0, 0, 1, 0)),
+}
 
 
 @pytest.mark.parametrize("name,cin,cout,k,xyz,B,ups", [
@@ -847,36 +883,95 @@ def test_conv_tile_shapes_fp32_vs_cpu(hip, name, cin, cout, k, xyz, B, ups):
 ])
 def test_conv_tile_long_thin_volumes(hip, monkeypatch, name, cin, cout, k, xyz, B, ups):
     """the halo-tile kernels on long thin 10-level volumes (tile coordinates are packed in 8 bits per axis: a needle-shaped
-    tile through such a volume must not wrap them), against the CPU conv; WSR_CT_NOSMALL keeps them on the 512-voxel tiles"""
+    tile through such a volume must not wrap them), against the CPU conv; WSR_CT_NOSMALL keeps them off the 128-voxel
+    tiles.  With so few tiles the 32- and 128-wide launches take the 384-voxel forms (dispatch_ct: one round of
+    workgroups either way), the 144-wide one the 512-voxel tile."""
     monkeypatch.setenv("WSR_CT_NOSMALL", "1")
     reload_wsr_env()
-    _check_tile_conv(name, cin, cout, k, xyz, B, ups)
+    _check_tile_conv(name, cin, cout, k, xyz, B, ups, want=THIN_WITNESS[name])
 
 
-@pytest.mark.parametrize("name,cin,cout,k,xyz,B,ups", [
-    # the tile geometry of the benchmarked 128-level workloads (conv_tile_impl.h pick_tile: 4 x 8 x 16 voxels,
-    # several z tiles); WSR_CT_NOSMALL keeps these small volumes on the kernels the full-size volumes take
+PROD_CASES = [
+    # z extents of several 16-level tiles, as in the benchmarked 128-level workloads; WSR_CT_NOSMALL keeps these small
+    # volumes off the 128-voxel tiles.  A handful of tiles is one round of workgroups on 512- and on 384-voxel tiles alike,
+    # so dispatch_ct moves the 32- and 128-wide launches to the 384-voxel forms (3 < 4), and the workspace the call carries
+    # makes the SIMPLE forms step aside wherever the reduction has >= 4 chunks: the comments name what the witness shows
     ("hr0_prod", 144, 144, (5, 5, 5), (12, 16, 32), 1, False),   # <8,1,4,9>: one activation buffer, 9 chunks
-    ("n128_prod", 128, 128, (3, 3, 3), (8, 16, 32), 1, False),   # <8,1,4,8>: 512-voxel tile, 128 outputs
+    ("n128_prod", 128, 128, (3, 3, 3), (8, 16, 32), 1, False),   # <8,1,3,8>: 384-voxel tile, 128 outputs
     ("pre_prod", 128, 128, (3, 3, 3), (4, 8, 48), 2, False),     # same, batch 2, 3 z tiles
-    ("up_prod", 128, 128, (3, 3, 3), (4, 8, 32), 1, True),       # up-sampling gather on the 512-voxel tile
-    ("grow_prod", 96, 32, (3, 3, 3), (8, 8, 32), 1, False),      # <8,1,4,2>: growth conv over 96 channels
-    ("rdb_prod", 224, 32, (3, 3, 3), (8, 8, 16), 1, False),      # <8,1,4,2>: last growth conv (per-conv form)
-    ("dwin_prod", 32, 128, (3, 3, 3), (8, 8, 32), 1, False),     # input gradient of a growth window: 128 -> 32
-    ("hr1z_prod", 144, 15, (5, 5, 1), (8, 16, 32), 1, False),    # z-folded last conv, <8,1,4,1>
-    ("t1_prod", 16, 16, (3, 3, 3), (8, 16, 32), 1, False),       # terrain conv 16 -> 16
-])
+    ("up_prod", 128, 128, (3, 3, 3), (4, 8, 32), 1, True),       # up-sampling gather on the 512-voxel tile <8,1,4,8>
+    ("grow_prod", 96, 32, (3, 3, 3), (8, 8, 32), 1, False),      # <8,1,3,2>: growth conv over 96 channels
+    ("rdb_prod", 224, 32, (3, 3, 3), (8, 8, 16), 1, False),      # <8,1,3,2>: last growth conv (per-conv form); dgrad <4,2,4,7>
+    ("dwin_prod", 32, 128, (3, 3, 3), (8, 8, 32), 1, False),     # input gradient of a growth window: 128 -> 32, <8,1,3,2>
+    ("hr1z_prod", 144, 15, (5, 5, 1), (8, 16, 32), 1, False),    # z-folded last conv, <8,1,4,1>; dgrad <4,2,4,5>
+    ("t1_prod", 16, 16, (3, 3, 3), (8, 16, 32), 1, False),       # terrain conv 16 -> 16; dgrad: the sliding-window kernel
+]
+PROD_WITNESS = {  # (forward, input gradient) with WSR_CT_NOSMALL and the call's workspace
+    "hr0_prod": ((8, 1, 4, 9, 2, 0, 0, 1, 0), (8, 1, 4, 9, 2, 0, 0, 1, 0)),
+    "n128_prod": ((8, 1, 3, 8, 2, 0, 0, 1, 0), (8, 1, 3, 8, 2, 0, 0, 1, 0)),
+    "pre_prod": ((8, 1, 3, 8, 2, 0, 0, 1, 0), (8, 1, 3, 8, 2, 0, 0, 1, 0)),
+    "up_prod": ((8, 1, 4, 8, 2, 0, 0, 1, 0), (8, 1, 3, 8, 2, 0, 0, 1, 0)),
+    "grow_prod": ((8, 1, 3, 2, 2, 0, 0, 1, 0), (8, 1, 3, 8, 2, 0, 0, 1, 1)),
+    "rdb_prod": ((8, 1, 3, 2, 2, 0, 0, 1, 0), (4, 2, 4, 7, 2, 0, 0, 1, 0)),
+    "dwin_prod": ((8, 1, 3, 8, 2, 0, 0, 1, 1), (8, 1, 3, 2, 2, 0, 0, 1, 0)),
+    "hr1z_prod": ((8, 1, 4, 1, 2, 0, 0, 1, 0), (4, 2, 4, 5, 2, 0, 0, 1, 0)),
+    "t1_prod": ((8, 1, 4, 1, 2, 0, 0, 1, 0), None),
+}
+PROD_WITNESS_512 = {  # ... with WSR_CT_NO_TM3 as well and no workspace: the forms the full-size volumes take
+    "hr0_prod": ((8, 1, 4, 9, 2, 0, 0, 1, 0), (8, 1, 4, 9, 2, 0, 0, 1, 0)),
+    "n128_prod": ((8, 1, 4, 8, 2, 0, 0, 1, 1), (8, 1, 4, 8, 2, 0, 0, 1, 1)),
+    "pre_prod": ((8, 1, 4, 8, 2, 0, 0, 1, 1), (8, 1, 4, 8, 2, 0, 0, 1, 1)),
+    "up_prod": ((8, 1, 4, 8, 2, 0, 0, 1, 0), (8, 1, 4, 8, 2, 0, 0, 1, 1)),
+    "grow_prod": ((8, 1, 4, 2, 2, 0, 0, 1, 1), (8, 1, 4, 8, 2, 0, 0, 1, 1)),
+    "rdb_prod": ((8, 1, 4, 2, 2, 0, 0, 1, 1), (4, 2, 4, 7, 2, 0, 0, 1, 0)),
+    "dwin_prod": ((8, 1, 4, 8, 2, 0, 0, 1, 1), (8, 1, 4, 2, 2, 0, 0, 1, 1)),
+    "hr1z_prod": ((8, 1, 4, 1, 2, 0, 0, 1, 0), (4, 2, 4, 5, 2, 0, 0, 1, 0)),
+    "t1_prod": ((8, 1, 4, 1, 2, 0, 0, 1, 0), None),
+}
+
+
+@pytest.mark.parametrize("name,cin,cout,k,xyz,B,ups", PROD_CASES)
 def test_conv_tile_production_geometry(hip, monkeypatch, name, cin, cout, k, xyz, B, ups):
     monkeypatch.setenv("WSR_CT_NOSMALL", "1")
     reload_wsr_env()
-    _check_tile_conv(name, cin, cout, k, xyz, B, ups)
+    _check_tile_conv(name, cin, cout, k, xyz, B, ups, want=PROD_WITNESS[name])
+
+
+@pytest.mark.parametrize("name,cin,cout,k,xyz,B,ups", PROD_CASES)
+def test_conv_tile_production_geometry_on_512_voxel_tiles(hip, monkeypatch, name, cin, cout, k, xyz, B, ups):
+    """the same cases kept off the 384-voxel tiles too (WSR_CT_NO_TM3) and without a workspace: the 512-voxel SIMPLE forms
+    of conv_tile_simple_narrow.hip / conv_tile_simple_n128.hip, which the full-size volumes take"""
+    monkeypatch.setenv("WSR_CT_NOSMALL", "1")
+    monkeypatch.setenv("WSR_CT_NO_TM3", "1")
+    reload_wsr_env()
+    _check_tile_conv(name, cin, cout, k, xyz, B, ups, want=PROD_WITNESS_512[name], use_ws=False)
 
 
 def dt_name(dt):
     return "bf16" if dt == torch.bfloat16 else "fp32"
 
 
-def _check_tile_conv(name, cin, cout, k, xyz, B, ups, dt=torch.bfloat16):
+def _witnessed(want, label, call):
+    """run ``call`` (one tile entry point) and hold ``hip_ops.last_tile_instantiation()`` to ``want``: the nine template
+    parameters of the launch_ct that served it, with the thread's launch count advanced by one - or, ``want`` None, a
+    count that stood still: the streaming 1x1x1 or sliding-window kernel served the call"""
+    o = ops()
+    seq0 = o.last_tile_instantiation()["seq"]
+    ok = call()
+    w = o.last_tile_instantiation()
+    got = tuple(w[f] for f in o.TILE_INST_FIELDS[:9])
+    print(f"[witness] {label}: {got if w['seq'] != seq0 else None} seq +{w['seq'] - seq0} plan {o.last_tile_plan()}")
+    if want is None:
+        assert w["seq"] == seq0, f"{label}: expected another kernel, the halo-tile kernel ran {got}"
+    else:
+        assert w["seq"] == seq0 + 1, f"{label}: {w['seq'] - seq0} halo-tile launches"
+        assert got == tuple(want), f"{label}: instantiation {got}, expected {tuple(want)}"
+    return ok
+
+
+def _check_tile_conv(name, cin, cout, k, xyz, B, ups, dt=torch.bfloat16, want=None, use_ws=True):
+    """``want`` = (forward, input gradient): the launch_ct<WM, WN, TM, TN, TPK, MASK, F32, WK, SIMPLE> each launch must be
+    served by (None: not the halo-tile kernel)"""
     o = ops()
     tol = 4e-3 if dt == torch.bfloat16 else 2e-5  # (operands are bf16-exact in both: fp32 products are exact)
     gen = torch.Generator().manual_seed(cin * 7 + cout)
@@ -893,7 +988,10 @@ def _check_tile_conv(name, cin, cout, k, xyz, B, ups, dt=torch.bfloat16):
     yg = kb.Guarded((B,) + oxyz + (cout_p + 8,), dt, DEV, window=(0, cout), fill=0.0)
     yb = yg.t
     wm = packed_master(w)
-    assert o.conv_fwd_tile(d, xb, o.pack_filter_frag(wm, dtype=dt), yb, res=rb, res_off=0, alpha=0.2, beta=1.0)
+    wfr = o.pack_filter_frag(wm, dtype=dt)
+    assert want is not None, name
+    assert _witnessed(want[0], f"{name} forward", lambda: o.conv_fwd_tile(d, xb, wfr, yb, res=rb, res_off=0, alpha=0.2,
+                                                                         beta=1.0, use_ws=use_ws))
     xr = x.repeat_interleave(2, dim=2).repeat_interleave(2, dim=3) if ups else x
     ref = 0.2 * F.conv3d(xr, w, None, 1, p) + res
     assert rel_l2(from_ndhwc(yb, 0, cout), ref) < tol, name
@@ -911,7 +1009,8 @@ def _check_tile_conv(name, cin, cout, k, xyz, B, ups, dt=torch.bfloat16):
     dd = o.make_desc(o.ConvGeom(cin, cout_p, k, (1, 1, 1), p, upsample=ups), dt, B, xyz, cin + 8, 8, cout_p + 8, 0)
     dxg = kb.Guarded((B,) + tuple(xr.shape[2:]) + (cin + 8,), dt, DEV, window=(8, cin), fill=0.0)
     dxb = dxg.t
-    assert o.conv_dgrad_tile(dd, gb, o.pack_filter_frag(wm, transpose=True, dtype=dt), dxb)
+    wft = o.pack_filter_frag(wm, transpose=True, dtype=dt)
+    assert _witnessed(want[1], f"{name} input gradient", lambda: o.conv_dgrad_tile(dd, gb, wft, dxb, use_ws=use_ws))
     xg = xr.clone().requires_grad_(True)
     F.conv3d(xg, w, None, 1, p).backward(gy)
     assert rel_l2(from_ndhwc(dxb, 8, cin), xg.grad) < tol, name
@@ -1638,7 +1737,9 @@ def test_lff_filter_gradient_on_ten_level_patches(hip):
 def test_conv_tile_384_voxel_tiles(hip, name, cin, cout, k, xyz, B):
     """conv_tile_tm3.hip: the launches dispatch_ct moves to 384-voxel tiles (fewer rounds x rows than on 512-voxel
     ones) against the fp32 CPU conv of the same bf16 operands - forward with a residual, input gradient."""
-    _check_tile_conv(name, cin, cout, k, xyz, B, False)
+    want = {"tm3_n128": ((8, 1, 3, 8, 2, 0, 0, 1, 1), (8, 1, 3, 8, 2, 0, 0, 1, 1)),
+            "tm3_grow": ((8, 1, 3, 2, 2, 0, 0, 1, 1), (8, 1, 3, 8, 2, 0, 0, 1, 1))}[name]
+    _check_tile_conv(name, cin, cout, k, xyz, B, False, want=want)
 
 
 def test_conv_tile_384_voxel_tiles_masked_window(hip):
@@ -1652,18 +1753,24 @@ def test_conv_tile_384_voxel_tiles_masked_window(hip):
     w = (torch.randn((red, n, 3, 3, 3), generator=gen) / math.sqrt(red * 27)).bfloat16().float()  # (Cout = red, Cin = n)
     acc = torch.randn((B, n) + xyz, generator=gen).bfloat16().float()         # what the window already holds
     ysaved = torch.randn((B, n) + xyz, generator=gen).bfloat16().float()      # saved forward output (sign = mask)
-    buf = torch.zeros((B,) + xyz + (256,), dtype=dt, device=DEV)
-    buf[..., 128:128 + n] = acc.permute(0, 2, 3, 4, 1).to(DEV).to(dt)
+    bufg = kb.Guarded((B,) + xyz + (256,), dt, DEV, window=(128, n), fill=acc.permute(0, 2, 3, 4, 1).to(DEV).to(dt), outside=0.0)
+    buf = bufg.t
     buf[..., 160:160 + red] = gy.permute(0, 2, 3, 4, 1).to(DEV).to(dt)
+    bufg.snap = bufg.base.view(kb._INT_VIEW[dt])[bufg.mask].clone()  # (the gradients it reads are guard elements from here on)
     yb = to_ndhwc(ysaved, 256, 128, dt)
     d = o.make_desc(o.ConvGeom(n, red, (3, 3, 3), (1, 1, 1), (1, 1, 1)), dt, B, xyz, 256, 128, 256, 160)
     wt = o.pack_filter_frag(packed_master(w), transpose=True, dtype=dt)
-    assert o.conv_dgrad_tile(d, buf, wt, buf, alpha=1.0, accumulate=True, mask=(yb, 128, 0, n, 0.2))
+    assert _witnessed((8, 1, 3, 2, 2, 1, 0, 1, 1), "tm3 masked window",
+                      lambda: o.conv_dgrad_tile(d, buf, wt, buf, alpha=1.0, accumulate=True, mask=(yb, 128, 0, n, 0.2)))
     xg = torch.zeros((B, n) + xyz, requires_grad=True)
     F.conv3d(xg, w, None, 1, 1).backward(gy)
     ref = (xg.grad + acc) * torch.where(ysaved > 0, torch.ones_like(ysaved), torch.full_like(ysaved, 0.2))
     assert rel_l2(from_ndhwc(buf, 128, n), ref) < 4e-3
     assert torch.equal(buf[..., 160:160 + red].cpu(), gy.permute(0, 2, 3, 4, 1).to(dt))  # the gradients it read are intact
+    kb.assert_guards_intact(bufg, label="tm3 masked window")
+    # element-wise: the accumulated value is an exact bf16 operand, so rho is paid on the stored result only
+    r64, A = kb.ref_dgrad(gy, w, (1, 1, 1), acc=acc, mask_y=ysaved, slope=kb._f32(0.2), mask_win=(0, n))
+    kb.assert_within(from_ndhwc(buf, 128, n), r64, kb.bound(r64, A, 27 * red, kb.RHO_BF16), "tile dgrad bf16[tm3 masked window]")
 
 
 def test_conv_thin_paired_stores_equal_the_plain_form(hip, monkeypatch):

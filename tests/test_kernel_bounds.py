@@ -453,3 +453,295 @@ def test_stream_stale_tail_is_caught(stream):
     assert s.nvox % 16 == 9
     got[tail:] = s.acc[tail:]  # the last strip's voxels keep the buffer's old contents
     _rejected(s, got, lambda v, c: v >= tail, 9 * 256 * 9 // 10, "stale tail")
+
+
+# ---- the stride-1 halo-tile kernel's further epilogue forms (ref_fwd / ref_dgrad keyword forms) ------------------------
+
+def test_tile_reference_forms_equal_a_direct_composition():
+    """each keyword form of ``ref_fwd`` / ``ref_dgrad`` against float64 autograd and plain torch ops written out here;
+    the defaults still give the earlier result bit for bit"""
+    gen = torch.Generator().manual_seed(23)
+    B, cin, cout, xyz, k, pad = 2, 6, 12, (4, 5, 6), (3, 3, 3), (1, 1, 1)
+    bc = lambda t: t.view(1, -1, 1, 1, 1)
+    x = torch.randn((B, cin) + xyz, generator=gen, dtype=f64).requires_grad_(True)
+    w = torch.randn((cout, cin) + k, generator=gen, dtype=f64)
+    bias = torch.randn(cout, generator=gen, dtype=f64)
+    y = F.conv3d(x, w, None, 1, pad)
+    res = torch.randn(y.shape, generator=gen, dtype=f64)
+    cs = torch.rand((B, cout), generator=gen, dtype=f64).view(B, cout, 1, 1, 1)
+    yd = y.detach()
+    # act_c1: bias + LeakyReLU below it, raw sums from it on; residual after
+    want = torch.cat([F.leaky_relu(yd[:, :4] + bc(bias[:4]), 0.1), yd[:, 4:]], 1) * cs * 0.3 + 0.7 * res
+    got, A = kb.ref_fwd(x, w, pad, bias=bias, act=True, slope=0.1, chan_scale=cs, alpha=0.3, res=res, beta=0.7, act_c1=4)
+    torch.testing.assert_close(got, want, rtol=1e-12, atol=1e-12)
+    assert bool((A >= got.abs() - 1e-12).all())
+    # act2: the residual joins in front of the activation; with act_c1 < Cout the rest is conv + beta * res
+    want = 0.3 * F.leaky_relu(yd + bc(bias) - 0.7 * res, 0.1)
+    got, A = kb.ref_fwd(x, w, pad, bias=bias, slope=0.1, alpha=0.3, res=res, beta=-0.7, act2=True)
+    torch.testing.assert_close(got, want, rtol=1e-12, atol=1e-12)
+    assert bool((A >= got.abs() - 1e-12).all())
+    want = torch.cat([F.leaky_relu(yd[:, :8] + bc(bias[:8]) + res[:, :8], 0.1), yd[:, 8:] + res[:, 8:]], 1)
+    got, _ = kb.ref_fwd(x, w, pad, bias=bias, slope=0.1, res=res, beta=1.0, act2=True, act_c1=8)
+    torch.testing.assert_close(got, want, rtol=1e-12, atol=1e-12)
+    # forward-form mask on a channel window, last
+    h = torch.randn((B, 4) + xyz, generator=gen, dtype=f64)
+    want = F.leaky_relu(yd + bc(bias), 0.1) + 0.5 * res
+    want[:, 4:8] *= torch.where(h > 0, 1.0, 0.25)
+    got, A = kb.ref_fwd(x, w, pad, bias=bias, act=True, slope=0.1, res=res, beta=0.5, mask_y=h, mask_win=(4, 8),
+                        mask_slope=0.25)
+    torch.testing.assert_close(got, want, rtol=1e-12, atol=1e-12)
+    assert bool((A >= got.abs() - 1e-12).all())
+    # input gradient: partial accumulate with its own weight, mask on a sub-window
+    gy = torch.randn(y.shape, generator=gen, dtype=f64)
+    (dx,) = torch.autograd.grad(y, x, gy)
+    acc = torch.randn(dx.shape, generator=gen, dtype=f64)
+    hm = torch.randn((B, 2) + xyz, generator=gen, dtype=f64)
+    want = 0.5 * dx
+    want[:, :4] += 0.3 * acc[:, :4]
+    want[:, 2:4] *= torch.where(hm > 0, 1.0, 0.2)
+    got, A = kb.ref_dgrad(gy, w, pad, alpha=0.5, acc=acc, acc_c1=4, acc_beta=0.3, mask_y=hm, mask_win=(2, 4))
+    torch.testing.assert_close(got, want, rtol=1e-12, atol=1e-12)
+    assert bool((A >= got.abs() - 1e-12).all())
+    # keep together with a mask, in the kernel's order: equal to the earlier order (it commutes without acc)
+    hf = torch.randn(dx.shape, generator=gen, dtype=f64)
+    keep = torch.rand((B, cin), generator=gen, dtype=f64)
+    keep[0, 1] = keep[1, 4] = 0.0
+    got, A = kb.ref_dgrad(gy, w, pad, alpha=0.5, mask_y=hf, keep=keep, mask_win=(0, cin))
+    old, A_old = kb.ref_dgrad(gy, w, pad, alpha=0.5, mask_y=hf, keep=keep)
+    torch.testing.assert_close(got, 0.5 * dx * torch.where(hf > 0, 1.0, 0.2) * keep.view(B, cin, 1, 1, 1), rtol=1e-12, atol=1e-12)
+    torch.testing.assert_close(got, old, rtol=1e-12, atol=1e-12)
+    torch.testing.assert_close(A, A_old, rtol=1e-12, atol=1e-12)
+    with pytest.raises(AssertionError, match="keep together with an accumulate"):
+        kb.ref_dgrad(gy, w, pad, mask_y=hf, keep=keep, acc=acc, mask_win=(0, cin))
+    # the mask's sign convention on the special values
+    sp = torch.tensor([0.0, -0.0, 2.0 ** -133, -2.0 ** -133, 2.0 ** -126, -3e38, 1e-45, -1e-45], dtype=torch.float32)
+    assert kb._lrelu_mask(sp, 0.25).tolist() == [0.25, 0.25, 1.0, 0.25, 1.0, 0.25, 1.0, 0.25]
+
+
+class _TileForms:
+    """the halo-tile epilogue forms on a 3x3x3 conv over (5, 6, 9) voxels, B = 2, with fp32 emulations of the kernel's
+    arithmetic (fp32 conv of the bf16-exact operands, the epilogue of conv_tile_impl.h :679-713 in fp32, one bf16 store)
+    that carry a switch for each mistake a kernel could make.
+
+    fwd1: 16 -> 32, bias + LeakyReLU below act_c1 = 16, channel scale, alpha, residual.   fwd2: the same conv, act = 2.
+    dg1: produced 32 <- reduction 16, accumulate below acc_c1 = 16 with acc_beta = 0.5, mask on [8, 24).
+    dg2: the same gradient with keep (zeros among it) and the mask on all 32 channels."""
+    B, xyz, cin, cout, c1 = 2, (5, 6, 9), 16, 32, 16
+    alpha, beta, slope, acc_beta, mslope = 0.7, 0.3, 0.2, 0.5, 0.2
+    acc_c1, win = 16, (8, 24)
+
+    def __init__(self):
+        gen = torch.Generator().manual_seed(57)
+        B, xyz, cin, cout = self.B, self.xyz, self.cin, self.cout
+        r = lambda *s: _bf(torch.randn(*s, generator=gen))
+        self.x, self.w = r((B, cin) + xyz), _bf(torch.randn((cout, cin, 3, 3, 3), generator=gen) / math.sqrt(27 * cin))
+        self.bias, self.res = r(cout), r((B, cout) + xyz)
+        self.cs = _bf(torch.rand((B, cout), generator=gen) + 0.5)
+        f = kb._f32
+        self.fwd1 = kb.ref_fwd(self.x, self.w, (1, 1, 1), bias=self.bias, act=True, slope=f(self.slope), chan_scale=self.cs,
+                               alpha=f(self.alpha), res=self.res, beta=f(self.beta), act_c1=self.c1)
+        self.fwd2 = kb.ref_fwd(self.x, self.w, (1, 1, 1), bias=self.bias, slope=f(self.slope), alpha=f(self.alpha),
+                               res=self.res, beta=f(self.beta), act2=True, act_c1=self.c1)
+        # input gradient of a conv 32 -> 16: produced channels 32, reduction 16
+        self.gy, self.wd = r((B, cin) + xyz), _bf(torch.randn((cin, cout, 3, 3, 3), generator=gen) / math.sqrt(27 * cin))
+        self.acc = r((B, cout) + xyz)
+        self.y = torch.randn((B, cout) + xyz, generator=gen).bfloat16()
+        self.keep = _bf(torch.rand((B, cout), generator=gen) + 0.5)
+        self.keep[0, 5] = self.keep[1, 20] = self.keep[1, 31] = 0.0
+        plain = F.conv3d(self.gy, kb.dgrad_filter(self.wd), None, 1, 1)
+        # -0.0 and a positive subnormal inside the window [8, 24), where the unmasked value is large
+        m0, m1 = self.win
+        mag = (plain[:, m0:m1] + self.acc_beta * torch.cat([self.acc[:, m0:self.acc_c1],
+                                                            torch.zeros_like(self.acc[:, self.acc_c1:m1])], 1)).abs()
+        i0 = int(mag[0].argmax())
+        i1 = int(mag[1].argmax())
+        self.e0 = (0,) + tuple(int(v) for v in np_unravel(i0, mag[0].shape))
+        self.e1 = (1,) + tuple(int(v) for v in np_unravel(i1, mag[1].shape))
+        self.y[self.e0[0], m0 + self.e0[1], self.e0[2], self.e0[3], self.e0[4]] = _bits(NEG_ZERO)
+        self.y[self.e1[0], m0 + self.e1[1], self.e1[2], self.e1[3], self.e1[4]] = _bits(POS_SUB)
+        self.dg1 = kb.ref_dgrad(self.gy, self.wd, (1, 1, 1), alpha=f(self.alpha), acc=self.acc, acc_c1=self.acc_c1,
+                                acc_beta=f(self.acc_beta), mask_y=self.y[:, m0:m1], slope=f(self.mslope), mask_win=self.win)
+        self.dg2 = kb.ref_dgrad(self.gy, self.wd, (1, 1, 1), alpha=f(self.alpha), mask_y=self.y, slope=f(self.mslope),
+                                keep=self.keep, mask_win=(0, cout))
+
+    def bound(self, form, extra=0):
+        ref, A = getattr(self, form)
+        return kb.bound(ref, A, 27 * self.cin + extra, kb.RHO_BF16)
+
+    def emul_fwd(self, *, act2=False, act_c1=None, bias_c1=None, res_after=False):
+        t = lambda v: torch.tensor(float(v), dtype=torch.float32)
+        bc = lambda v: v.view(1, -1, 1, 1, 1)
+        ac1 = self.c1 if act_c1 is None else act_c1
+        bias = self.bias.clone()
+        bias[self.c1 if bias_c1 is None else bias_c1:] = 0.0
+        v = F.conv3d(self.x, self.w, None, 1, 1) + bc(bias)
+        if act2 and not res_after:
+            v = v + t(self.beta) * self.res
+        v = torch.cat([torch.where(v[:, :ac1] > 0, v[:, :ac1], v[:, :ac1] * t(self.slope)), v[:, ac1:]], 1)
+        if act2:  # (res_after: the join moved behind the activation, everything else as the kernel has it)
+            return _bf((v + t(self.beta) * self.res if res_after else v) * t(self.alpha))
+        v = v * (self.cs.view(self.B, self.cout, 1, 1, 1) * t(self.alpha))
+        return _bf(v + t(self.beta) * self.res)
+
+    def emul_dgrad(self, *, keep=False, no_keep=False, acc_c1=None, win=None, znext=False, flip=()):
+        t = lambda v: torch.tensor(float(v), dtype=torch.float32)
+        v = F.conv3d(self.gy, kb.dgrad_filter(self.wd), None, 1, 1)
+        if keep:
+            scale = torch.ones_like(self.keep) if no_keep else self.keep
+            v = v * (scale.view(self.B, self.cout, 1, 1, 1) * t(self.alpha))
+            m0, m1 = 0, self.cout
+        else:
+            v = v * t(self.alpha)
+            c1 = self.acc_c1 if acc_c1 is None else acc_c1
+            v[:, :c1] += t(self.acc_beta) * self.acc[:, :c1]
+            m0, m1 = self.win if win is None else win
+        # the mask source stays where the caller put it: a kernel that moves its window reads the row at (c - its c0)
+        y0 = 0 if keep else self.win[0]
+        ys = self.y[:, y0:y0 + (m1 - m0)].float()
+        if znext:
+            ys = torch.roll(ys, -1, dims=4)
+        pos = ys > 0
+        for e in flip:
+            pos[e] = ~pos[e]
+        v[:, m0:m1] *= torch.where(pos, torch.ones(()), t(self.mslope))
+        return _bf(v)
+
+    def violations(self, got, form, extra=0):
+        ref, _ = getattr(self, form)
+        _, _, _, ratio = kb.check_within(got, ref, self.bound(form, extra))
+        return {tuple(int(i) for i in e) for e in (ratio > 1.0).nonzero().tolist()}
+
+
+def np_unravel(i, shape):
+    out = []
+    for s in reversed(shape):
+        out.append(i % s)
+        i //= s
+    return tuple(reversed(out))
+
+
+@pytest.fixture(scope="module")
+def tile_forms():
+    return _TileForms()
+
+
+def test_tile_form_emulations_are_within_the_bound(tile_forms):
+    s = tile_forms
+    runs = {"fwd1": (s.emul_fwd(), 0), "fwd2": (s.emul_fwd(act2=True), 1), "dg1": (s.emul_dgrad(), 1),
+            "dg2": (s.emul_dgrad(keep=True), 0)}
+    for form, (got, extra) in runs.items():
+        ref, _ = getattr(s, form)
+        assert kb.assert_within(got, ref, s.bound(form, extra), f"emul tile {form}") <= 1.0
+    # K-step shares (WK = 4): four partial fp32 sums over the taps meet in share order
+    parts = [F.conv3d(s.gy, kb.dgrad_filter(s.wd) * sel.view(1, 1, 3, 3, 3), None, 1, 1)
+             for sel in (torch.arange(27) % 4 == q for q in range(4))]
+    v = ((parts[0] + parts[1]) + parts[2]) + parts[3]
+    ref, A = kb.ref_dgrad(s.gy, s.wd, (1, 1, 1))
+    assert kb.assert_within(_bf(v), ref, kb.bound(ref, A, 27 * s.cin + 4, kb.RHO_BF16), "emul tile WK=4") <= 1.0
+
+
+N_VOX = 2 * 5 * 6 * 9
+TILE_MUTATIONS = {  # name -> (form, K extra, emulation switches, region of the wrong elements (b, c, x, y, z), least hits)
+    "activation_past_act_c1": ("fwd1", 0, "fwd", dict(act_c1=32), lambda e: e[1] >= 16, N_VOX * 16 // 4),
+    "bias_past_act_c1": ("fwd1", 0, "fwd", dict(bias_c1=32), lambda e: e[1] >= 16, N_VOX * 16 * 8 // 10),
+    "act2_res_after_the_activation": ("fwd2", 1, "fwd", dict(act2=True, res_after=True), lambda e: e[1] < 16,
+                                      N_VOX * 16 // 4),
+    "accumulate_past_acc_c1": ("dg1", 1, "dgrad", dict(acc_c1=20), lambda e: 16 <= e[1] < 20, N_VOX * 4 * 8 // 10),
+    "mask_window_shifted_by_4": ("dg1", 1, "dgrad", dict(win=(12, 28)), lambda e: 8 <= e[1] < 28, N_VOX * 8 // 4),
+    "mask_from_the_next_voxel_along_z": ("dg1", 1, "dgrad", dict(znext=True), lambda e: 8 <= e[1] < 24, N_VOX * 16 // 4),
+    "keep_dropped": ("dg2", 0, "dgrad", dict(keep=True, no_keep=True), lambda e: True, N_VOX * 3),
+}
+
+
+def _tile_rejected(s, got, form, extra, region, min_hits, label):
+    bad = s.violations(got, form, extra)
+    assert len(bad) >= min_hits, (label, len(bad))
+    assert all(region(e) for e in bad), (label, sorted(bad)[:5])
+    ref, _ = getattr(s, form)
+    with pytest.raises(AssertionError) as ei:
+        kb.assert_within(got, ref, s.bound(form, extra), label)
+    named = [tuple(int(v) for v in m[:5]) for m in
+             re.findall(r"^\s+\(b=(\d+), c=(\d+), x=(\d+), y=(\d+), z=(\d+)\):.* ratio (\S+)$", str(ei.value), flags=re.M)
+             if float(m[5]) > 1.0]
+    assert named and all(region(e) for e in named), (label, str(ei.value))
+    return named
+
+
+@pytest.mark.parametrize("name", list(TILE_MUTATIONS))
+def test_tile_epilogue_mutation_is_caught(tile_forms, name):
+    form, extra, which, kw, region, min_hits = TILE_MUTATIONS[name]
+    s = tile_forms
+    got = s.emul_fwd(**kw) if which == "fwd" else s.emul_dgrad(**kw)
+    if name == "keep_dropped":  # every channel whose keep factor is not 1 is wrong; the dropped ones (keep = 0) certainly
+        zero = {(0, 5), (1, 20), (1, 31)}
+        bad = s.violations(got, form, extra)
+        assert {(e[0], e[1]) for e in bad} >= zero
+        region = lambda e: float(s.keep[e[0], e[1]]) != 1.0
+    _tile_rejected(s, got, form, extra, region, min_hits, name)
+
+
+@pytest.mark.parametrize("which", ["negative_zero_taken_as_positive", "positive_subnormal_taken_as_not_positive"])
+def test_tile_mask_sign_of_special_values_is_caught(tile_forms, which):
+    s = tile_forms
+    e = s.e0 if which.startswith("negative") else s.e1
+    at = (e[0], s.win[0] + e[1]) + e[2:]
+    named = _tile_rejected(s, s.emul_dgrad(flip=[e]), "dg1", 1, lambda q: q == at, 1, which)
+    assert named[0] == at
+
+
+# ---- completeness of tests/test_conv_tile_matrix.py -------------------------------------------------------------------
+
+STRIDE1_UNITS = ("narrow", "narrow_masked", "n128", "n144", "wide", "masked", "small", "tm3", "simple_narrow",
+                 "simple_n128", "simple_small", "f32", "f32_wide", "f32_masked")
+
+
+def _launch_ct_instantiations(src):
+    """every ``launch_ct<...>`` of a translation unit as (WM, WN, TM, TN, TPK, MASK, F32, WK, SIMPLE), a ``TPK``
+    argument expanded over the ``run<n>`` its dispatcher calls and narrowed by an enclosing ``if constexpr (TPK == 2)``"""
+    src = re.sub(r"//[^\n]*", "", src)
+    dispatched = sorted({int(n) for n in re.findall(r"\brun<(\d)>\(", src)})
+    only2 = []  # character ranges of `if constexpr (TPK == 2) { ... }` blocks
+    for m in re.finditer(r"if constexpr \(TPK == 2\) \{", src):
+        depth, i = 1, m.end()
+        while depth:
+            depth += {"{": 1, "}": -1}.get(src[i], 0)
+            i += 1
+        only2.append((m.end(), i))
+    out = set()
+    for m in re.finditer(r"launch_ct<([^>]*)>\(", src):
+        args = [a.strip() for a in m.group(1).split(",")]
+        args += ["false", "BF16", "1", "0"][len(args) - 5:]
+        assert len(args) == 9, m.group(0)
+        tpks = [int(args[4])] if args[4].isdigit() else dispatched
+        if args[4] == "TPK" and any(lo <= m.start() < hi for lo, hi in only2):
+            tpks = [t for t in tpks if t == 2]
+        assert tpks, m.group(0)
+        word = {"true": 1, "false": 0, "BF16": 0, "F32": 1}
+        for t in tpks:
+            v = [int(a) if a.isdigit() else word[a] for a in args[:4] + [str(t)] + args[5:]]
+            out.add(tuple(v))
+    return out
+
+
+def test_every_stride1_instantiation_has_a_matrix_row_or_a_reason():
+    """the ``launch_ct<...>`` of the stride-1 translation units, read from the sources, are exactly the instantiations
+    test_conv_tile_matrix.py names: a row that reaches it, or an entry of UNREACHABLE that says why none can"""
+    import os
+
+    import test_conv_tile_matrix as mx
+
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gan_sr_wind_field_amd", "csrc")
+    in_src = {}
+    for unit in STRIDE1_UNITS:
+        with open(os.path.join(csrc, f"conv_tile_{unit}.hip")) as f:
+            for inst in _launch_ct_instantiations(f.read()):
+                in_src.setdefault(inst, []).append(unit)
+    units = {n[len("conv_tile_"):-len(".hip")] for n in os.listdir(csrc) if n.startswith("conv_tile_") and n.endswith(".hip")}
+    assert units - {"strided"} == set(STRIDE1_UNITS), "a new conv_tile_*.hip: add it to STRIDE1_UNITS and to the matrix"
+    assert in_src and all(len(u) == 1 for u in in_src.values()), "an instantiation in two translation units"
+    rows = {r[8] for r in mx.INSTANTIATION_ROWS}
+    named = rows | set(mx.UNREACHABLE)
+    missing = {i: u for i, u in in_src.items() if i not in named}
+    assert not missing, f"instantiations without a row in test_conv_tile_matrix.py: {missing}"
+    assert not named - set(in_src), f"rows that name an instantiation the sources do not hold: {sorted(named - set(in_src))}"
+    assert not rows & set(mx.UNREACHABLE)
