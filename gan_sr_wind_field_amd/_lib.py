@@ -30,6 +30,7 @@ EXPORTS = [
     "wsr_level_spectra_bins", "wsr_level_spectra_workspace_floats", "wsr_level_spectra",
     "wsr_spectral_energy_workspace_floats", "wsr_spectral_energy_saved_floats", "wsr_spectral_energy",
     "wsr_spectral_energy_bwd",
+    "wsr_gather_batch_filtered",
     "wsr_last_tile_plan", "wsr_last_tile_instantiation",
 ]
 
@@ -164,6 +165,8 @@ def lib() -> C.CDLL:
         "wsr_level_spectra": [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp],   # additive export
         "wsr_spectral_energy": [vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp],   # additive export
         "wsr_spectral_energy_bwd": [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp],   # additive export
+        "wsr_gather_batch_filtered": [vp, i64, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp,
+                                      vp],   # additive export
         "wsr_last_tile_plan": [C.POINTER(C.c_int32)],   # additive export (diagnostic)
         "wsr_last_tile_instantiation": [C.POINTER(C.c_int32)],   # additive export (diagnostic)
     }

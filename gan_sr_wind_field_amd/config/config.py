@@ -37,6 +37,9 @@ Extension (optional keys, defaults keep reference behaviour):
   [SPECTRAL_LOSS] weight / window / k_min / k_max / rel_floor
             the generator loss gains an energy-spectrum term: the mean squared log ratio of the binned horizontal
             kinetic-energy spectra of SR and HR (spectral_loss.py, csrc/spectral_loss.hip), logged as ``spectral``
+  [DEGRADATION] kernel / sigma / channels
+            the LR inputs of training, validation and --test are a box- or gaussian-filtered, then sampled copy of the
+            full-resolution channels instead of every scale-th column (degradation.py, csrc/data_degrade.hip)
 """
 from __future__ import annotations
 
@@ -611,6 +614,67 @@ class SpectralLossConfig(IniConfig):
         return "[SPECTRAL_LOSS]\n" + "".join(f"{k} = {getattr(self, k)}\n" for k, _ in self._schema)
 
 
+class DegradationConfig(IniConfig):
+    """[DEGRADATION] (extension): anti-aliased LR inputs (degradation.py, csrc/data_degrade.hip); absent section = off -
+    LR is every ``scale``-th HR column, as in the reference - and never printed by ``asINI``.  ``kernel`` (required):
+    ``box`` (a width-``scale`` mean centred on the sample point) or ``gaussian``; ``sigma`` (gaussian only, required
+    there: no reference default to inherit): in HR grid cells, 0 < sigma <= 10; ``channels``: ``all`` LR channels, or
+    ``wind`` - channels 0..2 only, the others stay point-sampled."""
+
+    present: bool = False
+    kernel: str = None
+    sigma: float = None
+    channels: str = "all"
+    _schema = (("kernel", None), ("sigma", _F), ("channels", None))
+
+    def setDegradationConfig(self, section):
+        """``section`` None (no [DEGRADATION] in the file) restores the defaults and switches the section off."""
+        self.present = section is not None
+        for key, kind in self._schema:
+            if kind is None:
+                raw = None if section is None else section.get(key)
+                val = None if raw is None else raw.strip().lower()
+            else:
+                try:
+                    val = None if section is None else _read(section, key, kind)
+                except ValueError:
+                    raise ValueError(f"[DEGRADATION] {key} must be a number, not {section.get(key)!r}") from None
+            setattr(self, key, getattr(DegradationConfig, key) if val is None else val)
+
+    def validate(self, scale) -> None:
+        if not self.present:
+            return
+        from ..degradation import CHANNELS, KERNELS, MAX_RADIUS, taps
+        if self.kernel is None:
+            raise ValueError("[DEGRADATION] kernel is required: box or gaussian")
+        if self.kernel not in KERNELS:
+            raise ValueError(f"[DEGRADATION] kernel must be box or gaussian, not {self.kernel!r}")
+        if self.kernel == "gaussian":
+            if self.sigma is None:
+                raise ValueError("[DEGRADATION] sigma is required with kernel = gaussian: the width in HR grid cells")
+            if not 0.0 < self.sigma <= 10.0:  # (NaN fails both)
+                raise ValueError(f"[DEGRADATION] sigma must be > 0 and <= 10, not {self.sigma}")
+        if self.channels not in CHANNELS:
+            raise ValueError(f"[DEGRADATION] channels must be all or wind, not {self.channels!r}")
+        if scale is None or scale < 1:
+            raise ValueError(f"[DEGRADATION] needs [DEFAULT] scale >= 1, not {scale}")
+        try:
+            taps(self.kernel, scale, self.sigma)
+        except ValueError:
+            raise ValueError(f"[DEGRADATION] kernel = {self.kernel} at scale {scale} needs a tap radius above "
+                             f"{MAX_RADIUS}") from None
+
+    def spec(self):
+        """what the datasets take (``preprosess(degradation=...)``): a ``degradation.DegradationSpec``, None when off"""
+        if not self.present:
+            return None
+        from ..degradation import DegradationSpec
+        return DegradationSpec(self.kernel, self.sigma if self.kernel == "gaussian" else None, self.channels)
+
+    def __str__(self) -> str:
+        return "[DEGRADATION]\n" + "".join(f"{k} = {getattr(self, k)}\n" for k, _ in self._schema)
+
+
 class Config(IniConfig):
     name: str = "default_name"
     model: str = "default_model"
@@ -641,6 +705,7 @@ class Config(IniConfig):
     diagnostics: DiagnosticsConfig = DiagnosticsConfig()
     spectrum: SpectrumConfig = SpectrumConfig()
     spectral_loss: SpectralLossConfig = SpectralLossConfig()
+    degradation: DegradationConfig = DegradationConfig()
     compute_dtype: str = "fp32"
     is_train: bool
     is_use: bool
@@ -683,6 +748,8 @@ class Config(IniConfig):
         self.spectrum.validate()
         self.spectral_loss.setSpectralLossConfig(parser["SPECTRAL_LOSS"] if parser.has_section("SPECTRAL_LOSS") else None)
         self.spectral_loss.validate()
+        self.degradation.setDegradationConfig(parser["DEGRADATION"] if parser.has_section("DEGRADATION") else None)
+        self.degradation.validate(self.scale)
 
     def setBaseConfig(self, base):
         self.name = base.get("name")

@@ -9,7 +9,8 @@ the same ``torch`` / ``np.random`` seeds.  Opt-in through ``[DATA] device_reside
 The store holds, per sample, ``reformat_to_torch`` of the FULL field at coarseness 1 - the LR channels at full
 resolution (channels 0..2 are the HR wind) - and the raw altitude Z: fp32 (N, Cin + 1, X, Y, NZ).  Normalising is
 elementwise, so doing it before the slice gives the slice's fp32 bits; coarsening is not done here (its phase depends
-on the slice origin).  The random part of ``__getitem__`` (``CustomizedDataset.draw_augmentation``) runs on the host in
+on the slice origin; with ``dataset.degradation`` set - [DEGRADATION], degradation.py - the gather also filters the LR
+channels before it samples them, ``wsr_gather_batch_filtered``).  The random part of ``__getitem__`` (``CustomizedDataset.draw_augmentation``) runs on the host in
 a ``DataLoader`` over descriptors ``(sample, x0, y0, k, flip_x, flip_y)``: the sampler, its torch seeds and the
 ``np.random`` draws happen exactly where the CPU loader makes them, so every later draw of the step sees the same
 streams.
@@ -95,6 +96,16 @@ class ResidentStore:
             torch.cuda.synchronize(device)
         self.seconds = time.perf_counter() - t0
         self.gigabytes = need / 1e9
+        # [DEGRADATION]: the dataset's LR is filtered, then sampled - the gather does the same from the two weight
+        # tables the CPU path reads (degradation.tables), built and uploaded once
+        self.degradation = getattr(dataset, "degradation", None)
+        if self.degradation is not None:
+            from . import degradation
+            X, Y = shape[2:4]
+            W, H = (self.slice_size, self.slice_size) if self.slice_size else (X, Y)
+            wx, wy, _ = degradation.tables(self.degradation, int(self.s), W, H)
+            self.wx, self.wy = (torch.from_numpy(w.copy()).to(device) for w in (wx, wy))
+            self.n_filt = self.degradation.n_filt(self.cin)
         logging.getLogger("status").info(f"device-resident data: {len(dataset)} samples, {self.gigabytes:.3f} GB "
                                          f"loaded in {self.seconds:.1f} s ({num_workers} workers)")
 
@@ -110,8 +121,11 @@ class ResidentStore:
         if not bool(((n >= 0) & (n < len(self)) & (x0 >= 0) & (x0 + W <= X) & (y0 >= 0) & (y0 + H <= Y) & (k >= 0)
                      & (k <= 3) & ((k % 2 == 0) | (W == H))).all()):
             raise ValueError(f"descriptor outside the store {tuple(self.data.shape)}: {d.tolist()}")
-        return hip_ops.gather_batch(self.data, d.pin_memory().to(self.data.device, non_blocking=True), self.cin,
-                                    self.s, self.slice_size)
+        d_dev = d.pin_memory().to(self.data.device, non_blocking=True)
+        if self.degradation is not None:
+            return hip_ops.gather_batch_filtered(self.data, d_dev, self.cin, self.s, self.slice_size, self.wx, self.wy,
+                                                 self.n_filt)
+        return hip_ops.gather_batch(self.data, d_dev, self.cin, self.s, self.slice_size)
 
 
 class _Draws(torch.utils.data.Dataset):

@@ -1059,6 +1059,53 @@ def gather_batch(store: Tensor, desc: Tensor, cin: int, s: int, slice_size: int)
     return lr, hr, z
 
 
+DEGRADE_MAX_R = 32  # WSR_DEGRADE_MAX_R
+
+
+def gather_batch_filtered(store: Tensor, desc: Tensor, cin: int, s: int, slice_size: int, wx: Tensor, wy: Tensor,
+                          n_filt: int, out: Optional[Tuple[Tensor, Tensor, Tensor]] = None
+                          ) -> Tuple[Tensor, Tensor, Tensor]:
+    """:func:`gather_batch` with the LR degradation of ``[DEGRADATION]`` (degradation.py) in the same launch: the LR
+    planes read from store channels below ``n_filt`` are filtered with the fp32 weight tables ``wx`` (ceil(W / s),
+    2 R + 1) and ``wy`` (ceil(H / s), 2 R + 1) of ``degradation.axis_weights`` (W x H: the slice, or the domain when
+    ``slice_size`` is 0) and then sampled; the other LR planes, HR and Z are the copies of :func:`gather_batch`.
+    ``out``: contiguous fp32 ``(LR, HR, Z)`` of the shapes below to write into (``wsr_gather_batch_filtered``)."""
+    _need_cuda(store, desc, wx, wy)
+    if store.dtype != torch.float32 or store.dim() != 5 or not store.is_contiguous() or store.shape[1] != cin + 1:
+        raise ValueError(f"gather_batch_filtered wants a contiguous fp32 store (N, {cin + 1}, X, Y, NZ), got "
+                         f"{tuple(store.shape)}")
+    if desc.dtype != torch.int32 or desc.dim() != 2 or desc.shape[1] != 6 or not desc.is_contiguous():
+        raise ValueError(f"gather_batch_filtered wants an int32 (B, 6) descriptor table, got {desc.dtype} "
+                         f"{tuple(desc.shape)}")
+    N, _, X, Y, NZ = store.shape
+    B = desc.shape[0]
+    W, H = (slice_size, slice_size) if slice_size else (X, Y)
+    Wc, Hc = -(-W // s), -(-H // s)
+    T = wx.shape[-1] if wx.dim() == 2 else 0
+    R = (T - 1) // 2
+    for name, w, rows in (("wx", wx, Wc), ("wy", wy, Hc)):
+        if w.dtype != torch.float32 or w.dim() != 2 or not w.is_contiguous() or tuple(w.shape) != (rows, T):
+            raise ValueError(f"gather_batch_filtered wants {name} as a contiguous fp32 ({rows}, 2 R + 1) table, got "
+                             f"{w.dtype} {tuple(w.shape)}")
+    if T != 2 * R + 1 or R > DEGRADE_MAX_R:
+        raise ValueError(f"gather_batch_filtered wants 2 R + 1 taps with 0 <= R <= {DEGRADE_MAX_R}, got {T}")
+    if not 0 <= n_filt <= cin:
+        raise ValueError(f"gather_batch_filtered: n_filt must be in 0 .. {cin}, not {n_filt}")
+    opts = dict(dtype=torch.float32, device=store.device)
+    shapes = ((B, cin, Wc, Hc, NZ), (B, 3, W, H, NZ), (B, 1, W, H, NZ))
+    if out is None:
+        out = tuple(torch.empty(shape, **opts) for shape in shapes)
+    _need_cuda(*out)
+    for name, t, shape in zip(("LR", "HR", "Z"), out, shapes):
+        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"gather_batch_filtered wants out {name} as a contiguous fp32 {shape} tensor, got "
+                             f"{t.dtype} {tuple(t.shape)}")
+    lr, hr, z = out
+    check(_lib.lib().wsr_gather_batch_filtered(_p(store), N, _p(desc), B, cin, s, slice_size, X, Y, NZ, _p(wx), _p(wy),
+                                               R, n_filt, _p(lr), _p(hr), _p(z), _stream()), "gather_batch_filtered")
+    return lr, hr, z
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # device-side evaluation ([EVAL] device_metrics; csrc/eval_metrics.hip)
 # ---------------------------------------------------------------------------------------------------------------------

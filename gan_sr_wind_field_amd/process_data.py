@@ -207,7 +207,7 @@ class CustomizedDataset(torch.utils.data.Dataset):
     def __init__(self, filenames, subfolder_name, Z_MIN, Z_MAX, UVW_MAX, P_MIN, P_MAX, Z_ABOVE_GROUND_MAX, x, y,
                  terrain, include_pressure=False, include_z_channel=False, interpolate_z=False,
                  include_above_ground_channel=False, COARSENESS_FACTOR=4, data_aug_rot=True, data_aug_flip=True,
-                 enable_slicing=False, slice_size=64, for_plotting=False, is_test=False):
+                 enable_slicing=False, slice_size=64, for_plotting=False, is_test=False, degradation=None):
         self.filenames = list(filenames)
         self.subfolder_name = subfolder_name
         self.Z_MIN, self.Z_MAX, self.Z_ABOVE_GROUND_MAX = Z_MIN, Z_MAX, Z_ABOVE_GROUND_MAX
@@ -221,6 +221,7 @@ class CustomizedDataset(torch.utils.data.Dataset):
         self.data_aug_rot, self.data_aug_flip = data_aug_rot, data_aug_flip
         self.enable_slicing, self.slice_size = enable_slicing, slice_size
         self.for_plotting, self.is_test = for_plotting, is_test
+        self.degradation = degradation  # a degradation.DegradationSpec ([DEGRADATION]) or None: LR = HR[:, ::s, ::s, :]
         self.slice_index = 0
         folder = os.path.join(DATA_ROOT, "full_dataset_files", subfolder_name)
         os.makedirs(os.path.join(folder, "max"), exist_ok=True)
@@ -234,12 +235,21 @@ class CustomizedDataset(torch.utils.data.Dataset):
         return len(self.filenames)
 
     def _tensors(self, u, v, w, pressure, z, z_above_ground, coarseness_factor=None):
+        """``reformat_to_torch`` of the given fields.  With ``self.degradation`` set and no explicit
+        ``coarseness_factor``, LR is the filtered, then sampled full-resolution LR (degradation.degrade_lr) instead of
+        every ``s``-th column; HR and Z are the same either way."""
+        degrade = self.degradation is not None and coarseness_factor is None
         s = self.coarseness_factor if coarseness_factor is None else coarseness_factor
-        return reformat_to_torch(u, v, w, pressure, z, z_above_ground, self.Z_MIN, self.Z_MAX, self.Z_ABOVE_GROUND_MAX,
-                                 self.UVW_MAX, self.P_MIN, self.P_MAX, coarseness_factor=s,
-                                 include_pressure=self.include_pressure, include_z_channel=self.include_z_channel,
-                                 include_above_ground_channel=self.include_above_ground_channel,
-                                 for_plotting=self.for_plotting)
+        LR, HR, Z = reformat_to_torch(u, v, w, pressure, z, z_above_ground, self.Z_MIN, self.Z_MAX,
+                                      self.Z_ABOVE_GROUND_MAX, self.UVW_MAX, self.P_MIN, self.P_MAX,
+                                      coarseness_factor=1 if degrade else s, include_pressure=self.include_pressure,
+                                      include_z_channel=self.include_z_channel,
+                                      include_above_ground_channel=self.include_above_ground_channel,
+                                      for_plotting=self.for_plotting)
+        if degrade:
+            from .degradation import degrade_lr
+            LR = torch.from_numpy(degrade_lr(LR.numpy(), s, self.degradation))
+        return LR, HR, Z
 
     def load_fields(self, index):
         """The file side of ``__getitem__``: the sample's pickle (and, with ``interpolate_z``, its cached
@@ -250,8 +260,9 @@ class CustomizedDataset(torch.utils.data.Dataset):
             z, z_above_ground, u, v, w, pressure = pickle.load(f)
         HR_raw = Z_raw = 0
         if self.interpolate_z:
-            if self.is_test:  # keep the un-interpolated truth for the evaluation harness
-                _, HR_raw, Z_raw = self._tensors(u, v, w, pressure, z, z_above_ground)
+            if self.is_test:  # keep the un-interpolated truth for the evaluation harness (its LR is not used)
+                _, HR_raw, Z_raw = self._tensors(u, v, w, pressure, z, z_above_ground,
+                                                 coarseness_factor=self.coarseness_factor)
             z, z_above_ground, u, v, w, pressure = get_interpolated_z_data(
                 os.path.join(DATA_ROOT, "interpolated_z_data", self.subfolder_name, name), self.x, self.y,
                 z_above_ground, u, v, w, pressure, self.terrain)
@@ -398,9 +409,10 @@ def preprosess(train_eval_test_ratio=0.8, X_DICT={"start": 0, "max": 128, "step"
                start_date=date(2018, 4, 1), end_date=date(2018, 4, 3), include_pressure=True, include_z_channel=False,
                interpolate_z=False, enable_slicing=False, slice_size=64, include_above_ground_channel=False,
                COARSENESS_FACTOR=4, train_aug_rot=False, val_aug_rot=False, train_aug_flip=False, val_aug_flip=False,
-               for_plotting=False):
+               for_plotting=False, degradation=None):
     """-> (dataset_train, dataset_test, dataset_validation, x, y): chronological 80 / 10 / 10 split
-    (reference :497-639; the spelling of the name is the reference's)."""
+    (reference :497-639; the spelling of the name is the reference's).  ``degradation``: the LR degradation of all
+    three datasets (a ``degradation.DegradationSpec``, [DEGRADATION]); None = every ``COARSENESS_FACTOR``-th column."""
     static = os.path.join(DATA_ROOT, "full_dataset_files", "static_terrain_x_y.pkl")
     if not os.path.isfile(static):
         write_synthetic_dataset(start_date, end_date, X_DICT, Y_DICT, Z_DICT)
@@ -412,7 +424,7 @@ def preprosess(train_eval_test_ratio=0.8, X_DICT={"start": 0, "max": 128, "step"
     n_test = int(len(names) * (1 - train_eval_test_ratio) / 2)
     common = dict(include_pressure=include_pressure, include_z_channel=include_z_channel, interpolate_z=interpolate_z,
                   include_above_ground_channel=include_above_ground_channel, COARSENESS_FACTOR=COARSENESS_FACTOR,
-                  slice_size=slice_size)
+                  slice_size=slice_size, degradation=degradation)
     args = (sub, Z_MIN, Z_MAX, UVW_MAX, P_MIN, P_MAX, ZAG_MAX, x, y, terrain)
     dataset_train = CustomizedDataset(names[:n_train], *args, data_aug_rot=train_aug_rot, data_aug_flip=train_aug_flip,
                                       enable_slicing=enable_slicing, for_plotting=for_plotting, **common)

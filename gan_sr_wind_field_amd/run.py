@@ -123,7 +123,7 @@ def prepare_data(cfg: Config):
         include_above_ground_channel=g.include_above_ground_channel, train_aug_rot=cfg.dataset_train.data_aug_rot,
         train_aug_flip=cfg.dataset_train.data_aug_flip, val_aug_rot=cfg.dataset_val.data_aug_rot,
         val_aug_flip=cfg.dataset_val.data_aug_flip, train_eval_test_ratio=cfg.training.train_eval_test_ratio,
-        COARSENESS_FACTOR=cfg.scale)
+        COARSENESS_FACTOR=cfg.scale, degradation=cfg.degradation.spec())
 
 
 def main(argv=None) -> None:

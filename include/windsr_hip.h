@@ -550,6 +550,21 @@ int wsr_ragan_loss(const float* u, const float* v, const float* lu, const float*
 int wsr_gather_batch(const float* store, int64_t n_samples, const int32_t* desc, int32_t B, int32_t Cin, int32_t s,
                      int32_t S, int32_t X, int32_t Y, int32_t NZ, float* lr, float* hr, float* z, void* stream);
 
+/* wsr_gather_batch with the anti-aliased LR degradation of [DEGRADATION] (degradation.py; csrc/data_degrade.hip), still
+ * one launch for lr, hr and z.  hr, z and the lr planes read from store channels >= n_filt are the copies of
+ * wsr_gather_batch.  An lr plane read from a store channel < n_filt is, in the slice frame before rotation and mirrors
+ * (W x H = S x S, or X x Y when S = 0), with f the store channel inside the slice,
+ *     g[i][y]  = sum over d = 0 .. 2R ascending of fl(wx[i][d] * f[s i + d - R][y])       (x pass first)
+ *     lr[i][j] = sum over d = 0 .. 2R ascending of fl(wy[j][d] * g[i][s j + d - R])
+ * per z level: fp32, every product and every sum rounded (no fused multiply-add), sums started from +0.0f, taps outside
+ * the slice skipped (not multiplied by zero), z never filtered; the sign flips of rotation and mirrors are applied to
+ * the finished sum.  wx: fp32 (ceil(W/s), 2R+1), wy: fp32 (ceil(H/s), 2R+1) device tables (degradation.axis_weights),
+ * 0 <= R <= WSR_DEGRADE_MAX_R, 0 <= n_filt <= Cin.  Reads stay inside the slice, hence inside the store.            */
+#define WSR_DEGRADE_MAX_R 32
+int wsr_gather_batch_filtered(const float* store, int64_t n_samples, const int32_t* desc, int32_t B, int32_t Cin,
+                              int32_t s, int32_t S, int32_t X, int32_t Y, int32_t NZ, const float* wx, const float* wy,
+                              int32_t R, int32_t n_filt, float* lr, float* hr, float* z, void* stream);
+
 /* ---- device-side evaluation ([EVAL] device_metrics; csrc/eval_metrics.hip) ---------------------------
  * Everything fp32 planar (B, C, X, Y, NZ), z innermost; replaces the ATen / numpy work of test.py:101-115 and
  * wind_field_GAN_3D.py:594-597 (F.interpolate, about fifteen reductions per field, np.interp per column).
