@@ -79,6 +79,10 @@ class wind_field_GAN_3D(BaseGAN):
             "SR_pix_distribution": torch.zeros(1), "D_pred_HR": torch.zeros(1), "D_pred_SR": torch.zeros(1),
         }
         self.metrics_dict = _zeros_dict(("val_PSNR", "Trilinear_PSNR", "pix_loss_unscaled", "trilinear_pix_loss"))
+        sc = getattr(cfg, "ssim", None)
+        self._ssim_cfg = sc if sc is not None and sc.on and sc.validation else None
+        if self._ssim_cfg is not None:  # ([SSIM] validation: two more metrics of a validation batch)
+            self.metrics_dict.update(_zeros_dict(("val_SSIM", "Trilinear_SSIM")))
         self.device_check = ""
         self.batch_size = 1
         dev = getattr(cfg, "device", self.device)
@@ -613,6 +617,8 @@ class wind_field_GAN_3D(BaseGAN):
             return
         fake_HR = self.update_G(LR, HR, Z, it, False)
         self.update_D(HR, fake_HR, it, False)
+        if self._ssim_cfg is not None:
+            self._val_ssim(LR, HR, fake_HR)
         if self.cfg.eval.on and HR.is_cuda:
             self._device_val_metrics(LR, HR, fake_HR)
             return
@@ -637,6 +643,16 @@ class wind_field_GAN_3D(BaseGAN):
         self.metrics_dict["val_PSNR"], self.metrics_dict["Trilinear_PSNR"] = m["PSNR"], m["PSNR_trilinear"]
         l2 = str(self.cfg.training.pixel_criterion).lower() == "l2"
         self.metrics_dict["trilinear_pix_loss"] = sums[1] / (3 * nvox) if l2 else m["old_pix_trilinear"]
+
+    def _val_ssim(self, LR, HR, fake_HR) -> None:
+        """[SSIM] validation: the mean SSIM over samples, levels, components and positions of a validation batch, for
+        the generator's output and for the trilinear baseline.  On a GPU the sums come from ``wsr_level_ssim`` and the two
+        values stay device tensors (float64); on a CPU from ``ssim.level_ssim_reference``."""
+        from ..ssim import n_positions
+
+        sums = self.level_ssim(HR, fake_HR, LR).sum(dim=(0, 1, 2))
+        n = 3 * HR.shape[0] * HR.shape[4] * n_positions(HR.shape[2], HR.shape[3], self._ssim_cfg.window_size)
+        self.metrics_dict["val_SSIM"], self.metrics_dict["Trilinear_SSIM"] = sums[0] / n, sums[2] / n
 
     def optimize_parameters(self, LR, HR, Z, it):
         self.compute_losses_and_optimize(LR, HR, Z, it, training_iteration=True)
@@ -730,6 +746,27 @@ class wind_field_GAN_3D(BaseGAN):
             return t.detach().float().contiguous()
 
         return hip_ops.level_spectra(f(HR), f(SR), hip_ops.trilinear_xy(f(LR), self.cfg.scale), window)
+
+    # ------------------------------------------------------------------ structural similarity ([SSIM])
+    def level_ssim(self, HR, SR, LR):
+        """The four sums of ``ssim.SSIM_SUMS`` per sample, z level and wind component of a batch -> float64
+        (B, NZ, 3, 4) on the tensors' device, with the window, sigma and data range of ``[SSIM]`` (its defaults without
+        the section): the trilinear baseline of ``LR`` is built here (``wsr_trilinear_xy`` on a GPU, ``F.interpolate`` on
+        a CPU), the sums come from ``hip_ops.level_ssim`` on a GPU and from ``ssim.level_ssim_reference`` on a CPU.
+        Reads no weights: the same inside ``ema_scope()``."""
+        from ..config.config import SsimConfig
+        from ..ssim import level_ssim_reference
+
+        sc = getattr(self.cfg, "ssim", None) or SsimConfig
+        par = (sc.window_size, sc.sigma, sc.data_range)
+        if not HR.is_cuda:
+            return level_ssim_reference(HR, SR.detach(), _trilinear(LR, self.cfg.scale), *par)
+        from .. import hip_ops
+
+        def f(t):
+            return t.detach().float().contiguous()
+
+        return hip_ops.level_ssim(f(HR), f(SR), hip_ops.trilinear_xy(f(LR), self.cfg.scale), *par)
 
     def make_new_labels(self, it):
         """Real / fake label vectors of this iteration (reference :627-678)."""

@@ -31,6 +31,7 @@ EXPORTS = [
     "wsr_spectral_energy_workspace_floats", "wsr_spectral_energy_saved_floats", "wsr_spectral_energy",
     "wsr_spectral_energy_bwd",
     "wsr_gather_batch_filtered",
+    "wsr_level_ssim_workspace_floats", "wsr_level_ssim",
     "wsr_last_tile_plan", "wsr_last_tile_instantiation",
 ]
 
@@ -167,6 +168,8 @@ def lib() -> C.CDLL:
         "wsr_spectral_energy_bwd": [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp],   # additive export
         "wsr_gather_batch_filtered": [vp, i64, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp,
                                       vp],   # additive export
+        "wsr_level_ssim": [vp, i32, vp, i32, vp, i32, vp, i32, C.c_float, C.c_float, i32, i32, i32, i32, vp, vp,
+                           vp],   # additive export
         "wsr_last_tile_plan": [C.POINTER(C.c_int32)],   # additive export (diagnostic)
         "wsr_last_tile_instantiation": [C.POINTER(C.c_int32)],   # additive export (diagnostic)
     }
@@ -187,6 +190,8 @@ def lib() -> C.CDLL:
     for name in ("wsr_spectral_energy_workspace_floats", "wsr_spectral_energy_saved_floats"):
         getattr(L, name).argtypes = [i32, i32, i32, i32]
         getattr(L, name).restype = C.c_int64
+    L.wsr_level_ssim_workspace_floats.argtypes = [i32, i32, i32, i32, i32]
+    L.wsr_level_ssim_workspace_floats.restype = C.c_int64
     if L.wsr_abi_version() != 9:
         raise RuntimeError("libwindsr_hip.so ABI version mismatch")
     _lib = L

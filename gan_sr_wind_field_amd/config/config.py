@@ -40,6 +40,10 @@ Extension (optional keys, defaults keep reference behaviour):
   [DEGRADATION] kernel / sigma / channels
             the LR inputs of training, validation and --test are a box- or gaussian-filtered, then sampled copy of the
             full-resolution channels instead of every scale-th column (degradation.py, csrc/data_degrade.hip)
+  [SSIM] window_size / sigma / data_range / per_level / validation
+            --test also writes the structural similarity of network and baseline with the truth on horizontal planes,
+            per field, per wind component and per z level (ssim.py, csrc/ssim.hip); validation epochs add val_SSIM and
+            Trilinear_SSIM to the metrics
 """
 from __future__ import annotations
 
@@ -675,6 +679,53 @@ class DegradationConfig(IniConfig):
         return "[DEGRADATION]\n" + "".join(f"{k} = {getattr(self, k)}\n" for k, _ in self._schema)
 
 
+class SsimConfig(IniConfig):
+    """[SSIM] (extension): structural similarity on horizontal planes in ``run.py --test`` and in validation epochs
+    (ssim.py, csrc/ssim.hip); absent section = off, and never printed by ``asINI``.  ``window_size``: the side of the
+    gaussian window, odd, 3 .. 15; ``sigma`` > 0: its standard deviation in HR grid cells; ``data_range`` > 0: the range
+    of one normalised wind component, behind C1 and C2; ``per_level``: ``--test`` also writes
+    ``<name>____ssim_levels.csv``; ``validation``: validation epochs add ``val_SSIM`` and ``Trilinear_SSIM`` to the
+    metrics."""
+
+    present: bool = False
+    window_size: int = 11
+    sigma: float = 1.5
+    data_range: float = 2.0
+    per_level: bool = False
+    validation: bool = True
+    _schema = (("window_size", _I), ("sigma", _F), ("data_range", _F), ("per_level", _B), ("validation", _B))
+
+    def setSsimConfig(self, section):
+        """``section`` None (no [SSIM] in the file) restores the defaults and switches the section off."""
+        self.present = section is not None
+        for key, kind in self._schema:
+            try:
+                val = None if section is None else _read(section, key, kind)
+            except ValueError:
+                what = {_I: "an integer", _F: "a number", _B: "True or False"}[kind]
+                raise ValueError(f"[SSIM] {key} must be {what}, not {section.get(key)!r}") from None
+            setattr(self, key, getattr(SsimConfig, key) if val is None else val)
+
+    def validate(self) -> None:
+        if not self.present:
+            return
+        from ..ssim import MAX_WIN
+        if self.window_size % 2 == 0 or not 3 <= self.window_size <= MAX_WIN:
+            raise ValueError(f"[SSIM] window_size must be odd and 3 .. {MAX_WIN}, not {self.window_size}")
+        if not (self.sigma > 0 and math.isfinite(self.sigma)):
+            raise ValueError(f"[SSIM] sigma must be a finite number > 0, not {self.sigma}")
+        if not (self.data_range > 0 and math.isfinite(self.data_range)):
+            raise ValueError(f"[SSIM] data_range must be a finite number > 0, not {self.data_range}")
+
+    @property
+    def on(self) -> bool:
+        """``--test`` takes the SSIM sums and writes the SSIM files"""
+        return bool(self.present)
+
+    def __str__(self) -> str:
+        return "[SSIM]\n" + "".join(f"{k} = {getattr(self, k)}\n" for k, _ in self._schema)
+
+
 class Config(IniConfig):
     name: str = "default_name"
     model: str = "default_model"
@@ -706,6 +757,7 @@ class Config(IniConfig):
     spectrum: SpectrumConfig = SpectrumConfig()
     spectral_loss: SpectralLossConfig = SpectralLossConfig()
     degradation: DegradationConfig = DegradationConfig()
+    ssim: SsimConfig = SsimConfig()
     compute_dtype: str = "fp32"
     is_train: bool
     is_use: bool
@@ -750,6 +802,8 @@ class Config(IniConfig):
         self.spectral_loss.validate()
         self.degradation.setDegradationConfig(parser["DEGRADATION"] if parser.has_section("DEGRADATION") else None)
         self.degradation.validate(self.scale)
+        self.ssim.setSsimConfig(parser["SSIM"] if parser.has_section("SSIM") else None)
+        self.ssim.validate()
 
     def setBaseConfig(self, base):
         self.name = base.get("name")

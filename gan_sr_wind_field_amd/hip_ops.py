@@ -1468,3 +1468,62 @@ def spectral_energy(HR: Tensor, SR: Tensor, window: str = "hann") -> Tensor:
         raise ValueError(f"spectral_energy: at most {SPECTRUM_MAX_XY} points in x and y, 65535 samples, 65535 levels and "
                          f"2^31 - 1 voxels per sample, not B = {B}, X = {X}, Y = {Y}, NZ = {NZ}")
     return _SpectralEnergy.apply(HR.detach().contiguous().float(), SR.contiguous().float(), SPECTRUM_WINDOWS[window])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# structural similarity on horizontal planes ([SSIM]; csrc/ssim.hip)
+# ---------------------------------------------------------------------------------------------------------------------
+SSIM_SUMS = 4  # WSR_SSIM_SUMS
+SSIM_MAX_WIN = 15  # WSR_SSIM_MAX_WIN
+SSIM_MAX_NZ = 256
+_ssim_taps: dict = {}
+
+
+def _ssim_taps_on(device, win: int, sigma: float) -> Tensor:
+    """``ssim.taps(win, sigma)`` on ``device``: uploaded once per (device, win, sigma)"""
+    from . import ssim
+
+    key = (device.index, int(win), float(sigma))
+    t = _ssim_taps.get(key)
+    if t is None:
+        if len(_ssim_taps) > 64:
+            _ssim_taps.clear()
+        t = _ssim_taps[key] = ssim.taps(win, sigma).to(device).contiguous()
+    return t
+
+
+def level_ssim(HR: Tensor, SR: Tensor, TL: Tensor, win: int = 11, sigma: float = 1.5, data_range: float = 2.0,
+               out: Optional[Tensor] = None) -> Tensor:
+    """Four sums per sample, z level and wind component -> float64 (B, NZ, 3, 4), in the order of ``ssim.SSIM_SUMS``: over
+    the (X - win + 1) (Y - win + 1) valid positions of the separable gaussian window ``ssim.taps(win, sigma)`` on the
+    horizontal plane, SSIM and its contrast-structure factor of ``HR`` with ``SR`` and of ``HR`` with the baseline ``TL``
+    (B, C >= 3, X, Y, NZ; channels 0..2 are read), C1 = (0.01 ``data_range``)^2, C2 = (0.03 ``data_range``)^2.  z is never
+    windowed.  No atomics: the same bits on every call, and exactly the number of positions where the two fields hold the
+    same bits.  ``out``: a float64 (B, NZ, 3, 4) slice to write into (``wsr_level_ssim``)."""
+    from . import ssim
+
+    _need_cuda(HR, SR, TL, out)
+    _planar5("level_ssim", "HR", HR, 3)
+    _planar5("level_ssim", "SR", SR, 3)
+    _planar5("level_ssim", "TL", TL, 3)
+    B, _, X, Y, NZ = HR.shape
+    for name, t in (("SR", SR), ("TL", TL)):
+        if (t.shape[0],) + tuple(t.shape[2:]) != (B, X, Y, NZ):
+            raise ValueError(f"level_ssim: {name} {tuple(t.shape)} does not match HR {tuple(HR.shape)}")
+    ssim.check_window(win, sigma, "level_ssim")
+    ssim.check_domain(X, Y, win, "level_ssim")
+    c1, c2 = ssim.constants(data_range)
+    if NZ > SSIM_MAX_NZ or B > 65535 or X > 32768 or Y > 32768 or X * Y * NZ >= 2 ** 31:
+        raise ValueError(f"level_ssim: at most {SSIM_MAX_NZ} levels, 65535 samples, 32768 points in x and y and 2^31 - 1 "
+                         f"voxels per sample, not B = {B}, X = {X}, Y = {Y}, NZ = {NZ}")
+    if out is None:
+        out = torch.empty((B, NZ, 3, SSIM_SUMS), dtype=torch.float64, device=HR.device)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (B, NZ, 3, SSIM_SUMS) or not out.is_contiguous():
+        raise ValueError(f"level_ssim wants out as a contiguous float64 ({B}, {NZ}, 3, {SSIM_SUMS}) tensor, got "
+                         f"{out.dtype} {tuple(out.shape)}")
+    L = _lib.lib()
+    taps = _ssim_taps_on(HR.device, win, sigma)
+    ws = torch.empty(int(L.wsr_level_ssim_workspace_floats(B, X, Y, NZ, int(win))), dtype=torch.float32, device=HR.device)
+    check(L.wsr_level_ssim(_p(HR), HR.shape[1], _p(SR), SR.shape[1], _p(TL), TL.shape[1], _p(taps), int(win), c1, c2, B, X,
+                           Y, NZ, _p(ws), _p(out), _stream()), "level_ssim")
+    return out

@@ -50,6 +50,19 @@ the host loop with ``spectra.level_spectra_reference`` on the host tensors - and
     ./test_output/<cfg.name>____energy_spectrum_levels.csv        (``per_level``) one row ``level,bin,...`` per level and bin
     ./test_output/<cfg.name>____energy_spectrum_reverse_interpolate.csv   (+ ``..._levels_reverse_interpolate.csv``)
         with ``reverse_interpolate``: the same on the raw truth and the re-levelled SR and baseline
+
+With an ``[SSIM]`` section both loops also take the four SSIM sums per level and wind component of every field
+(``ssim.py``) - the device loop with ONE ``hip_ops.level_ssim`` launch per batch on the stored baseline (which it then
+builds for every batch), the (B, NZ, 3, 4) rows kept on the device and read at the flush points of the metrics; the host
+loop with ``ssim.level_ssim_reference`` on the host tensors - and write
+    ./test_output/<cfg.name>____ssim.csv                          one row ``field,`` + ``SSIM_COLUMNS`` per field
+    ./test_output/averages_ssim.csv                               one appended row per run: the means over the fields
+                                                                   of the first four columns
+    ./test_output/<cfg.name>____ssim_levels.csv                   (``per_level``) one row ``level,...`` per z level,
+                                                                   summed over the fields
+    ./test_output/<cfg.name>____ssim_reverse_interpolate.csv      (+ ``averages_ssim_reverse_interpolate.csv``,
+        ``..._ssim_levels_reverse_interpolate.csv``) with ``reverse_interpolate``: the same on the raw truth and the
+        re-levelled SR and baseline
 """
 from __future__ import annotations
 
@@ -66,6 +79,7 @@ import torch.nn as nn
 from .GAN_models.wind_field_GAN_3D import calculate_PSNR, wind_field_GAN_3D
 from .diagnostics import PROFILE_COLUMNS, level_sums_reference, profile_from_sums
 from .process_data import reverse_interpolate_z_axis
+from .ssim import SSIM_COLUMNS, columns_from_sums, level_ssim_reference, n_positions
 from .spectra import SPECTRUM_COLUMNS, grid_spacing, level_spectra_reference, mode_counts, spectrum_from_sums
 
 METRIC_NAMES = ("PSNR", "PSNR_trilinear", "relative_error", "pix", "trilinear_pix", "relative_error_trilinear",
@@ -242,10 +256,54 @@ def _write_spectrum_rows(f, spec, prefix):
         f.write(f"{prefix}{k}," + ",".join(str(spec[c][k]) for c in SPECTRUM_COLUMNS) + "\n")
 
 
+class _Ssim:
+    """[SSIM]: the per-field file (rows wait in ``pending`` until ``flush``, the flush points of the metrics), the sums
+    of the whole test set, (NZ, 3, 4) float64 on the device of the sums it is given, for the per-level file
+    (``levels_path``, unless None), and the row of ``averages_path``."""
+
+    def __init__(self, path, levels_path, averages_path, name, win):
+        self.levels_path, self.averages_path, self.name, self.win = levels_path, averages_path, name, win
+        self.total, self.nfields, self.npos, self.pending = None, 0, 0, []
+        self.col_sums = [0.0] * 4
+        self.fields = open(path, "w")
+        self.fields.write("field," + ",".join(SSIM_COLUMNS) + "\n")
+        _header(averages_path, "Name," + ",".join("Average " + k for k in SSIM_COLUMNS[:4]))
+
+    def add(self, names, sums, X, Y):
+        """``sums`` (B, NZ, 3, 4) of the fields ``names`` of X x Y columns each"""
+        t = sums.sum(dim=0)
+        self.total = t if self.total is None else self.total + t
+        self.npos = n_positions(X, Y, self.win)
+        self.pending.append((list(names), sums))
+
+    def flush(self):
+        for names, sums in self.pending:
+            for name, table in zip(names, sums.cpu().tolist()):
+                row = columns_from_sums(table, self.npos)
+                self.fields.write(f"{name}," + ",".join(str(v) for v in row) + "\n")
+                self.col_sums = [a + v for a, v in zip(self.col_sums, row)]
+                self.nfields += 1
+        self.pending.clear()
+
+    def close(self):
+        self.flush()
+        self.fields.close()
+        if self.nfields:
+            with open(self.averages_path, "a") as f:
+                f.write(self.name + "," + ",".join(str(v / self.nfields) for v in self.col_sums) + "\n")
+        if self.levels_path is not None:
+            with open(self.levels_path, "w") as f:
+                f.write("level," + ",".join(SSIM_COLUMNS) + "\n")
+                table = [] if self.total is None else self.total.cpu().tolist()  # the ONE read
+                for lvl, t in enumerate(table):
+                    f.write(f"{lvl}," + ",".join(str(v) for v in columns_from_sums([t], self.npos * self.nfields)) + "\n")
+
+
 def _host_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread=None, seam=None, diag=None,
-               diag_rev=None, spec=None, spec_rev=None):
+               diag_rev=None, spec=None, spec_rev=None, ssim=None, ssim_rev=None):
     """one field at a time; baseline, re-levelling and metrics on the host (the reference's loop)"""
     dev = cfg.device
+    ssim_par = _ssim_par(cfg) if ssim is not None else None
     for j, (LR, HR, Z, names, HR_raw, Z_raw) in enumerate(loader):
         TL = nn.functional.interpolate(LR[:, :3], scale_factor=(cfg.scale, cfg.scale, 1), mode="trilinear",
                                        align_corners=True)
@@ -272,6 +330,11 @@ def _host_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread
                 if spec_rev is not None:
                     spec_rev.add(level_spectra_reference(HR_raw[i:i + 1], torch.as_tensor(SR_r), torch.as_tensor(TL_r),
                                                          cfg.spectrum.window), HR.shape[2], HR.shape[3])
+                if ssim_rev is not None:
+                    ssim_rev.add(names[i:i + 1], level_ssim_reference(HR_raw[i:i + 1], torch.as_tensor(SR_r),
+                                                                      torch.as_tensor(TL_r), *ssim_par),
+                                 HR.shape[2], HR.shape[3])
+                    ssim_rev.flush()
             vals = write_metrics(HR_i, SR_i, TL_i, names[i], out, uvw)
             for k, v in zip(METRIC_NAMES, vals):
                 avg[k] += v / n
@@ -281,6 +344,9 @@ def _host_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread
                 diag.flush()
             if spec is not None:
                 spec.add(level_spectra_reference(HR_i, SR_i, TL_i, cfg.spectrum.window), HR.shape[2], HR.shape[3])
+            if ssim is not None:
+                ssim.add(names[i:i + 1], level_ssim_reference(HR_i, SR_i, TL_i, *ssim_par), HR.shape[2], HR.shape[3])
+                ssim.flush()
             if j % cfg.training.log_period == 0:
                 write_fields(LR[i], HR[i], SR_i[0], TL[i], Z[i], cfg.env.this_runs_folder, names[i],
                              HR_raw[i] if rev else None, Z_raw[i] if rev else None, None,
@@ -288,13 +354,19 @@ def _host_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread
                              None if seam_i is None else torch.sqrt(seam_i[0]))
 
 
+def _ssim_par(cfg):
+    """(window size, sigma, data range) of [SSIM]"""
+    return cfg.ssim.window_size, cfg.ssim.sigma, cfg.ssim.data_range
+
+
 def _device_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread=None, seam=None, diag=None,
-                 diag_rev=None, spec=None, spec_rev=None):
+                 diag_rev=None, spec=None, spec_rev=None, ssim=None, ssim_rev=None):
     """[EVAL] device_metrics: one generator forward and one metrics launch per batch; the (B, 7) rows wait in a device
     table and are read once per ``log_period`` batches and at the end"""
     from . import hip_ops
 
     dev, s = cfg.device, cfg.scale
+    ssim_par = _ssim_par(cfg) if ssim is not None else None
     pending = []  # (names, nvox, sums (B, 7), sums on the raw levels (B, 7) or None) of the batches not yet written
     spreads = []  # ([ENSEMBLE] write_spread) (names, mean spread (B,)) of the batches not yet written
     seams = []  # ([TILE] write_seam) (names, mean seam (B,)) of the batches not yet written
@@ -321,7 +393,7 @@ def _device_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spre
                 for name, v in zip([nm for names, _ in rows for nm in names], vals):
                     dest.write(f"{name},{v}\n")
                 rows.clear()
-        for d in (diag, diag_rev):
+        for d in (diag, diag_rev, ssim, ssim_rev):
             if d is not None:
                 d.flush()
 
@@ -336,12 +408,15 @@ def _device_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spre
         nvox = HR.shape[2] * HR.shape[3] * HR.shape[4]
         sums = hip_ops.field_metrics(HR_d, SR_d, LR=LR_d, scale=s)  # (the baseline is blended inside, never stored)
         keep = j % cfg.training.log_period == 0
-        TL_d = hip_ops.trilinear_xy(LR_d, s) if rev or keep or diag is not None or spec is not None else None
+        TL_d = (hip_ops.trilinear_xy(LR_d, s) if rev or keep or diag is not None or spec is not None or ssim is not None
+                else None)
         ncols = HR.shape[2] * HR.shape[3]
         if diag is not None:  # (the stored baseline: its divergence needs the neighbouring columns)
             diag.add(names, hip_ops.level_diagnostics(HR_d, SR_d, TL_d, gan.x, gan.y, Z_d), ncols)
         if spec is not None:  # (one launch per batch, on the stored baseline)
             spec.add(hip_ops.level_spectra(HR_d, SR_d, TL_d, cfg.spectrum.window), HR.shape[2], HR.shape[3])
+        if ssim is not None:  # (one launch per batch, on the stored baseline; the rows wait on the device)
+            ssim.add(names, hip_ops.level_ssim(HR_d, SR_d, TL_d, *ssim_par), HR.shape[2], HR.shape[3])
         sums_raw = None
         if rev:  # back onto the raw terrain-following levels of every column, metrics against the raw truth
             raw_d, zraw_d = (t.to(dev, non_blocking=True).contiguous() for t in (HR_raw, Z_raw))
@@ -351,6 +426,8 @@ def _device_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spre
                 diag_rev.add(names, hip_ops.level_diagnostics(raw_d, SR_r, TL_r, gan.x, gan.y, zraw_d), ncols)
             if spec_rev is not None:
                 spec_rev.add(hip_ops.level_spectra(raw_d, SR_r, TL_r, cfg.spectrum.window), HR.shape[2], HR.shape[3])
+            if ssim_rev is not None:
+                ssim_rev.add(names, hip_ops.level_ssim(raw_d, SR_r, TL_r, *ssim_par), HR.shape[2], HR.shape[3])
         # (per field: the sums in the order the rows are written - all of `out`, then all of `out_rev`, per batch)
         pending.append((list(names), nvox, sums, sums_raw))
         if keep:
@@ -419,6 +496,17 @@ def test(cfg, dataset_test, reverse_interpolate: bool = False):
         return _Spectrum(path(False), path(True) if sp.per_level else None, uvw,
                          grid_spacing(np.asarray(dataset_test.x), np.asarray(dataset_test.y)))
 
+    # ([SSIM]: the SSIM sums of every field, one more CSV - two with per_level - and one averages row per set of levels)
+    sm = getattr(cfg, "ssim", None)
+    with_ssim = sm is not None and sm.on
+
+    def ssim_acc(suffix):
+        def path(levels):
+            return os.path.join("./test_output", f"{cfg.name}____ssim{'_levels' if levels else ''}{suffix}.csv")
+
+        return _Ssim(path(False), path(True) if sm.per_level else None, f"./test_output/averages_ssim{suffix}.csv",
+                     cfg.name, sm.window_size)
+
     def profile_path(fields, suffix):
         return os.path.join("./test_output", f"{cfg.name}____level_profile{'_fields' if fields else ''}{suffix}.csv")
 
@@ -432,6 +520,8 @@ def test(cfg, dataset_test, reverse_interpolate: bool = False):
         diag_rev = _LevelProfile(profile_path(False, "_reverse_interpolate"), uvw, pf_rev) if with_diag and rev else None
         spec = spectrum_acc("") if with_spec else None
         spec_rev = spectrum_acc("_reverse_interpolate") if with_spec and rev else None
+        ssim = ssim_acc("") if with_ssim else None
+        ssim_rev = ssim_acc("_reverse_interpolate") if with_ssim and rev else None
         out.write(cols + "\n")
         out_rev.write(cols + "\n")
         if with_spread:
@@ -440,11 +530,11 @@ def test(cfg, dataset_test, reverse_interpolate: bool = False):
             seam.write("field,mean_seam\n")
         if cfg.eval.on and torch.device(dev).type == "cuda":
             _device_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread, seam, diag, diag_rev, spec,
-                         spec_rev)
+                         spec_rev, ssim, ssim_rev)
         else:
             _host_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread, seam, diag, diag_rev, spec,
-                       spec_rev)
-        for d in (diag, diag_rev, spec, spec_rev):
+                       spec_rev, ssim, ssim_rev)
+        for d in (diag, diag_rev, spec, spec_rev, ssim, ssim_rev):
             if d is not None:
                 d.close()
     with open("./test_output/averages.csv", "a") as f:

@@ -234,6 +234,8 @@ def _validate(cfg, gan, dataloader_val, dataset_train, it, tb, status_logger, le
         tb.add_scalars("D_loss/", D_vals, it)
         tb.add_scalars("metrics/PSNR", {k: v for k, v in M_vals.items() if "PSNR" in k}, it)
         tb.add_scalars("metrics/pix", {k: v for k, v in M_vals.items() if "pix" in k}, it)
+        if any("SSIM" in k for k in M_vals):  # ([SSIM] validation)
+            tb.add_scalars("metrics/SSIM", {k: v for k, v in M_vals.items() if "SSIM" in k}, it)
     os.makedirs(os.path.join(cfg.env.this_runs_folder, "images"), exist_ok=True)
     with open(os.path.join(cfg.env.this_runs_folder, "images", f"val_imgs__it_{it}.pkl"), "wb") as f:
         pkl.dump(imgs, f)

@@ -726,6 +726,28 @@ int wsr_spectral_energy(const float* hr, int32_t hr_c, const float* sr, int32_t 
 int wsr_spectral_energy_bwd(const float* saved, const double* gbin, int32_t B, int32_t X, int32_t Y, int32_t NZ,
                             int32_t window, float* workspace, float* dsr, void* stream);
 
+/* ---- structural similarity on horizontal planes ([SSIM]; csrc/ssim.hip) ---------------------------------------
+ * wsr_level_ssim: out (B, NZ, 3, WSR_SSIM_SUMS) doubles: per sample, z level and component c (channels 0..2 of
+ * hr (B, hr_c, X, Y, NZ), sr (B, sr_c, ...), tl (B, tl_c, ...), fp32 planar) the sums over the (X - win + 1) (Y - win + 1)
+ * valid window positions of the plane of (ssim_sr, cs_sr, ssim_tl, cs_tl), with a = hr, s = sr (then tl) of that plane:
+ *    mu_a, mu_s, S_aa, S_ss, S_as     the separable window g(i) g(j), g = taps[0 .. win) (device, fp32, sum 1), applied to
+ *                                     a, s, a a, s s, a s: along x, then along y, taps ascending, no padding
+ *    var_a = S_aa - mu_a^2, var_s = S_ss - mu_s^2, cov = S_as - mu_a mu_s
+ *    l  = (2 mu_a mu_s + c1) / (mu_a^2 + mu_s^2 + c1),   cs = (2 cov + c2) / (var_a + var_s + c2),   ssim = l cs
+ * z is never windowed.  The moments of hr are computed once for both pairs.  fp32 without contraction, the positions of a
+ * workgroup added in a fixed order in fp32, the workgroups of a plane in double: no atomics, the same bits on every call,
+ * and ssim_sr = cs_sr = the number of positions exactly when sr equals hr bit for bit (likewise tl).
+ * workspace: wsr_level_ssim_workspace_floats(B, X, Y, NZ, win) floats (0 for arguments the entry refuses): one partial
+ * row per workgroup.  A null pointer, a channel count < 3, win even or outside 3 .. WSR_SSIM_MAX_WIN, X or Y < win, a
+ * non-positive size, c1 or c2 not > 0: WSR_EINVAL; NZ > 256, B > 65535, X or Y > 32768 or X * Y * NZ >= 2^31:
+ * WSR_EUNSUPPORTED; nothing is written in either case. */
+#define WSR_SSIM_SUMS 4
+#define WSR_SSIM_MAX_WIN 15
+int64_t wsr_level_ssim_workspace_floats(int32_t B, int32_t X, int32_t Y, int32_t NZ, int32_t win);
+int wsr_level_ssim(const float* hr, int32_t hr_c, const float* sr, int32_t sr_c, const float* tl, int32_t tl_c,
+                   const float* taps, int32_t win, float c1, float c2, int32_t B, int32_t X, int32_t Y, int32_t NZ,
+                   float* workspace, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
