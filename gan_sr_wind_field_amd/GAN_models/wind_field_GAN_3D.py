@@ -719,16 +719,8 @@ class wind_field_GAN_3D(BaseGAN):
         x, y = getattr(self, "x", None), getattr(self, "y", None)
         if x is None or y is None:
             raise ValueError("level_diagnostics needs the grid coordinates: call feed_xy_niter(x, y, ...) first")
-        if not HR.is_cuda:
-            return level_sums_reference(HR, SR.detach(), _trilinear(LR, self.cfg.scale), x.to(HR.device),
-                                        y.to(HR.device), Z)
-        from .. import hip_ops
-
-        def f(t):
-            return t.detach().float().contiguous()
-
-        TL = hip_ops.trilinear_xy(f(LR), self.cfg.scale)
-        return hip_ops.level_diagnostics(f(HR), f(SR), TL, f(x.to(HR.device)), f(y.to(HR.device)), f(Z))
+        return _level_sums("level_diagnostics", level_sums_reference, self.cfg.scale, HR, SR, LR,
+                           (x.to(HR.device), y.to(HR.device), Z))
 
     # ------------------------------------------------------------------ horizontal energy spectra ([SPECTRUM])
     def level_spectra(self, HR, SR, LR, window="hann"):
@@ -738,14 +730,7 @@ class wind_field_GAN_3D(BaseGAN):
         and from ``spectra.level_spectra_reference`` on a CPU.  Reads no weights: the same inside ``ema_scope()``."""
         from ..spectra import level_spectra_reference
 
-        if not HR.is_cuda:
-            return level_spectra_reference(HR, SR.detach(), _trilinear(LR, self.cfg.scale), window)
-        from .. import hip_ops
-
-        def f(t):
-            return t.detach().float().contiguous()
-
-        return hip_ops.level_spectra(f(HR), f(SR), hip_ops.trilinear_xy(f(LR), self.cfg.scale), window)
+        return _level_sums("level_spectra", level_spectra_reference, self.cfg.scale, HR, SR, LR, (), (window,))
 
     # ------------------------------------------------------------------ structural similarity ([SSIM])
     def level_ssim(self, HR, SR, LR):
@@ -758,15 +743,8 @@ class wind_field_GAN_3D(BaseGAN):
         from ..ssim import level_ssim_reference
 
         sc = getattr(self.cfg, "ssim", None) or SsimConfig
-        par = (sc.window_size, sc.sigma, sc.data_range)
-        if not HR.is_cuda:
-            return level_ssim_reference(HR, SR.detach(), _trilinear(LR, self.cfg.scale), *par)
-        from .. import hip_ops
-
-        def f(t):
-            return t.detach().float().contiguous()
-
-        return hip_ops.level_ssim(f(HR), f(SR), hip_ops.trilinear_xy(f(LR), self.cfg.scale), *par)
+        return _level_sums("level_ssim", level_ssim_reference, self.cfg.scale, HR, SR, LR, (),
+                           (sc.window_size, sc.sigma, sc.data_range))
 
     def make_new_labels(self, it):
         """Real / fake label vectors of this iteration (reference :627-678)."""
@@ -866,6 +844,19 @@ class wind_field_GAN_3D(BaseGAN):
 def _trilinear(LR, scale):
     return nn.functional.interpolate(LR[:, :3], scale_factor=(scale, scale, 1), mode="trilinear",
                                      align_corners=True)
+
+
+def _level_sums(name, reference, scale, HR, SR, LR, tensors=(), args=()):
+    """The sums of a batch against the trilinear baseline of ``LR``, which is built here: ``reference`` on a CPU,
+    ``hip_ops.<name>`` on a GPU; ``tensors`` follow the baseline (made fp32 and contiguous for the kernel), then ``args``"""
+    if not HR.is_cuda:
+        return reference(HR, SR.detach(), _trilinear(LR, scale), *tensors, *args)
+    from .. import hip_ops
+
+    def f(t):
+        return t.detach().float().contiguous()
+
+    return getattr(hip_ops, name)(f(HR), f(SR), hip_ops.trilinear_xy(f(LR), scale), *map(f, tensors), *args)
 
 
 def calculate_PSNR(HR: torch.Tensor, fake_HR: torch.Tensor, max_diff_squared=torch.tensor(4.0),

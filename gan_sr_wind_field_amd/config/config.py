@@ -52,7 +52,7 @@ import math
 from configparser import ConfigParser
 from typing import Any, List, Sequence, Tuple
 
-_B, _I, _F, _S = "bool", "int", "float", "str"
+_B, _I, _F, _S, _W = "bool", "int", "float", "str", "word"  # (word: a lower-cased string)
 
 
 def safe_list_from_string(text, target_type: type) -> list:
@@ -81,6 +81,8 @@ def _read(section, key: str, kind: str):
         return section.getfloat(key)
     if kind == "intlist":
         return safe_list_from_string(section.get(key), int)
+    if kind == _W:
+        return section.get(key).strip().lower()
     return section.get(key)
 
 
@@ -298,20 +300,43 @@ class DistConfig(IniConfig):
                 setattr(self, key, val)
 
 
-class DataConfig(IniConfig):
+class OptionalSection(IniConfig):
+    """An extension section.  Absent from the file = the class defaults with ``present`` False, and no text in
+    ``asINI``; present = printed by ``asINI`` unless ``_printed`` is False."""
+
+    _section: str = ""
+    _printed: bool = True
+    present: bool = False
+
+    def load(self, section) -> None:
+        """``section`` None (not in the file) restores the defaults and switches the section off."""
+        self.present = section is not None
+        for key, kind in self._schema:
+            try:
+                val = None if section is None else _read(section, key, kind)
+            except ValueError:
+                what = {_B: "True or False", _I: "an integer", _F: "a number"}[kind]
+                raise ValueError(f"[{self._section}] {key} must be {what}, not {section.get(key)!r}") from None
+            setattr(self, key, getattr(type(self), key) if val is None else val)
+
+    def validate(self) -> None:
+        pass
+
+    def __str__(self) -> str:
+        return f"[{self._section}]\n" + "".join(f"{k} = {getattr(self, k)}\n" for k, _ in self._schema)
+
+
+class DataConfig(OptionalSection):
     """[DATA] (extension): input-pipeline settings; absent section = defaults (not printed by ``asINI``)."""
 
     device_resident: bool = False
+    _section, _printed = "DATA", False
     _schema = (("device_resident", _B),)
 
-    def setDataConfig(self, section):
-        """``section`` None (no [DATA] in the file) restores the defaults."""
-        for key, kind in self._schema:
-            val = None if section is None else _read(section, key, kind)
-            setattr(self, key, getattr(DataConfig, key) if val is None else val)
+    setDataConfig = OptionalSection.load
 
 
-class GradClipConfig(IniConfig):
+class GradClipConfig(OptionalSection):
     """[GRAD_CLIP] (extension): gradient-norm clipping in the optimizer steps (tools/table_adam.py); absent section =
     defaults, all off, and not printed by ``asINI``.  The generator's bound is [GENERATOR] max_norm."""
 
@@ -319,15 +344,11 @@ class GradClipConfig(IniConfig):
     clip_discriminator: bool = False
     max_norm_discriminator: float = 1.0
     log_grad_norms: bool = False
+    _section = "GRAD_CLIP"
     _schema = (("clip_generator", _B), ("clip_discriminator", _B), ("max_norm_discriminator", _F),
                ("log_grad_norms", _B))
 
-    def setGradClipConfig(self, section):
-        """``section`` None (no [GRAD_CLIP] in the file) restores the defaults."""
-        self.present = section is not None
-        for key, kind in self._schema:
-            val = None if section is None else _read(section, key, kind)
-            setattr(self, key, getattr(GradClipConfig, key) if val is None else val)
+    setGradClipConfig = OptionalSection.load
 
     def validate(self, max_norm_generator) -> None:
         """every bound that clips must be > 0 and finite"""
@@ -336,28 +357,20 @@ class GradClipConfig(IniConfig):
             if on and not (bound is not None and bound > 0 and math.isfinite(bound)):
                 raise ValueError(f"{key} must be > 0 and finite when clipping is on, not {bound}")
 
-    def __str__(self) -> str:
-        return "[GRAD_CLIP]\n" + "".join(f"{k} = {getattr(self, k)}\n" for k, _ in self._schema)
 
-
-class EmaConfig(IniConfig):
+class EmaConfig(OptionalSection):
     """[EMA] (extension): moving average ``e <- decay * e + (1 - decay) * w`` of the generator's weights after every
     generator step; absent section = off, and not printed by ``asINI``.  Generator steps at iterations before
     ``start_iter`` copy (``e = w``)."""
 
-    present: bool = False
     decay: float = 0.999
     start_iter: int = 0
     validate_with_ema: bool = True
     test_with_ema: bool = True
+    _section = "EMA"
     _schema = (("decay", _F), ("start_iter", _I), ("validate_with_ema", _B), ("test_with_ema", _B))
 
-    def setEmaConfig(self, section):
-        """``section`` None (no [EMA] in the file) restores the defaults and switches the average off."""
-        self.present = section is not None
-        for key, kind in self._schema:
-            val = None if section is None else _read(section, key, kind)
-            setattr(self, key, getattr(EmaConfig, key) if val is None else val)
+    setEmaConfig = OptionalSection.load
 
     def validate(self) -> None:
         if not self.present:
@@ -371,28 +384,20 @@ class EmaConfig(IniConfig):
         """the factor of the generator step of iteration ``it``"""
         return self.decay if int(it) >= self.start_iter else 0.0
 
-    def __str__(self) -> str:
-        return "[EMA]\n" + "".join(f"{k} = {getattr(self, k)}\n" for k, _ in self._schema)
 
-
-class EvalConfig(IniConfig):
+class EvalConfig(OptionalSection):
     """[EVAL] (extension): device-side evaluation (csrc/eval_metrics.hip); absent section = off, and not printed by
     ``asINI``.  ``device_metrics``: the validation batches and ``run.py --test`` take the trilinear baseline and the
     error sums from the HIP kernels; ``batch_size``: fields per generator forward / metrics launch of ``--test``;
     ``reverse_interpolate``: ``--test`` also writes the ``*_reverse_interpolate.csv`` files."""
 
-    present: bool = False
     device_metrics: bool = True
     batch_size: int = 8
     reverse_interpolate: bool = False
+    _section = "EVAL"
     _schema = (("device_metrics", _B), ("batch_size", _I), ("reverse_interpolate", _B))
 
-    def setEvalConfig(self, section):
-        """``section`` None (no [EVAL] in the file) restores the defaults and switches the section off."""
-        self.present = section is not None
-        for key, kind in self._schema:
-            val = None if section is None else _read(section, key, kind)
-            setattr(self, key, getattr(EvalConfig, key) if val is None else val)
+    setEvalConfig = OptionalSection.load
 
     def validate(self, interpolate_z) -> None:
         if not self.present:
@@ -408,26 +413,18 @@ class EvalConfig(IniConfig):
         """the device kernels replace the host evaluation"""
         return bool(self.present and self.device_metrics)
 
-    def __str__(self) -> str:
-        return "[EVAL]\n" + "".join(f"{k} = {getattr(self, k)}\n" for k, _ in self._schema)
 
-
-class EnsembleConfig(IniConfig):
+class EnsembleConfig(OptionalSection):
     """[ENSEMBLE] (extension): geometric self-ensemble of ``run.py --test`` (ensemble.py, csrc/ensemble.hip); absent
     section = off, and not printed by ``asINI``.  ``members``: 1, 2, 4 or 8 symmetries of the square the generator is
     averaged over; ``write_spread``: ``--test`` also writes ``<name>____ensemble_spread.csv`` and pickles ``SR_spread``."""
 
-    present: bool = False
     members: int = 8
     write_spread: bool = False
+    _section = "ENSEMBLE"
     _schema = (("members", _I), ("write_spread", _B))
 
-    def setEnsembleConfig(self, section):
-        """``section`` None (no [ENSEMBLE] in the file) restores the defaults and switches the section off."""
-        self.present = section is not None
-        for key, kind in self._schema:
-            val = None if section is None else _read(section, key, kind)
-            setattr(self, key, getattr(EnsembleConfig, key) if val is None else val)
+    setEnsembleConfig = OptionalSection.load
 
     def validate(self) -> None:
         if not self.present:
@@ -435,34 +432,22 @@ class EnsembleConfig(IniConfig):
         if self.members not in (1, 2, 4, 8):
             raise ValueError(f"[ENSEMBLE] members must be 1, 2, 4 or 8, not {self.members}")
 
-    def __str__(self) -> str:
-        return "[ENSEMBLE]\n" + "".join(f"{k} = {getattr(self, k)}\n" for k, _ in self._schema)
 
-
-class TileConfig(IniConfig):
+class TileConfig(OptionalSection):
     """[TILE] (extension): tiled whole-domain inference of ``run.py --test`` (tiling.py, csrc/tiling.hip); absent section =
     off, and not printed by ``asINI``.  ``tile`` (required): LR voxels per tile side in x and y, an axis shorter than
     this is one tile; ``overlap``: LR voxels neighbouring tiles share at least, 0 .. tile // 2; ``tiles_per_forward``:
     tiles stacked into one generator forward; ``write_seam``: ``--test`` also writes ``<name>____tile_seam.csv`` and
     pickles ``SR_seam``."""
 
-    present: bool = False
     tile: int = None
     overlap: int = 4
     tiles_per_forward: int = 8
     write_seam: bool = False
+    _section = "TILE"
     _schema = (("tile", _I), ("overlap", _I), ("tiles_per_forward", _I), ("write_seam", _B))
 
-    def setTileConfig(self, section):
-        """``section`` None (no [TILE] in the file) restores the defaults and switches the section off."""
-        self.present = section is not None
-        for key, kind in self._schema:
-            try:
-                val = None if section is None else _read(section, key, kind)
-            except ValueError:
-                raise ValueError(f"[TILE] {key} must be {'True or False' if kind == _B else 'an integer'}, not "
-                                 f"{section.get(key)!r}") from None
-            setattr(self, key, getattr(TileConfig, key) if val is None else val)
+    setTileConfig = OptionalSection.load
 
     def validate(self) -> None:
         if not self.present:
@@ -476,30 +461,19 @@ class TileConfig(IniConfig):
         if self.tiles_per_forward < 1:
             raise ValueError(f"[TILE] tiles_per_forward must be >= 1, not {self.tiles_per_forward}")
 
-    def __str__(self) -> str:
-        return "[TILE]\n" + "".join(f"{k} = {getattr(self, k)}\n" for k, _ in self._schema)
 
-
-class DiagnosticsConfig(IniConfig):
+class DiagnosticsConfig(OptionalSection):
     """[DIAGNOSTICS] (extension): per-level evaluation diagnostics of ``run.py --test`` (diagnostics.py,
     csrc/diagnostics.hip); absent section = off, and not printed by ``asINI``.  ``level_profile``: ``--test`` also writes
     ``<name>____level_profile.csv``, one row per z level; ``per_field``: ... and ``<name>____level_profile_fields.csv``,
     one row per field and level."""
 
-    present: bool = False
     level_profile: bool = True
     per_field: bool = False
+    _section = "DIAGNOSTICS"
     _schema = (("level_profile", _B), ("per_field", _B))
 
-    def setDiagnosticsConfig(self, section):
-        """``section`` None (no [DIAGNOSTICS] in the file) restores the defaults and switches the section off."""
-        self.present = section is not None
-        for key, kind in self._schema:
-            try:
-                val = None if section is None else _read(section, key, kind)
-            except ValueError:
-                raise ValueError(f"[DIAGNOSTICS] {key} must be True or False, not {section.get(key)!r}") from None
-            setattr(self, key, getattr(DiagnosticsConfig, key) if val is None else val)
+    setDiagnosticsConfig = OptionalSection.load
 
     def validate(self) -> None:
         if not self.present:
@@ -513,34 +487,21 @@ class DiagnosticsConfig(IniConfig):
         """``--test`` takes the per-level sums and writes the profile"""
         return bool(self.present and self.level_profile)
 
-    def __str__(self) -> str:
-        return "[DIAGNOSTICS]\n" + "".join(f"{k} = {getattr(self, k)}\n" for k, _ in self._schema)
 
-
-class SpectrumConfig(IniConfig):
+class SpectrumConfig(OptionalSection):
     """[SPECTRUM] (extension): horizontal energy spectra of ``run.py --test`` (spectra.py, csrc/spectra.hip); absent
     section = off, and not printed by ``asINI``.  ``energy_spectrum``: ``--test`` also writes
     ``<name>____energy_spectrum.csv``, one row per wavenumber bin; ``per_level``: ... and
     ``<name>____energy_spectrum_levels.csv``, one row per z level and bin; ``window``: ``hann`` or ``none``, the taper
     of the detrended planes."""
 
-    present: bool = False
     energy_spectrum: bool = True
     per_level: bool = False
     window: str = "hann"
-    _schema = (("energy_spectrum", _B), ("per_level", _B))
+    _section = "SPECTRUM"
+    _schema = (("energy_spectrum", _B), ("per_level", _B), ("window", _W))
 
-    def setSpectrumConfig(self, section):
-        """``section`` None (no [SPECTRUM] in the file) restores the defaults and switches the section off."""
-        self.present = section is not None
-        for key, kind in self._schema:
-            try:
-                val = None if section is None else _read(section, key, kind)
-            except ValueError:
-                raise ValueError(f"[SPECTRUM] {key} must be True or False, not {section.get(key)!r}") from None
-            setattr(self, key, getattr(SpectrumConfig, key) if val is None else val)
-        raw = None if section is None else section.get("window")
-        self.window = SpectrumConfig.window if raw is None else raw.strip().lower()
+    setSpectrumConfig = OptionalSection.load
 
     def validate(self) -> None:
         if not self.present:
@@ -556,12 +517,8 @@ class SpectrumConfig(IniConfig):
         """``--test`` takes the spectral sums and writes the spectrum"""
         return bool(self.present and self.energy_spectrum)
 
-    def __str__(self) -> str:
-        return ("[SPECTRUM]\n" + "".join(f"{k} = {getattr(self, k)}\n" for k, _ in self._schema)
-                + f"window = {self.window}\n")
 
-
-class SpectralLossConfig(IniConfig):
+class SpectralLossConfig(OptionalSection):
     """[SPECTRAL_LOSS] (extension): an energy-spectrum term of the generator loss (spectral_loss.py,
     csrc/spectral_loss.hip); absent section = off, and not printed by ``asINI``.  ``weight`` (required, > 0: there is no
     reference default to inherit) multiplies ``L_spec``, the mean over samples, levels and wavenumber bins of
@@ -570,28 +527,15 @@ class SpectralLossConfig(IniConfig):
     k_min <= k_max < NK of the training patch, checked at the first batch) select the bins; ``rel_floor`` >= 0: the floor
     is that fraction of the level's total e_hr."""
 
-    present: bool = False
     weight: float = None
     window: str = "hann"
     k_min: int = 1
     k_max: int = 0
     rel_floor: float = 1e-6
-    _schema = (("weight", _F), ("window", None), ("k_min", _I), ("k_max", _I), ("rel_floor", _F))
+    _section = "SPECTRAL_LOSS"
+    _schema = (("weight", _F), ("window", _W), ("k_min", _I), ("k_max", _I), ("rel_floor", _F))
 
-    def setSpectralLossConfig(self, section):
-        """``section`` None (no [SPECTRAL_LOSS] in the file) restores the defaults and switches the section off."""
-        self.present = section is not None
-        for key, kind in self._schema:
-            if kind is None:
-                raw = None if section is None else section.get(key)
-                val = None if raw is None else raw.strip().lower()
-            else:
-                try:
-                    val = None if section is None else _read(section, key, kind)
-                except ValueError:
-                    raise ValueError(f"[SPECTRAL_LOSS] {key} must be {'an integer' if kind == _I else 'a number'}, not "
-                                     f"{section.get(key)!r}") from None
-            setattr(self, key, getattr(SpectralLossConfig, key) if val is None else val)
+    setSpectralLossConfig = OptionalSection.load
 
     def validate(self) -> None:
         if not self.present:
@@ -614,36 +558,21 @@ class SpectralLossConfig(IniConfig):
         """the generator loss carries the spectral term"""
         return bool(self.present)
 
-    def __str__(self) -> str:
-        return "[SPECTRAL_LOSS]\n" + "".join(f"{k} = {getattr(self, k)}\n" for k, _ in self._schema)
 
-
-class DegradationConfig(IniConfig):
+class DegradationConfig(OptionalSection):
     """[DEGRADATION] (extension): anti-aliased LR inputs (degradation.py, csrc/data_degrade.hip); absent section = off -
     LR is every ``scale``-th HR column, as in the reference - and never printed by ``asINI``.  ``kernel`` (required):
     ``box`` (a width-``scale`` mean centred on the sample point) or ``gaussian``; ``sigma`` (gaussian only, required
     there: no reference default to inherit): in HR grid cells, 0 < sigma <= 10; ``channels``: ``all`` LR channels, or
     ``wind`` - channels 0..2 only, the others stay point-sampled."""
 
-    present: bool = False
     kernel: str = None
     sigma: float = None
     channels: str = "all"
-    _schema = (("kernel", None), ("sigma", _F), ("channels", None))
+    _section, _printed = "DEGRADATION", False
+    _schema = (("kernel", _W), ("sigma", _F), ("channels", _W))
 
-    def setDegradationConfig(self, section):
-        """``section`` None (no [DEGRADATION] in the file) restores the defaults and switches the section off."""
-        self.present = section is not None
-        for key, kind in self._schema:
-            if kind is None:
-                raw = None if section is None else section.get(key)
-                val = None if raw is None else raw.strip().lower()
-            else:
-                try:
-                    val = None if section is None else _read(section, key, kind)
-                except ValueError:
-                    raise ValueError(f"[DEGRADATION] {key} must be a number, not {section.get(key)!r}") from None
-            setattr(self, key, getattr(DegradationConfig, key) if val is None else val)
+    setDegradationConfig = OptionalSection.load
 
     def validate(self, scale) -> None:
         if not self.present:
@@ -675,11 +604,8 @@ class DegradationConfig(IniConfig):
         from ..degradation import DegradationSpec
         return DegradationSpec(self.kernel, self.sigma if self.kernel == "gaussian" else None, self.channels)
 
-    def __str__(self) -> str:
-        return "[DEGRADATION]\n" + "".join(f"{k} = {getattr(self, k)}\n" for k, _ in self._schema)
 
-
-class SsimConfig(IniConfig):
+class SsimConfig(OptionalSection):
     """[SSIM] (extension): structural similarity on horizontal planes in ``run.py --test`` and in validation epochs
     (ssim.py, csrc/ssim.hip); absent section = off, and never printed by ``asINI``.  ``window_size``: the side of the
     gaussian window, odd, 3 .. 15; ``sigma`` > 0: its standard deviation in HR grid cells; ``data_range`` > 0: the range
@@ -687,24 +613,15 @@ class SsimConfig(IniConfig):
     ``<name>____ssim_levels.csv``; ``validation``: validation epochs add ``val_SSIM`` and ``Trilinear_SSIM`` to the
     metrics."""
 
-    present: bool = False
     window_size: int = 11
     sigma: float = 1.5
     data_range: float = 2.0
     per_level: bool = False
     validation: bool = True
+    _section, _printed = "SSIM", False
     _schema = (("window_size", _I), ("sigma", _F), ("data_range", _F), ("per_level", _B), ("validation", _B))
 
-    def setSsimConfig(self, section):
-        """``section`` None (no [SSIM] in the file) restores the defaults and switches the section off."""
-        self.present = section is not None
-        for key, kind in self._schema:
-            try:
-                val = None if section is None else _read(section, key, kind)
-            except ValueError:
-                what = {_I: "an integer", _F: "a number", _B: "True or False"}[kind]
-                raise ValueError(f"[SSIM] {key} must be {what}, not {section.get(key)!r}") from None
-            setattr(self, key, getattr(SsimConfig, key) if val is None else val)
+    setSsimConfig = OptionalSection.load
 
     def validate(self) -> None:
         if not self.present:
@@ -721,9 +638,6 @@ class SsimConfig(IniConfig):
     def on(self) -> bool:
         """``--test`` takes the SSIM sums and writes the SSIM files"""
         return bool(self.present)
-
-    def __str__(self) -> str:
-        return "[SSIM]\n" + "".join(f"{k} = {getattr(self, k)}\n" for k, _ in self._schema)
 
 
 class Config(IniConfig):
@@ -766,6 +680,12 @@ class Config(IniConfig):
     is_download: bool
     slurm_array_id: int = 1
 
+    # the optional sections in the order they load and print: (attribute, what its ``validate`` is given)
+    _optional = (("data", None), ("grad_clip", lambda c: c.generator.max_norm), ("ema", None),
+                 ("eval", lambda c: c.gan_config.interpolate_z), ("ensemble", None), ("tile", None),
+                 ("diagnostics", None), ("spectrum", None), ("spectral_loss", None),
+                 ("degradation", lambda c: c.scale), ("ssim", None))
+
     def __init__(self, ini_path):
         parser = ConfigParser(allow_no_value=True)
         parser.read(ini_path)
@@ -783,27 +703,10 @@ class Config(IniConfig):
                 setattr(self, attr, None)
         if parser.has_section("DIST"):
             self.dist.setDistConfig(parser["DIST"])
-        self.data.setDataConfig(parser["DATA"] if parser.has_section("DATA") else None)
-        self.grad_clip.setGradClipConfig(parser["GRAD_CLIP"] if parser.has_section("GRAD_CLIP") else None)
-        self.grad_clip.validate(self.generator.max_norm)
-        self.ema.setEmaConfig(parser["EMA"] if parser.has_section("EMA") else None)
-        self.ema.validate()
-        self.eval.setEvalConfig(parser["EVAL"] if parser.has_section("EVAL") else None)
-        self.eval.validate(self.gan_config.interpolate_z)
-        self.ensemble.setEnsembleConfig(parser["ENSEMBLE"] if parser.has_section("ENSEMBLE") else None)
-        self.ensemble.validate()
-        self.tile.setTileConfig(parser["TILE"] if parser.has_section("TILE") else None)
-        self.tile.validate()
-        self.diagnostics.setDiagnosticsConfig(parser["DIAGNOSTICS"] if parser.has_section("DIAGNOSTICS") else None)
-        self.diagnostics.validate()
-        self.spectrum.setSpectrumConfig(parser["SPECTRUM"] if parser.has_section("SPECTRUM") else None)
-        self.spectrum.validate()
-        self.spectral_loss.setSpectralLossConfig(parser["SPECTRAL_LOSS"] if parser.has_section("SPECTRAL_LOSS") else None)
-        self.spectral_loss.validate()
-        self.degradation.setDegradationConfig(parser["DEGRADATION"] if parser.has_section("DEGRADATION") else None)
-        self.degradation.validate(self.scale)
-        self.ssim.setSsimConfig(parser["SSIM"] if parser.has_section("SSIM") else None)
-        self.ssim.validate()
+        for attr, given in self._optional:
+            sec = getattr(self, attr)
+            sec.load(parser[sec._section] if parser.has_section(sec._section) else None)
+            sec.validate(*(() if given is None else (given(self),)))
 
     def setBaseConfig(self, base):
         self.name = base.get("name")
@@ -831,20 +734,8 @@ class Config(IniConfig):
         for sec in sections:
             if sec is not None:
                 out += "\n" + str(sec)
-        if getattr(self.grad_clip, "present", False):  # (absent: the text of a file without the extension, unchanged)
-            out += "\n" + str(self.grad_clip)
-        if getattr(self.ema, "present", False):
-            out += "\n" + str(self.ema)
-        if getattr(self.eval, "present", False):
-            out += "\n" + str(self.eval)
-        if getattr(self.ensemble, "present", False):
-            out += "\n" + str(self.ensemble)
-        if getattr(self.tile, "present", False):
-            out += "\n" + str(self.tile)
-        if getattr(self.diagnostics, "present", False):
-            out += "\n" + str(self.diagnostics)
-        if getattr(self.spectrum, "present", False):
-            out += "\n" + str(self.spectrum)
-        if getattr(self.spectral_loss, "present", False):
-            out += "\n" + str(self.spectral_loss)
+        for attr, _ in self._optional:  # (absent: the text of a file without the extension, unchanged)
+            sec = getattr(self, attr)
+            if sec.present and sec._printed:
+                out += "\n" + str(sec)
         return out

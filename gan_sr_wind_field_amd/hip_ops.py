@@ -1119,6 +1119,30 @@ def _planar5(name: str, what: str, t: Tensor, min_c: int = 1) -> None:
                          f"{t.dtype} {tuple(t.shape)}")
 
 
+def _same_grid(name: str, HR: Tensor, **fields: Tensor):
+    """``HR`` and ``fields`` (by name) are planar fp32 with at least 3 channels, the fields on HR's grid -> (B, X, Y, NZ)"""
+    for what, t in (("HR", HR), *fields.items()):
+        _planar5(name, what, t, 3)
+    B, _, X, Y, NZ = HR.shape
+    for what, t in fields.items():
+        if (t.shape[0],) + tuple(t.shape[2:]) != (B, X, Y, NZ):
+            raise ValueError(f"{name}: {what} {tuple(t.shape)} does not match HR {tuple(HR.shape)}")
+    return B, X, Y, NZ
+
+
+def _sums_out(name: str, out: Optional[Tensor], shape: tuple, device) -> Tensor:
+    """``out`` or, for None, a new float64 tensor of ``shape``: what the reductions write their sums into"""
+    if out is None:
+        return torch.empty(shape, dtype=torch.float64, device=device)
+    if out.dtype != torch.float64 or tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError(f"{name} wants out as a contiguous float64 {shape} tensor, got {out.dtype} {tuple(out.shape)}")
+    return out
+
+
+def _workspace(floats: int, device) -> Tensor:
+    return torch.empty(int(floats), dtype=torch.float32, device=device)
+
+
 def trilinear_xy(LR: Tensor, s: int) -> Tensor:
     """The trilinear baseline ``F.interpolate(LR[:, :3], scale_factor=(s, s, 1), mode="trilinear",
     align_corners=True)`` in one launch: ``LR`` fp32 (B, Cin >= 3, Xl, Yl, NZ) -> (B, 3, Xl * s, Yl * s, NZ); only
@@ -1145,27 +1169,15 @@ def field_metrics(HR: Tensor, SR: Tensor, *, LR: Optional[Tensor] = None, scale:
     if (TL is None) == (LR is None) or (LR is not None and scale is None):
         raise ValueError("field_metrics wants either TL= or LR= and scale=")
     _need_cuda(HR, SR, LR, TL, out)
-    _planar5("field_metrics", "HR", HR, 3)
-    _planar5("field_metrics", "SR", SR, 3)
-    B, _, X, Y, NZ = HR.shape
-    if (SR.shape[0],) + tuple(SR.shape[2:]) != (B, X, Y, NZ):
-        raise ValueError(f"field_metrics: SR {tuple(SR.shape)} does not match HR {tuple(HR.shape)}")
+    B, X, Y, NZ = _same_grid("field_metrics", HR, SR=SR, **({} if TL is None else {"TL": TL}))
     s = 0
-    if TL is not None:
-        _planar5("field_metrics", "TL", TL, 3)
-        if (TL.shape[0],) + tuple(TL.shape[2:]) != (B, X, Y, NZ):
-            raise ValueError(f"field_metrics: TL {tuple(TL.shape)} does not match HR {tuple(HR.shape)}")
-    else:
+    if TL is None:
         _planar5("field_metrics", "LR", LR, 3)
         s = int(scale)
         if s < 1 or (LR.shape[0], LR.shape[2] * s, LR.shape[3] * s, LR.shape[4]) != (B, X, Y, NZ):
             raise ValueError(f"field_metrics: LR {tuple(LR.shape)} x{s} does not match HR {tuple(HR.shape)}")
-    if out is None:
-        out = torch.empty((B, FIELD_METRICS_SUMS), dtype=torch.float64, device=HR.device)
-    elif out.dtype != torch.float64 or tuple(out.shape) != (B, FIELD_METRICS_SUMS) or not out.is_contiguous():
-        raise ValueError(f"field_metrics wants out as a contiguous float64 ({B}, 7) tensor, got {out.dtype} "
-                         f"{tuple(out.shape)}")
-    partials = torch.empty(B * FIELD_METRICS_MAX_ROWS * FIELD_METRICS_SUMS, dtype=torch.float32, device=HR.device)
+    out = _sums_out("field_metrics", out, (B, FIELD_METRICS_SUMS), HR.device)
+    partials = _workspace(B * FIELD_METRICS_MAX_ROWS * FIELD_METRICS_SUMS, HR.device)
     check(_lib.lib().wsr_field_metrics(_p(HR), HR.shape[1], _p(SR), SR.shape[1], _p(TL), 0 if TL is None else TL.shape[1],
                                        _p(LR), 0 if LR is None else LR.shape[1], s, B, X, Y, NZ, _p(partials), _p(out),
                                        _stream()), "field_metrics")
@@ -1336,14 +1348,8 @@ def level_diagnostics(HR: Tensor, SR: Tensor, TL: Tensor, x: Tensor, y: Tensor, 
     pass, no atomics: the same bits on every call.  ``out``: a float64 (B, NZ, 15) slice to write into
     (``wsr_level_diagnostics``)."""
     _need_cuda(HR, SR, TL, x, y, Z, out)
-    _planar5("level_diagnostics", "HR", HR, 3)
-    _planar5("level_diagnostics", "SR", SR, 3)
-    _planar5("level_diagnostics", "TL", TL, 3)
+    B, X, Y, NZ = _same_grid("level_diagnostics", HR, SR=SR, TL=TL)
     _planar5("level_diagnostics", "Z", Z)
-    B, _, X, Y, NZ = HR.shape
-    for name, t in (("SR", SR), ("TL", TL)):
-        if (t.shape[0],) + tuple(t.shape[2:]) != (B, X, Y, NZ):
-            raise ValueError(f"level_diagnostics: {name} {tuple(t.shape)} does not match HR {tuple(HR.shape)}")
     if tuple(Z.shape) != (B, 1, X, Y, NZ):
         raise ValueError(f"level_diagnostics wants Z ({B}, 1, {X}, {Y}, {NZ}), got {tuple(Z.shape)}")
     for name, t, n in (("x", x, X), ("y", y, Y)):
@@ -1353,13 +1359,9 @@ def level_diagnostics(HR: Tensor, SR: Tensor, TL: Tensor, x: Tensor, y: Tensor, 
     if NZ > LEVEL_DIAG_MAX_NZ or B > 65535 or X > 32768 or Y > 32768 or X * Y * NZ >= 2 ** 31:
         raise ValueError(f"level_diagnostics: at most {LEVEL_DIAG_MAX_NZ} levels, 65535 samples, 32768 points in x and y "
                          f"and 2^31 - 1 voxels per sample, not B = {B}, X = {X}, Y = {Y}, NZ = {NZ}")
-    if out is None:
-        out = torch.empty((B, NZ, LEVEL_DIAG_SUMS), dtype=torch.float64, device=HR.device)
-    elif out.dtype != torch.float64 or tuple(out.shape) != (B, NZ, LEVEL_DIAG_SUMS) or not out.is_contiguous():
-        raise ValueError(f"level_diagnostics wants out as a contiguous float64 ({B}, {NZ}, {LEVEL_DIAG_SUMS}) tensor, got "
-                         f"{out.dtype} {tuple(out.shape)}")
+    out = _sums_out("level_diagnostics", out, (B, NZ, LEVEL_DIAG_SUMS), HR.device)
     L = _lib.lib()
-    ws = torch.empty(int(L.wsr_level_diagnostics_workspace_floats(B, X, Y, NZ)), dtype=torch.float32, device=HR.device)
+    ws = _workspace(L.wsr_level_diagnostics_workspace_floats(B, X, Y, NZ), HR.device)
     check(L.wsr_level_diagnostics(_p(HR), HR.shape[1], _p(SR), SR.shape[1], _p(TL), TL.shape[1], _p(Z), _p(x), _p(y), B,
                                   X, Y, NZ, _p(ws), _p(out), _stream()), "level_diagnostics")
     return out
@@ -1380,13 +1382,7 @@ def level_spectra(HR: Tensor, SR: Tensor, TL: Tensor, window: str = "hann", out:
     the detrended, windowed (``window``: ``hann`` or ``none``) planes; NK = ``spectra.n_bins(X, Y)``.  No atomics: the
     same bits on every call.  ``out``: a float64 (B, NZ, NK, 5) slice to write into (``wsr_level_spectra``)."""
     _need_cuda(HR, SR, TL, out)
-    _planar5("level_spectra", "HR", HR, 3)
-    _planar5("level_spectra", "SR", SR, 3)
-    _planar5("level_spectra", "TL", TL, 3)
-    B, _, X, Y, NZ = HR.shape
-    for name, t in (("SR", SR), ("TL", TL)):
-        if (t.shape[0],) + tuple(t.shape[2:]) != (B, X, Y, NZ):
-            raise ValueError(f"level_spectra: {name} {tuple(t.shape)} does not match HR {tuple(HR.shape)}")
+    B, X, Y, NZ = _same_grid("level_spectra", HR, SR=SR, TL=TL)
     if window not in SPECTRUM_WINDOWS:
         raise ValueError(f"level_spectra: window must be one of {tuple(SPECTRUM_WINDOWS)} (codes 0, 1), not {window!r}")
     if X > SPECTRUM_MAX_XY or Y > SPECTRUM_MAX_XY or B > 65535 or NZ > 65535 or X * Y * NZ >= 2 ** 31:
@@ -1394,12 +1390,8 @@ def level_spectra(HR: Tensor, SR: Tensor, TL: Tensor, window: str = "hann", out:
                          f"2^31 - 1 voxels per sample, not B = {B}, X = {X}, Y = {Y}, NZ = {NZ}")
     L = _lib.lib()
     NK = int(L.wsr_level_spectra_bins(X, Y))
-    if out is None:
-        out = torch.empty((B, NZ, NK, SPECTRUM_SUMS), dtype=torch.float64, device=HR.device)
-    elif out.dtype != torch.float64 or tuple(out.shape) != (B, NZ, NK, SPECTRUM_SUMS) or not out.is_contiguous():
-        raise ValueError(f"level_spectra wants out as a contiguous float64 ({B}, {NZ}, {NK}, {SPECTRUM_SUMS}) tensor, got "
-                         f"{out.dtype} {tuple(out.shape)}")
-    ws = torch.empty(int(L.wsr_level_spectra_workspace_floats(B, X, Y, NZ)), dtype=torch.float32, device=HR.device)
+    out = _sums_out("level_spectra", out, (B, NZ, NK, SPECTRUM_SUMS), HR.device)
+    ws = _workspace(L.wsr_level_spectra_workspace_floats(B, X, Y, NZ), HR.device)
     check(L.wsr_level_spectra(_p(HR), HR.shape[1], _p(SR), SR.shape[1], _p(TL), TL.shape[1], B, X, Y, NZ,
                               SPECTRUM_WINDOWS[window], _p(ws), _p(out), _stream()), "level_spectra")
     return out
@@ -1418,10 +1410,10 @@ class _SpectralEnergy(torch.autograd.Function):
         L = _lib.lib()
         NK = int(L.wsr_level_spectra_bins(X, Y))
         out = torch.empty((B, NZ, NK, 2), dtype=torch.float64, device=sr.device)
-        ws = torch.empty(int(L.wsr_spectral_energy_workspace_floats(B, X, Y, NZ)), dtype=torch.float32, device=sr.device)
+        ws = _workspace(L.wsr_spectral_energy_workspace_floats(B, X, Y, NZ), sr.device)
         saved = None
         if ctx.needs_input_grad[1]:
-            saved = torch.empty(int(L.wsr_spectral_energy_saved_floats(B, X, Y, NZ)), dtype=torch.float32, device=sr.device)
+            saved = _workspace(L.wsr_spectral_energy_saved_floats(B, X, Y, NZ), sr.device)
         check(L.wsr_spectral_energy(_p(hr), hr.shape[1], _p(sr), sr.shape[1], B, X, Y, NZ, window, _p(ws), _p(saved),
                                     _p(out), _stream()), "spectral_energy")
         ctx.meta = (tuple(sr.shape), window)
@@ -1437,7 +1429,7 @@ class _SpectralEnergy(torch.autograd.Function):
         (B, C_, X, Y, NZ), window = ctx.meta
         L = _lib.lib()
         gbin = g[..., 1].to(torch.float64).contiguous()
-        ws = torch.empty(int(L.wsr_spectral_energy_workspace_floats(B, X, Y, NZ)), dtype=torch.float32, device=g.device)
+        ws = _workspace(L.wsr_spectral_energy_workspace_floats(B, X, Y, NZ), g.device)
         dsr = torch.empty((B, 3, X, Y, NZ), dtype=torch.float32, device=g.device)
         check(L.wsr_spectral_energy_bwd(_p(saved), _p(gbin), B, X, Y, NZ, window, _p(ws), _p(dsr), _stream()),
               "spectral_energy_bwd")
@@ -1503,27 +1495,17 @@ def level_ssim(HR: Tensor, SR: Tensor, TL: Tensor, win: int = 11, sigma: float =
     from . import ssim
 
     _need_cuda(HR, SR, TL, out)
-    _planar5("level_ssim", "HR", HR, 3)
-    _planar5("level_ssim", "SR", SR, 3)
-    _planar5("level_ssim", "TL", TL, 3)
-    B, _, X, Y, NZ = HR.shape
-    for name, t in (("SR", SR), ("TL", TL)):
-        if (t.shape[0],) + tuple(t.shape[2:]) != (B, X, Y, NZ):
-            raise ValueError(f"level_ssim: {name} {tuple(t.shape)} does not match HR {tuple(HR.shape)}")
+    B, X, Y, NZ = _same_grid("level_ssim", HR, SR=SR, TL=TL)
     ssim.check_window(win, sigma, "level_ssim")
     ssim.check_domain(X, Y, win, "level_ssim")
     c1, c2 = ssim.constants(data_range)
     if NZ > SSIM_MAX_NZ or B > 65535 or X > 32768 or Y > 32768 or X * Y * NZ >= 2 ** 31:
         raise ValueError(f"level_ssim: at most {SSIM_MAX_NZ} levels, 65535 samples, 32768 points in x and y and 2^31 - 1 "
                          f"voxels per sample, not B = {B}, X = {X}, Y = {Y}, NZ = {NZ}")
-    if out is None:
-        out = torch.empty((B, NZ, 3, SSIM_SUMS), dtype=torch.float64, device=HR.device)
-    elif out.dtype != torch.float64 or tuple(out.shape) != (B, NZ, 3, SSIM_SUMS) or not out.is_contiguous():
-        raise ValueError(f"level_ssim wants out as a contiguous float64 ({B}, {NZ}, 3, {SSIM_SUMS}) tensor, got "
-                         f"{out.dtype} {tuple(out.shape)}")
+    out = _sums_out("level_ssim", out, (B, NZ, 3, SSIM_SUMS), HR.device)
     L = _lib.lib()
     taps = _ssim_taps_on(HR.device, win, sigma)
-    ws = torch.empty(int(L.wsr_level_ssim_workspace_floats(B, X, Y, NZ, int(win))), dtype=torch.float32, device=HR.device)
+    ws = _workspace(L.wsr_level_ssim_workspace_floats(B, X, Y, NZ, int(win)), HR.device)
     check(L.wsr_level_ssim(_p(HR), HR.shape[1], _p(SR), SR.shape[1], _p(TL), TL.shape[1], _p(taps), int(win), c1, c2, B, X,
                            Y, NZ, _p(ws), _p(out), _stream()), "level_ssim")
     return out

@@ -71,6 +71,7 @@ import logging
 import math
 import os
 import pickle as pkl
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -154,9 +155,9 @@ def _generate_fields(cfg, gan, LR_d, Z_d):
     """-> (SR, var, seam) of a device batch - the single point where both loops obtain SR: the variance between the
     ensemble members (None unless ``[ENSEMBLE] write_spread``) and the seam map of the tiles (None unless ``[TILE]
     write_seam``); without either section, or on a CPU device, the plain generator forward"""
-    ens, tile = cfg.ensemble, getattr(cfg, "tile", None)
+    ens, tile = cfg.ensemble, cfg.tile
     on_gpu = torch.device(cfg.device).type == "cuda"
-    if tile is not None and tile.present and on_gpu:
+    if tile.present and on_gpu:
         with_var = bool(ens.present and ens.write_spread)
         res = gan.G_tiled(LR_d, Z_d, members=ens.members if ens.present else 1, with_var=with_var,
                           with_seam=tile.write_seam)
@@ -170,140 +171,221 @@ def _generate_fields(cfg, gan, LR_d, Z_d):
     return gan.G_ensemble(LR_d, Z_d), None, None
 
 
-def _generate(cfg, gan, LR_d, Z_d):
-    """SR and the variance between the ensemble members of ``_generate_fields``"""
-    return _generate_fields(cfg, gan, LR_d, Z_d)[:2]
-
-
 def _mean_spread(var: torch.Tensor, uvw: float) -> torch.Tensor:
     """per field: the mean over voxels of sqrt(var_u + var_v + var_w) in m/s -> (B,)"""
     return torch.sqrt(var.sum(dim=1)).flatten(1).mean(dim=1) * uvw
 
 
-class _LevelProfile:
-    """[DIAGNOSTICS]: the per-level sums of the whole test set, (NZ, 15) float64 on the device of the sums it is given,
-    and the two files made of them.  ``fields``: the open per-field file or None; its rows wait in ``pending`` until
-    ``flush`` (the flush points of the metrics)."""
+OUT_DIR = "./test_output"
+RAW = "_reverse_interpolate"  # the suffix of the files about the raw levels
 
-    def __init__(self, path, uvw, fields=None):
-        self.path, self.uvw, self.fields = path, uvw, fields
-        self.total, self.ncols, self.pending = None, 0, []
-        if fields is not None:
-            fields.write("field,level," + ",".join(PROFILE_COLUMNS) + "\n")
 
-    def add(self, names, sums, ncols_per_field):
-        """``sums`` (B, NZ, 15) of the fields ``names`` with ``ncols_per_field`` = X * Y columns each"""
-        t = sums.sum(dim=0)
-        self.total = t if self.total is None else self.total + t
-        self.ncols += ncols_per_field * len(names)
-        if self.fields is not None:
-            self.pending.append((list(names), sums, ncols_per_field))
+class _Output:
+    """One family of extra CSV files about one set of levels (``suffix`` "" for the flat levels, ``RAW`` for the raw ones),
+    named ``<folder>/<name>____<stem><part><suffix>.csv``.  ``add(names, b)`` takes what it needs of the batch ``b`` (HR,
+    SR, TL, Z, var, seam of the fields ``names``) and queues it, ``flush`` writes the per-field rows that wait on the
+    device (the loops call it at the flush points of the metrics), ``close`` writes the whole-set files.  The object owns
+    its files: as a context manager it closes them, and writes the whole-set files only after a clean run."""
+
+    stem = ""
+    needs_baseline = False  # the stored baseline ``b.TL``
+
+    def __init__(self, name, suffix="", folder=OUT_DIR):
+        self.name, self.suffix, self.folder = name, suffix, folder
+        self.fields, self.pending = None, []  # the open per-field file; (names, rows (B, ...)) not yet written
+
+    def path(self, part=""):
+        return os.path.join(self.folder, f"{self.name}____{self.stem}{part}{self.suffix}.csv")
+
+    def open_fields(self, part, header):
+        self.fields = open(self.path(part), "w")
+        self.fields.write(header + "\n")
 
     def flush(self):
-        for names, sums, ncols in self.pending:
-            for name, table in zip(names, sums.cpu().tolist()):
-                _write_profile_rows(self.fields, profile_from_sums(table, ncols, self.uvw), name + ",")
-        self.pending.clear()
+        if self.pending:
+            rows = torch.cat([r for _, r in self.pending]).cpu().tolist()
+            for name, row in zip([nm for names, _ in self.pending for nm in names], rows):
+                self.write_field(name, row)
+            self.pending.clear()
 
     def close(self):
         self.flush()
-        with open(self.path, "w") as f:
-            f.write("level," + ",".join(PROFILE_COLUMNS) + "\n")
-            if self.total is not None:
-                _write_profile_rows(f, profile_from_sums(self.total.cpu(), self.ncols, self.uvw), "")  # the ONE read
+        if self.fields is not None:
+            self.fields.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            self.close()
+        elif self.fields is not None:
+            self.fields.close()
 
 
-def _write_profile_rows(f, prof, prefix):
-    for lvl in range(len(prof[PROFILE_COLUMNS[0]])):
-        f.write(f"{prefix}{lvl}," + ",".join(str(prof[k][lvl]) for k in PROFILE_COLUMNS) + "\n")
+class _FieldMean(_Output):
+    """[ENSEMBLE] write_spread (``key`` "var") and [TILE] write_seam ("seam"): one row ``field,<column>`` per field"""
+
+    def __init__(self, stem, column, key, uvw, *where):
+        super().__init__(*where)
+        self.stem, self.key, self.uvw = stem, key, uvw
+        self.open_fields("", "field," + column)
+
+    def add(self, names, b):
+        self.pending.append((list(names), _mean_spread(getattr(b, self.key), self.uvw)))
+
+    def write_field(self, name, v):
+        self.fields.write(f"{name},{v}\n")
 
 
-class _Spectrum:
-    """[SPECTRUM]: the spectral sums of the whole test set, (NZ, NK, 5) float64 on the device of the sums it is given,
-    and the files made of them: ``path`` (summed over the levels) and, unless None, ``levels_path`` (per level).
-    ``d``: the mean grid spacing in metres."""
+class _LevelSums(_Output):
+    """The per-level sums ``fn(HR, SR, TL, Z)`` -> float64 (B, NZ, ...) of every batch - the host reference or the
+    ``hip_ops`` launch it was built with - and their total over the test set, which stays on the device of the sums
+    until ``close``"""
 
-    def __init__(self, path, levels_path, uvw, d):
-        self.path, self.levels_path, self.uvw, self.d = path, levels_path, uvw, d
-        self.total, self.nfields, self.shape = None, 0, None
+    needs_baseline = True
 
-    def add(self, sums, X, Y):
-        """``sums`` (B, NZ, NK, 5) of B fields of X x Y columns"""
+    def __init__(self, fn, *where):
+        super().__init__(*where)
+        self.fn, self.total, self.nfields, self.shape = fn, None, 0, None
+
+    def add(self, names, b):
+        sums = self.fn(b.HR, b.SR, b.TL, b.Z)
         t = sums.sum(dim=0)
         self.total = t if self.total is None else self.total + t
-        self.nfields += sums.shape[0]
-        self.shape = (X, Y)
+        self.nfields += len(names)
+        self.shape = (b.HR.shape[2], b.HR.shape[3])  # X, Y
+        if self.fields is not None:
+            self.pending.append((list(names), sums))
+
+
+class _LevelProfile(_LevelSums):
+    """[DIAGNOSTICS]: sums (B, NZ, 15); the profile of the test set and, with ``per_field``, of every field"""
+
+    stem = "level_profile"
+
+    def __init__(self, fn, uvw, per_field, *where):
+        super().__init__(fn, *where)
+        self.uvw = uvw
+        if per_field:
+            self.open_fields("_fields", "field,level," + ",".join(PROFILE_COLUMNS))
+
+    def write_field(self, name, table):
+        _write_rows(self.fields, profile_from_sums(table, self.shape[0] * self.shape[1], self.uvw), PROFILE_COLUMNS,
+                    name + ",")
 
     def close(self):
+        super().close()
+        with open(self.path(), "w") as f:
+            f.write("level," + ",".join(PROFILE_COLUMNS) + "\n")
+            if self.total is not None:
+                ncols = self.shape[0] * self.shape[1] * self.nfields
+                _write_rows(f, profile_from_sums(self.total.cpu(), ncols, self.uvw), PROFILE_COLUMNS, "")  # the ONE read
+
+
+def _write_rows(f, table, columns, prefix):
+    """``table``: a list per column; one line ``<prefix><row>,<values>`` per row"""
+    for row in range(len(table[columns[0]])):
+        f.write(f"{prefix}{row}," + ",".join(str(table[c][row]) for c in columns) + "\n")
+
+
+class _Spectrum(_LevelSums):
+    """[SPECTRUM]: sums (B, NZ, NK, 5); the spectrum summed over the levels and, with ``per_level``, of every level.
+    ``d``: the mean grid spacing in metres."""
+
+    stem = "energy_spectrum"
+
+    def __init__(self, fn, uvw, d, per_level, *where):
+        super().__init__(fn, *where)
+        self.uvw, self.d, self.per_level = uvw, d, per_level
+
+    def close(self):
+        super().close()
         table = None if self.total is None else self.total.cpu()  # the ONE read
         if table is not None:
             N, counts = max(self.shape), mode_counts(*self.shape)
-        with open(self.path, "w") as f:
+        with open(self.path(), "w") as f:
             f.write("bin," + ",".join(SPECTRUM_COLUMNS) + "\n")
             if table is not None:
                 spec = spectrum_from_sums(table.sum(dim=0), self.nfields * table.shape[0], self.uvw, N, self.d, counts)
-                _write_spectrum_rows(f, spec, "")
-        if self.levels_path is not None:
-            with open(self.levels_path, "w") as f:
+                _write_rows(f, spec, SPECTRUM_COLUMNS, "")
+        if self.per_level:
+            with open(self.path("_levels"), "w") as f:
                 f.write("level,bin," + ",".join(SPECTRUM_COLUMNS) + "\n")
                 for lvl in range(0 if table is None else table.shape[0]):
-                    _write_spectrum_rows(f, spectrum_from_sums(table[lvl], self.nfields, self.uvw, N, self.d, counts),
-                                         f"{lvl},")
+                    _write_rows(f, spectrum_from_sums(table[lvl], self.nfields, self.uvw, N, self.d, counts),
+                                SPECTRUM_COLUMNS, f"{lvl},")
 
 
-def _write_spectrum_rows(f, spec, prefix):
-    for k in range(len(spec[SPECTRUM_COLUMNS[0]])):
-        f.write(f"{prefix}{k}," + ",".join(str(spec[c][k]) for c in SPECTRUM_COLUMNS) + "\n")
+class _Ssim(_LevelSums):
+    """[SSIM]: sums (B, NZ, 3, 4); one row per field, the row of ``averages_ssim<suffix>.csv`` and, with ``per_level``,
+    the rows per level summed over the fields.  ``win``: the window size."""
 
+    stem = "ssim"
 
-class _Ssim:
-    """[SSIM]: the per-field file (rows wait in ``pending`` until ``flush``, the flush points of the metrics), the sums
-    of the whole test set, (NZ, 3, 4) float64 on the device of the sums it is given, for the per-level file
-    (``levels_path``, unless None), and the row of ``averages_path``."""
+    def __init__(self, fn, win, per_level, *where):
+        super().__init__(fn, *where)
+        self.win, self.per_level, self.col_sums = win, per_level, [0.0] * 4
+        self.averages_path = os.path.join(self.folder, f"averages_ssim{self.suffix}.csv")
+        self.open_fields("", "field," + ",".join(SSIM_COLUMNS))
+        _header(self.averages_path, "Name," + ",".join("Average " + k for k in SSIM_COLUMNS[:4]))
 
-    def __init__(self, path, levels_path, averages_path, name, win):
-        self.levels_path, self.averages_path, self.name, self.win = levels_path, averages_path, name, win
-        self.total, self.nfields, self.npos, self.pending = None, 0, 0, []
-        self.col_sums = [0.0] * 4
-        self.fields = open(path, "w")
-        self.fields.write("field," + ",".join(SSIM_COLUMNS) + "\n")
-        _header(averages_path, "Name," + ",".join("Average " + k for k in SSIM_COLUMNS[:4]))
-
-    def add(self, names, sums, X, Y):
-        """``sums`` (B, NZ, 3, 4) of the fields ``names`` of X x Y columns each"""
-        t = sums.sum(dim=0)
-        self.total = t if self.total is None else self.total + t
-        self.npos = n_positions(X, Y, self.win)
-        self.pending.append((list(names), sums))
-
-    def flush(self):
-        for names, sums in self.pending:
-            for name, table in zip(names, sums.cpu().tolist()):
-                row = columns_from_sums(table, self.npos)
-                self.fields.write(f"{name}," + ",".join(str(v) for v in row) + "\n")
-                self.col_sums = [a + v for a, v in zip(self.col_sums, row)]
-                self.nfields += 1
-        self.pending.clear()
+    def write_field(self, name, table):
+        row = columns_from_sums(table, n_positions(*self.shape, self.win))
+        self.fields.write(f"{name}," + ",".join(str(v) for v in row) + "\n")
+        self.col_sums = [a + v for a, v in zip(self.col_sums, row)]
 
     def close(self):
-        self.flush()
-        self.fields.close()
+        super().close()
         if self.nfields:
             with open(self.averages_path, "a") as f:
                 f.write(self.name + "," + ",".join(str(v / self.nfields) for v in self.col_sums) + "\n")
-        if self.levels_path is not None:
-            with open(self.levels_path, "w") as f:
+        if self.per_level:
+            with open(self.path("_levels"), "w") as f:
                 f.write("level," + ",".join(SSIM_COLUMNS) + "\n")
                 table = [] if self.total is None else self.total.cpu().tolist()  # the ONE read
                 for lvl, t in enumerate(table):
-                    f.write(f"{lvl}," + ",".join(str(v) for v in columns_from_sums([t], self.npos * self.nfields)) + "\n")
+                    row = columns_from_sums([t], n_positions(*self.shape, self.win) * self.nfields)
+                    f.write(f"{lvl}," + ",".join(str(v) for v in row) + "\n")
 
 
-def _host_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread=None, seam=None, diag=None,
-               diag_rev=None, spec=None, spec_rev=None, ssim=None, ssim_rev=None):
-    """one field at a time; baseline, re-levelling and metrics on the host (the reference's loop)"""
+def _outputs(cfg, gan, uvw, d, suffix, on_device, folder=OUT_DIR):
+    """The extra outputs of one set of levels that ``cfg`` asks for, each yielded as soon as its files are open; the
+    sums come from ``hip_ops`` with ``on_device`` (the device loop), else from the host references.  ``d``: the mean grid
+    spacing in metres ([SPECTRUM]); [DIAGNOSTICS] reads the coordinates ``gan.x``, ``gan.y``."""
+    where = (cfg.name, suffix, folder)
+    if on_device:
+        from . import hip_ops
+    if suffix == "" and torch.device(cfg.device).type == "cuda":  # (what only the GPU paths of _generate_fields return)
+        if cfg.ensemble.present and cfg.ensemble.write_spread:
+            yield _FieldMean("ensemble_spread", "mean_spread", "var", uvw, *where)
+        if cfg.tile.present and cfg.tile.write_seam:
+            yield _FieldMean("tile_seam", "mean_seam", "seam", uvw, *where)
+    if cfg.diagnostics.on:
+        fn, x, y = (hip_ops.level_diagnostics, gan.x, gan.y) if on_device else (level_sums_reference, gan.x.cpu(), gan.y.cpu())
+        yield _LevelProfile(lambda HR, SR, TL, Z: fn(HR, SR, TL, x, y, Z), uvw, cfg.diagnostics.per_field, *where)
+    if cfg.spectrum.on:
+        spectra = hip_ops.level_spectra if on_device else level_spectra_reference
+        yield _Spectrum(lambda HR, SR, TL, Z: spectra(HR, SR, TL, cfg.spectrum.window), uvw, d, cfg.spectrum.per_level,
+                        *where)
+    if cfg.ssim.on:
+        ssim, par = hip_ops.level_ssim if on_device else level_ssim_reference, (cfg.ssim.window_size, cfg.ssim.sigma,
+                                                                                 cfg.ssim.data_range)
+        yield _Ssim(lambda HR, SR, TL, Z: ssim(HR, SR, TL, *par), par[0], cfg.ssim.per_level, *where)
+
+
+class _LevelSet:
+    """What is written about one set of levels: the open metrics file ``out``, the running averages ``avg`` of its
+    nine columns and the extra ``outputs``"""
+
+    def __init__(self, out, outputs=()):
+        self.out, self.outputs, self.avg = out, list(outputs), {k: 0.0 for k in METRIC_NAMES}
+
+
+def _host_loop(cfg, gan, loader, uvw, n, flat, raw=None):
+    """one field at a time; baseline, re-levelling and metrics on the host (the reference's loop).  ``flat``, ``raw``: the
+    ``_LevelSet`` of the flat levels and, with ``reverse_interpolate``, of the raw ones."""
     dev = cfg.device
-    ssim_par = _ssim_par(cfg) if ssim is not None else None
     for j, (LR, HR, Z, names, HR_raw, Z_raw) in enumerate(loader):
         TL = nn.functional.interpolate(LR[:, :3], scale_factor=(cfg.scale, cfg.scale, 1), mode="trilinear",
                                        align_corners=True)
@@ -311,124 +393,73 @@ def _host_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread
             SR_i, var_i, seam_i = _generate_fields(cfg, gan, LR[i:i + 1].to(dev, non_blocking=True),
                                                    Z[i:i + 1].to(dev, non_blocking=True))
             SR_i = SR_i.cpu()
-            if var_i is not None:
-                spread.write(f"{names[i]},{float(_mean_spread(var_i, uvw)[0])}\n")
-            if seam_i is not None:  # (the same reduction: sqrt of the sum over components, mean over voxels)
-                seam.write(f"{names[i]},{float(_mean_spread(seam_i, uvw)[0])}\n")
-            HR_i, TL_i = HR[i:i + 1, :3], TL[i:i + 1]
-            if rev:  # back onto the raw terrain-following levels of every column
-                SR_r = reverse_interpolate_z_axis(SR_i.numpy(), Z_raw[i:i + 1].numpy(), Z[i:i + 1].numpy())
-                TL_r = reverse_interpolate_z_axis(TL_i.numpy(), Z_raw[i:i + 1].numpy(), Z[i:i + 1].numpy())
-                vals = write_metrics(HR_raw[i:i + 1, :3], SR_r, TL_r, names[i], out_rev, uvw)
+            sets = [(flat, SimpleNamespace(HR=HR[i:i + 1, :3], SR=SR_i, TL=TL[i:i + 1], Z=Z[i:i + 1], var=var_i,
+                                           seam=seam_i))]
+            if raw is not None:  # back onto the raw terrain-following levels of every column
+                SR_r, TL_r = (reverse_interpolate_z_axis(t.numpy(), Z_raw[i:i + 1].numpy(), Z[i:i + 1].numpy())
+                              for t in (SR_i, TL[i:i + 1]))
+                sets.insert(0, (raw, SimpleNamespace(HR=HR_raw[i:i + 1], SR=SR_r, TL=TL_r, Z=Z_raw[i:i + 1])))
+            for ls, b in sets:
+                vals = write_metrics(b.HR[:, :3], b.SR, b.TL, names[i], ls.out, uvw)
                 for k, v in zip(METRIC_NAMES, vals):
-                    avg_rev[k] += v / n
-                if diag_rev is not None:
-                    diag_rev.add(names[i:i + 1], level_sums_reference(HR_raw[i:i + 1], SR_r, TL_r, gan.x.cpu(),
-                                                                      gan.y.cpu(), Z_raw[i:i + 1]),
-                                 HR.shape[2] * HR.shape[3])
-                    diag_rev.flush()
-                if spec_rev is not None:
-                    spec_rev.add(level_spectra_reference(HR_raw[i:i + 1], torch.as_tensor(SR_r), torch.as_tensor(TL_r),
-                                                         cfg.spectrum.window), HR.shape[2], HR.shape[3])
-                if ssim_rev is not None:
-                    ssim_rev.add(names[i:i + 1], level_ssim_reference(HR_raw[i:i + 1], torch.as_tensor(SR_r),
-                                                                      torch.as_tensor(TL_r), *ssim_par),
-                                 HR.shape[2], HR.shape[3])
-                    ssim_rev.flush()
-            vals = write_metrics(HR_i, SR_i, TL_i, names[i], out, uvw)
-            for k, v in zip(METRIC_NAMES, vals):
-                avg[k] += v / n
-            if diag is not None:
-                diag.add(names[i:i + 1], level_sums_reference(HR_i, SR_i, TL_i, gan.x.cpu(), gan.y.cpu(), Z[i:i + 1]),
-                         HR.shape[2] * HR.shape[3])
-                diag.flush()
-            if spec is not None:
-                spec.add(level_spectra_reference(HR_i, SR_i, TL_i, cfg.spectrum.window), HR.shape[2], HR.shape[3])
-            if ssim is not None:
-                ssim.add(names[i:i + 1], level_ssim_reference(HR_i, SR_i, TL_i, *ssim_par), HR.shape[2], HR.shape[3])
-                ssim.flush()
+                    ls.avg[k] += v / n
+                for o in ls.outputs:
+                    o.add(names[i:i + 1], b)
+                    o.flush()
             if j % cfg.training.log_period == 0:
                 write_fields(LR[i], HR[i], SR_i[0], TL[i], Z[i], cfg.env.this_runs_folder, names[i],
-                             HR_raw[i] if rev else None, Z_raw[i] if rev else None, None,
+                             None if raw is None else HR_raw[i], None if raw is None else Z_raw[i], None,
                              None if var_i is None else torch.sqrt(var_i[0]),
                              None if seam_i is None else torch.sqrt(seam_i[0]))
 
 
-def _ssim_par(cfg):
-    """(window size, sigma, data range) of [SSIM]"""
-    return cfg.ssim.window_size, cfg.ssim.sigma, cfg.ssim.data_range
-
-
-def _device_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread=None, seam=None, diag=None,
-                 diag_rev=None, spec=None, spec_rev=None, ssim=None, ssim_rev=None):
+def _device_loop(cfg, gan, loader, uvw, n, flat, raw=None):
     """[EVAL] device_metrics: one generator forward and one metrics launch per batch; the (B, 7) rows wait in a device
-    table and are read once per ``log_period`` batches and at the end"""
+    table and are read once per ``log_period`` batches and at the end.  ``flat``, ``raw``: as in ``_host_loop``; every
+    output makes one launch per batch."""
     from . import hip_ops
 
-    dev, s = cfg.device, cfg.scale
-    ssim_par = _ssim_par(cfg) if ssim is not None else None
+    dev, s, rev = cfg.device, cfg.scale, raw is not None
+    sets = (flat, raw) if rev else (flat,)
+    store_baseline = rev or any(o.needs_baseline for o in flat.outputs)
     pending = []  # (names, nvox, sums (B, 7), sums on the raw levels (B, 7) or None) of the batches not yet written
-    spreads = []  # ([ENSEMBLE] write_spread) (names, mean spread (B,)) of the batches not yet written
-    seams = []  # ([TILE] write_seam) (names, mean seam (B,)) of the batches not yet written
 
     def flush():
-        if not pending:
-            return
-        table = torch.cat([t for p in pending for t in p[2:] if t is not None]).cpu().tolist()  # the ONE read
-        at = 0
-        for names, nvox, _, raw in pending:
-            for dest, acc, present in ((out, avg, True), (out_rev, avg_rev, raw is not None)):
-                if not present:
-                    continue
-                for name in names:
-                    m = metrics_from_sums(table[at], nvox, uvw)
-                    at += 1
-                    dest.write(f"{name}," + ",".join(str(m[k]) for k in METRIC_NAMES) + "\n")
-                    for k in METRIC_NAMES:
-                        acc[k] += m[k] / n
-        pending.clear()
-        for rows, dest in ((spreads, spread), (seams, seam)):
-            if rows:
-                vals = torch.cat([t for _, t in rows]).cpu().tolist()
-                for name, v in zip([nm for names, _ in rows for nm in names], vals):
-                    dest.write(f"{name},{v}\n")
-                rows.clear()
-        for d in (diag, diag_rev, ssim, ssim_rev):
-            if d is not None:
-                d.flush()
+        if pending:
+            table = torch.cat([t for p in pending for t in p[2:] if t is not None]).cpu().tolist()  # the ONE read
+            at = 0
+            for names, nvox, *_ in pending:  # (per batch: all rows of the flat levels, then all of the raw ones)
+                for ls in sets:
+                    for name in names:
+                        m = metrics_from_sums(table[at], nvox, uvw)
+                        at += 1
+                        ls.out.write(f"{name}," + ",".join(str(m[k]) for k in METRIC_NAMES) + "\n")
+                        for k in METRIC_NAMES:
+                            ls.avg[k] += m[k] / n
+            pending.clear()
+        for ls in sets:
+            for o in ls.outputs:
+                o.flush()
 
     for j, (LR, HR, Z, names, HR_raw, Z_raw) in enumerate(loader):
         LR_d, HR_d, Z_d = (t.to(dev, non_blocking=True).contiguous() for t in (LR, HR, Z))
         SR_d, var_d, seam_d = _generate_fields(cfg, gan, LR_d, Z_d)
         SR_d = SR_d.float().contiguous()
-        if var_d is not None:
-            spreads.append((list(names), _mean_spread(var_d, uvw)))
-        if seam_d is not None:
-            seams.append((list(names), _mean_spread(seam_d, uvw)))
         nvox = HR.shape[2] * HR.shape[3] * HR.shape[4]
         sums = hip_ops.field_metrics(HR_d, SR_d, LR=LR_d, scale=s)  # (the baseline is blended inside, never stored)
         keep = j % cfg.training.log_period == 0
-        TL_d = (hip_ops.trilinear_xy(LR_d, s) if rev or keep or diag is not None or spec is not None or ssim is not None
-                else None)
-        ncols = HR.shape[2] * HR.shape[3]
-        if diag is not None:  # (the stored baseline: its divergence needs the neighbouring columns)
-            diag.add(names, hip_ops.level_diagnostics(HR_d, SR_d, TL_d, gan.x, gan.y, Z_d), ncols)
-        if spec is not None:  # (one launch per batch, on the stored baseline)
-            spec.add(hip_ops.level_spectra(HR_d, SR_d, TL_d, cfg.spectrum.window), HR.shape[2], HR.shape[3])
-        if ssim is not None:  # (one launch per batch, on the stored baseline; the rows wait on the device)
-            ssim.add(names, hip_ops.level_ssim(HR_d, SR_d, TL_d, *ssim_par), HR.shape[2], HR.shape[3])
+        # (the stored baseline: the outputs' kernels read it, the divergence needs the neighbouring columns)
+        TL_d = hip_ops.trilinear_xy(LR_d, s) if store_baseline or keep else None
+        b = SimpleNamespace(HR=HR_d, SR=SR_d, TL=TL_d, Z=Z_d, var=var_d, seam=seam_d)
+        for o in flat.outputs:
+            o.add(names, b)
         sums_raw = None
         if rev:  # back onto the raw terrain-following levels of every column, metrics against the raw truth
             raw_d, zraw_d = (t.to(dev, non_blocking=True).contiguous() for t in (HR_raw, Z_raw))
             SR_r, TL_r = hip_ops.column_interp(SR_d, Z_d, zraw_d), hip_ops.column_interp(TL_d, Z_d, zraw_d)
             sums_raw = hip_ops.field_metrics(raw_d, SR_r, TL=TL_r)
-            if diag_rev is not None:
-                diag_rev.add(names, hip_ops.level_diagnostics(raw_d, SR_r, TL_r, gan.x, gan.y, zraw_d), ncols)
-            if spec_rev is not None:
-                spec_rev.add(hip_ops.level_spectra(raw_d, SR_r, TL_r, cfg.spectrum.window), HR.shape[2], HR.shape[3])
-            if ssim_rev is not None:
-                ssim_rev.add(names, hip_ops.level_ssim(raw_d, SR_r, TL_r, *ssim_par), HR.shape[2], HR.shape[3])
-        # (per field: the sums in the order the rows are written - all of `out`, then all of `out_rev`, per batch)
+            for o in raw.outputs:
+                o.add(names, SimpleNamespace(HR=raw_d, SR=SR_r, TL=TL_r, Z=zraw_d))
         pending.append((list(names), nvox, sums, sums_raw))
         if keep:
             SR_h, TL_h = SR_d.cpu(), TL_d.cpu()
@@ -459,89 +490,26 @@ def test(cfg, dataset_test, reverse_interpolate: bool = False):
         cfg.gan_config.interpolate_z = False
     rev = bool(cfg.gan_config.interpolate_z)
     uvw = float(dataset_test.UVW_MAX)
-    os.makedirs("./test_output", exist_ok=True)
+    os.makedirs(OUT_DIR, exist_ok=True)
     os.makedirs(os.path.join(cfg.env.this_runs_folder, "fields"), exist_ok=True)
-    cols = "field," + ",".join(METRIC_NAMES)
-    _header("./test_output/averages.csv", "Name," + ",".join("Average " + k for k in METRIC_NAMES))
-    metrics_path = os.path.join("./test_output", cfg.name + "____metrics.csv")
-    rev_path = os.path.join("./test_output", cfg.name + "____metrics_reverse_interpolate.csv")
-    if rev:
-        _header("./test_output/averages_reverse_interpolate.csv",
-                "Name," + ",".join("Average " + k for k in METRIC_NAMES))
     n = max(len(dataset_test), 1)
-    avg = {k: 0.0 for k in METRIC_NAMES}
-    avg_rev = {k: 0.0 for k in METRIC_NAMES}
     dev = cfg.device
     log.info("beginning test")
-    # ([ENSEMBLE] write_spread on a GPU: one more CSV, the spread between the members per field)
-    with_spread = cfg.ensemble.present and cfg.ensemble.write_spread and torch.device(dev).type == "cuda"
-    spread_path = os.path.join("./test_output", cfg.name + "____ensemble_spread.csv")
-    # ([TILE] write_seam on a GPU: one more CSV, the disagreement of the tiles in their overlaps per field)
-    with_seam = cfg.tile.present and cfg.tile.write_seam and torch.device(dev).type == "cuda"
-    seam_path = os.path.join("./test_output", cfg.name + "____tile_seam.csv")
-    # ([DIAGNOSTICS]: the per-level sums of every batch, one more CSV - two with per_field - per set of levels)
-    dg = getattr(cfg, "diagnostics", None)
-    with_diag = dg is not None and dg.on
-    if with_diag:
+    if cfg.diagnostics.on:  # (the coordinates of the whole test domain)
         gan.x, gan.y = (torch.from_numpy(np.asarray(v)).float().contiguous().to(dev) for v in (dataset_test.x, dataset_test.y))
-
-    # ([SPECTRUM]: the spectral sums of every batch, one more CSV - two with per_level - per set of levels)
-    sp = getattr(cfg, "spectrum", None)
-    with_spec = sp is not None and sp.on
-
-    def spectrum_acc(suffix):
-        def path(levels):
-            return os.path.join("./test_output", f"{cfg.name}____energy_spectrum{'_levels' if levels else ''}{suffix}.csv")
-
-        return _Spectrum(path(False), path(True) if sp.per_level else None, uvw,
-                         grid_spacing(np.asarray(dataset_test.x), np.asarray(dataset_test.y)))
-
-    # ([SSIM]: the SSIM sums of every field, one more CSV - two with per_level - and one averages row per set of levels)
-    sm = getattr(cfg, "ssim", None)
-    with_ssim = sm is not None and sm.on
-
-    def ssim_acc(suffix):
-        def path(levels):
-            return os.path.join("./test_output", f"{cfg.name}____ssim{'_levels' if levels else ''}{suffix}.csv")
-
-        return _Ssim(path(False), path(True) if sm.per_level else None, f"./test_output/averages_ssim{suffix}.csv",
-                     cfg.name, sm.window_size)
-
-    def profile_path(fields, suffix):
-        return os.path.join("./test_output", f"{cfg.name}____level_profile{'_fields' if fields else ''}{suffix}.csv")
-
-    with open(metrics_path, "w") as out, (open(rev_path, "w") if rev else open(os.devnull, "w")) as out_rev, \
-            (open(spread_path, "w") if with_spread else contextlib.nullcontext()) as spread, \
-            (open(seam_path, "w") if with_seam else contextlib.nullcontext()) as seam, \
-            (open(profile_path(True, ""), "w") if with_diag and dg.per_field else contextlib.nullcontext()) as pf, \
-            (open(profile_path(True, "_reverse_interpolate"), "w") if with_diag and dg.per_field and rev
-             else contextlib.nullcontext()) as pf_rev:
-        diag = _LevelProfile(profile_path(False, ""), uvw, pf) if with_diag else None
-        diag_rev = _LevelProfile(profile_path(False, "_reverse_interpolate"), uvw, pf_rev) if with_diag and rev else None
-        spec = spectrum_acc("") if with_spec else None
-        spec_rev = spectrum_acc("_reverse_interpolate") if with_spec and rev else None
-        ssim = ssim_acc("") if with_ssim else None
-        ssim_rev = ssim_acc("_reverse_interpolate") if with_ssim and rev else None
-        out.write(cols + "\n")
-        out_rev.write(cols + "\n")
-        if with_spread:
-            spread.write("field,mean_spread\n")
-        if with_seam:
-            seam.write("field,mean_seam\n")
-        if cfg.eval.on and torch.device(dev).type == "cuda":
-            _device_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread, seam, diag, diag_rev, spec,
-                         spec_rev, ssim, ssim_rev)
-        else:
-            _host_loop(cfg, gan, loader, rev, uvw, n, out, out_rev, avg, avg_rev, spread, seam, diag, diag_rev, spec,
-                       spec_rev, ssim, ssim_rev)
-        for d in (diag, diag_rev, spec, spec_rev, ssim, ssim_rev):
-            if d is not None:
-                d.close()
-    with open("./test_output/averages.csv", "a") as f:
-        f.write(cfg.name + "," + ",".join(str(avg[k]) for k in METRIC_NAMES) + "\n")
+    d = grid_spacing(np.asarray(dataset_test.x), np.asarray(dataset_test.y)) if cfg.spectrum.on else None
+    on_device = cfg.eval.on and torch.device(dev).type == "cuda"
+    with contextlib.ExitStack() as stack:  # (an exception in any batch closes every file)
+        sets = []
+        for suffix in ("", RAW) if rev else ("",):
+            _header(f"{OUT_DIR}/averages{suffix}.csv", "Name," + ",".join("Average " + k for k in METRIC_NAMES))
+            out = stack.enter_context(open(os.path.join(OUT_DIR, f"{cfg.name}____metrics{suffix}.csv"), "w"))
+            out.write("field," + ",".join(METRIC_NAMES) + "\n")
+            sets.append(_LevelSet(out, (stack.enter_context(o) for o in _outputs(cfg, gan, uvw, d, suffix, on_device))))
+        (_device_loop if on_device else _host_loop)(cfg, gan, loader, uvw, n, *sets)
+    for ls, suffix in zip(sets, ("", RAW)):
+        with open(f"{OUT_DIR}/averages{suffix}.csv", "a") as f:
+            f.write(cfg.name + "," + ",".join(str(ls.avg[k]) for k in METRIC_NAMES) + "\n")
     for k in METRIC_NAMES:
-        log.info(f"Average {k}: {avg[k]}")
-    if rev:
-        with open("./test_output/averages_reverse_interpolate.csv", "a") as f:
-            f.write(cfg.name + "," + ",".join(str(avg_rev[k]) for k in METRIC_NAMES) + "\n")
-    return avg
+        log.info(f"Average {k}: {sets[0].avg[k]}")
+    return sets[0].avg

@@ -260,7 +260,7 @@ def test_tree_of_identical_members_is_exact():
 def test_generate_without_the_section_is_the_plain_forward():
     """test.py's switch: no section (or a CPU device) -> ``gan.G`` itself, no variance"""
     from gan_sr_wind_field_amd.config.config import Config
-    from gan_sr_wind_field_amd.test import _generate
+    from gan_sr_wind_field_amd.test import _generate_fields
 
     class Gan:
         def G(self, lr, z):
@@ -272,11 +272,11 @@ def test_generate_without_the_section_is_the_plain_forward():
     cfg = Config(LOCAL_INI)
     cfg.device = torch.device("cpu")
     lr = torch.zeros(1, 4, 2, 2, 3)
-    sr, var = _generate(cfg, Gan(), lr, None)
+    sr, var = _generate_fields(cfg, Gan(), lr, None)[:2]
     assert var is None and torch.equal(sr, lr[:, :3] + 1)
     cfg.ensemble.present, cfg.ensemble.write_spread = True, True  # a CPU device keeps the plain path
     try:
-        sr, var = _generate(cfg, Gan(), lr, None)
+        sr, var = _generate_fields(cfg, Gan(), lr, None)[:2]
         assert var is None and torch.equal(sr, lr[:, :3] + 1)
     finally:
         Config(LOCAL_INI)

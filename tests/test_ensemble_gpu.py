@@ -379,11 +379,12 @@ def test_host_and_device_loops_take_sr_from_the_ensemble(hip, tmp_path):
             cfg.env.this_runs_folder = str(tmp_path / name)
             cfg.eval.present, cfg.eval.device_metrics, cfg.eval.batch_size = name == "device", True, bs
             loader = torch.utils.data.DataLoader(fields, batch_size=bs, shuffle=False)
-            out, spread = io.StringIO(), io.StringIO()
-            avg, avg_rev = ({k: 0.0 for k in tmod.METRIC_NAMES} for _ in range(2))
-            with open(os.devnull, "w") as out_rev:
-                loop(cfg, gan, loader, False, uvw, n, out, out_rev, avg, avg_rev, spread)
-            rows = [r.split(",") for r in spread.getvalue().strip().splitlines()]
+            out = io.StringIO()
+            with tmod._FieldMean("ensemble_spread", "mean_spread", "var", uvw, name, "", str(tmp_path)) as spread:
+                loop(cfg, gan, loader, uvw, n, tmod._LevelSet(out, [spread]))
+            text = open(spread.path()).read()
+            assert text.startswith("field,mean_spread\n")
+            rows = [r.split(",") for r in text.strip().splitlines()[1:]]
             assert [r[0] for r in rows] == [f"f{i}" for i in range(n)] == [r.split(",")[0] for r in out.getvalue().strip().splitlines()]
             got[name] = [float(r[1]) for r in rows]
             for i in range(n):

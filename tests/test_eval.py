@@ -296,3 +296,132 @@ def test_run_py_passes_reverse_interpolate(data_root, tmp_path, monkeypatch):
     runmod.main(["--test", "--cfg", ini])
     assert os.path.isfile(os.path.join("test_output", "norev____metrics.csv"))
     assert not os.path.exists(os.path.join("test_output", "norev____metrics_reverse_interpolate.csv"))
+
+
+def _only(cfg, monkeypatch, **sections):
+    """fresh [DIAGNOSTICS], [SPECTRUM] and [SSIM] objects on ``cfg``, absent but for ``sections`` (name -> attributes)"""
+    from gan_sr_wind_field_amd.config.config import DiagnosticsConfig, SpectrumConfig, SsimConfig
+
+    for attr, cls in (("diagnostics", DiagnosticsConfig), ("spectrum", SpectrumConfig), ("ssim", SsimConfig)):
+        sec = cls()
+        sec.load(None)
+        for k, v in sections.get(attr, {}).items():
+            setattr(sec, k, v)
+        sec.present = attr in sections
+        sec.validate()
+        monkeypatch.setattr(cfg, attr, sec)
+
+
+SECTIONS = {"diagnostics": {"per_field": True}, "spectrum": {"per_level": True},
+            "ssim": {"per_level": True, "window_size": 7, "sigma": 1.0}}
+STEMS = {"diagnostics": "level_profile", "spectrum": "energy_spectrum", "ssim": "ssim"}
+
+
+def _files(name):
+    """what a run called ``name`` wrote: file name without the run's name -> text"""
+    out = {}
+    for f in sorted(os.listdir("test_output")):
+        if f.startswith(name + "____"):
+            with open(os.path.join("test_output", f)) as fh:
+                out[f[len(name) + 4:]] = fh.read()
+    return out
+
+
+def test_all_sections_together_write_each_sections_own_files(data_root, tmp_path, monkeypatch):
+    """[DIAGNOSTICS], [SPECTRUM] and [SSIM] at once, with ``reverse_interpolate``: 14 files, each the bytes of the run
+    with only its own section; the metrics files are those of every run.  Exact: no tolerance.  And a first batch that
+    raises (an SSIM window larger than the domain) leaves no file of the evaluation open."""
+    import gan_sr_wind_field_amd.test as tmod
+
+    cfg, ds = _trained(tmp_path, monkeypatch, interpolate_z=True)
+    runs = {"plain": {}, **{k: {k: v} for k, v in SECTIONS.items()}, "all": SECTIONS}
+    for name, sections in runs.items():
+        cfg.gan_config.interpolate_z = True
+        _only(cfg, monkeypatch, **sections)
+        cfg.name = name
+        tmod.test(cfg, ds, reverse_interpolate=True)
+    got = {name: _files(name) for name in runs}
+    metrics = {"metrics.csv", "metrics_reverse_interpolate.csv"}
+    assert set(got["plain"]) == metrics
+    assert len(got["all"]) == 14, sorted(got["all"])
+    for sec, stem in STEMS.items():
+        own = {f for f in got[sec] if f.startswith(stem)}
+        assert len(own) == 4 and set(got[sec]) == metrics | own, (sec, sorted(got[sec]))
+        for f in own:
+            assert got["all"][f] == got[sec][f], f
+    assert set(got["all"]) == metrics | {f for sec in STEMS for f in got[sec]}
+    for f in metrics:
+        assert len(got["plain"][f].splitlines()) == 1 + len(ds)
+        assert all(got[name][f] == got["plain"][f] for name in runs), f
+    # a window larger than the domain: the ValueError of the first batch comes through, and every file is closed
+    made = []
+    outputs = tmod._outputs
+    monkeypatch.setattr(tmod, "_outputs", lambda *a, **kw: (made.append(o) or o for o in outputs(*a, **kw)))
+    X, Y = ds[0][1].shape[1:3]
+    _only(cfg, monkeypatch, **SECTIONS)
+    cfg.ssim.window_size, cfg.name, cfg.gan_config.interpolate_z = 2 * max(X, Y) + 1, "wide", True
+    with pytest.raises(ValueError, match=str(cfg.ssim.window_size)):
+        tmod.test(cfg, ds, reverse_interpolate=True)
+    assert [type(o).__name__ for o in made] == ["_LevelProfile", "_Spectrum", "_Ssim"] * 2
+    for o in made:
+        assert o.fields is None or o.fields.closed, type(o).__name__
+    ssim_files = [o.path() for o in made if type(o).__name__ == "_Ssim"]
+    assert len(ssim_files) == 2
+    for path in ssim_files:
+        os.remove(path)
+    assert not any(os.path.realpath(os.path.join("/proc/self/fd", fd)).startswith(os.path.realpath("test_output"))
+                   for fd in os.listdir("/proc/self/fd"))
+    # (the whole-set files are written after a clean run only)
+    assert not os.path.exists(os.path.join("test_output", "wide____level_profile.csv"))
+
+
+OPTIONAL = {  # attribute -> (section, a key, a value that does not parse, what the message asks for)
+    "grad_clip": ("GRAD_CLIP", "clip_generator", "maybe", "True or False"),
+    "ema": ("EMA", "decay", "fast", "a number"),
+    "eval": ("EVAL", "batch_size", "many", "an integer"),
+    "ensemble": ("ENSEMBLE", "members", "8.5", "an integer"),
+    "tile": ("TILE", "tile", "wide", "an integer"),
+    "diagnostics": ("DIAGNOSTICS", "per_field", "some", "True or False"),
+    "spectrum": ("SPECTRUM", "per_level", "2", "True or False"),
+    "spectral_loss": ("SPECTRAL_LOSS", "weight", "heavy", "a number"),
+    "degradation": ("DEGRADATION", "sigma", "wide", "a number"),
+    "ssim": ("SSIM", "window_size", "11.0", "an integer"),
+}
+
+
+@pytest.mark.parametrize("attr", sorted(OPTIONAL))
+def test_every_optional_section_names_section_and_key_of_an_unparsable_value(attr, tmp_path):
+    from gan_sr_wind_field_amd.config.config import Config
+
+    section, key, bad, what = OPTIONAL[attr]
+    try:
+        with pytest.raises(ValueError) as err:
+            Config(_ini_with(tmp_path, f"[{section}]\n{key} = {bad}\n"))
+        assert str(err.value) == f"[{section}] {key} must be {what}, not {bad!r}"
+        assert type(getattr(Config, attr))._section == section
+    finally:
+        Config(LOCAL_INI)  # (the section objects are singletons: reset)
+    assert getattr(Config, attr).present is False
+
+
+def test_optional_sections_print_in_their_order(tmp_path):
+    """three sections present at once print as the concatenation of what the per-section tests pin, in the order
+    GRAD_CLIP, EMA, EVAL, ENSEMBLE, TILE, DIAGNOSTICS, SPECTRUM, SPECTRAL_LOSS, however the file orders them; [DATA],
+    [DEGRADATION] and [SSIM] load and stay unprinted"""
+    from gan_sr_wind_field_amd.config.config import Config
+
+    try:
+        plain = Config(LOCAL_INI).asINI()
+        cfg = Config(_ini_with(tmp_path, "[SSIM]\nper_level = True\n\n[SPECTRUM]\nwindow = None\n\n[DATA]\n"
+                                         "device_resident = True\n\n[EVAL]\n\n[DEGRADATION]\nkernel = Box\n\n[ENSEMBLE]\n"
+                                         "members = 2\n"))
+        assert cfg.ssim.on and cfg.ssim.per_level and cfg.data.device_resident and cfg.degradation.kernel == "box"
+        assert cfg.asINI() == (plain + "\n[EVAL]\ndevice_metrics = True\nbatch_size = 8\nreverse_interpolate = False\n"
+                               + "\n[ENSEMBLE]\nmembers = 2\nwrite_spread = False\n"
+                               + "\n[SPECTRUM]\nenergy_spectrum = True\nper_level = False\nwindow = none\n")
+        order = [attr for attr, _ in Config._optional]
+        assert order == ["data", "grad_clip", "ema", "eval", "ensemble", "tile", "diagnostics", "spectrum",
+                         "spectral_loss", "degradation", "ssim"]
+    finally:
+        Config(LOCAL_INI)
+    assert Config(LOCAL_INI).asINI() == plain

@@ -254,8 +254,26 @@ def _assert_rows_within(a, b, nvox, extras, label):
     print(f"[e2e] {label}: worst |difference| / bound {worst:.3g}")
 
 
+def _run(tmp_path, name, flags, section, interpolate_z=False, **env):
+    """``run.py`` with ``flags`` on the e2e configuration named ``name`` plus the text ``section`` -> (cfg, run folder)"""
+    from test_hip_train_e2e import _write_ini
+
+    from gan_sr_wind_field_amd import run as runmod
+
+    ini = str(tmp_path / f"{name}.ini")
+    cfg = _write_ini(ini)
+    cfg.name = name
+    cfg.gan_config.interpolate_z = interpolate_z
+    for k, v in env.items():
+        setattr(cfg.env, k, v)
+    with open(ini, "w") as f:
+        f.write(cfg.asINI() + section)
+    runmod.main(flags + ["--cfg", ini])
+    return cfg, os.path.join(str(tmp_path), "runs", name)
+
+
 def test_run_train_and_test_with_and_without_the_section(hip, tmp_path, monkeypatch):
-    from test_hip_train_e2e import LOSS_KEYS, _write_ini
+    from test_hip_train_e2e import LOSS_KEYS
 
     from gan_sr_wind_field_amd import process_data as pd
     from gan_sr_wind_field_amd import run as runmod
@@ -305,17 +323,8 @@ def test_run_train_and_test_with_and_without_the_section(hip, tmp_path, monkeypa
 
     monkeypatch.setattr(cls, "validation", rec_val_typed)
 
-    def run(name, flags, section, interpolate_z=False, **env):
-        ini = str(tmp_path / f"{name}.ini")
-        cfg = _write_ini(ini)
-        cfg.name = name
-        cfg.gan_config.interpolate_z = interpolate_z
-        for k, v in env.items():
-            setattr(cfg.env, k, v)
-        with open(ini, "w") as f:
-            f.write(cfg.asINI() + section)
-        runmod.main(flags + ["--cfg", ini])
-        return cfg, os.path.join(str(tmp_path), "runs", name)
+    def run(*a, **kw):
+        return _run(tmp_path, *a, **kw)
 
     cfg_a, dir_a = run("plain", ["--train", "--test"], "")
     assert calls == {"field_metrics": 0, "trilinear_xy": 0, "column_interp": 0}  # the section absent: no new launch
@@ -400,3 +409,127 @@ def test_run_train_and_test_with_and_without_the_section(hip, tmp_path, monkeypa
     for name in ("rev_host", "rev_dev"):
         assert any(r.startswith(name + ",") for r in open("test_output/averages_reverse_interpolate.csv").read().splitlines())
     print(f"[time] tests/test_eval_gpu.py up to here: {time.time() - T0:.1f} s")
+
+
+# ------------------------------------------------------------------------------- the extra outputs of the device loop
+def _counted(monkeypatch, names):
+    """counting wrappers around ``hip_ops.<name>`` -> the counts"""
+    from gan_sr_wind_field_amd import hip_ops
+
+    calls = dict.fromkeys(names, 0)
+
+    def counted(name):
+        orig = getattr(hip_ops, name)
+
+        def f(*a, **kw):
+            calls[name] += 1
+            return orig(*a, **kw)
+        return f
+
+    for name in names:
+        monkeypatch.setattr(hip_ops, name, counted(name))
+    return calls
+
+
+def _lines(path):
+    with open(path) as f:
+        return [r.split(",") for r in f.read().strip().splitlines()]
+
+
+def test_device_loop_with_a_remainder_batch_and_a_flush_in_mid_run(hip, tmp_path, monkeypatch):
+    """three fields in batches of two with ``log_period = 2``: a flush after the first batch, a last batch of one field.
+    [DIAGNOSTICS], [SPECTRUM] and [SSIM] on, every file of theirs asked for: each field once and in the loader's order in
+    every per-field file, every whole-set file complete, one launch per output, baseline and metrics per batch.  Exact
+    counts and orders, no tolerance."""
+    import contextlib
+    import io
+
+    from gan_sr_wind_field_amd import test as tmod
+    from gan_sr_wind_field_amd.diagnostics import PROFILE_COLUMNS
+    from gan_sr_wind_field_amd.spectra import SPECTRUM_COLUMNS, n_bins
+    from gan_sr_wind_field_amd.ssim import SSIM_COLUMNS
+    from test_ensemble_gpu import _gan
+    from test_tiling_gpu import _inputs, _reset_config
+
+    try:
+        gan, cfg = _gan(nz=5)
+        cfg.name, cfg.env.this_runs_folder = "loop", str(tmp_path / "run")
+        cfg.eval.present, cfg.eval.device_metrics, cfg.eval.batch_size = True, True, 2
+        cfg.training.log_period = 2
+        cfg.diagnostics.present = cfg.diagnostics.per_field = True
+        cfg.spectrum.present = cfg.spectrum.per_level = True
+        cfg.ssim.present = cfg.ssim.per_level = True
+        gan.G.eval()
+        n, uvw, NZ = 3, 30.0, 5
+        LR, HR, Z = _inputs(n)
+        X, Y = HR.shape[2:4]
+        assert (X, Y, HR.shape[4]) == (48, 40, NZ)
+        gan.x, gan.y = (200.0 * torch.arange(k, dtype=torch.float32, device=DEV) for k in (X, Y))
+        empty = torch.zeros(0)
+        names = [f"f{i}" for i in range(n)]
+        loader = torch.utils.data.DataLoader([(LR[i], HR[i], Z[i], names[i], empty, empty) for i in range(n)], batch_size=2,
+                                             shuffle=False)
+        calls = _counted(monkeypatch, ("level_diagnostics", "level_spectra", "level_ssim", "trilinear_xy", "field_metrics"))
+        out = io.StringIO()
+        with contextlib.ExitStack() as stack:
+            flat = tmod._LevelSet(out, (stack.enter_context(o)
+                                        for o in tmod._outputs(cfg, gan, uvw, 200.0, "", True, str(tmp_path))))
+            assert [type(o).__name__ for o in flat.outputs] == ["_LevelProfile", "_Spectrum", "_Ssim"]
+            tmod._device_loop(cfg, gan, loader, uvw, n, flat)
+        assert calls == dict.fromkeys(calls, 2), calls  # (two batches: one launch each per batch)
+        assert [r.split(",")[0] for r in out.getvalue().strip().splitlines()] == names
+        assert sorted(f for f in os.listdir(tmp_path) if f.endswith(".csv")) == sorted(
+            ["averages_ssim.csv"] + [f"loop____{stem}.csv" for stem in (
+                "level_profile", "level_profile_fields", "energy_spectrum", "energy_spectrum_levels", "ssim", "ssim_levels")])
+        NK = n_bins(X, Y)
+        levels = [str(k) for k in range(NZ)]
+        rows = _lines(tmp_path / "loop____level_profile_fields.csv")
+        assert rows[0] == ["field", "level"] + list(PROFILE_COLUMNS)
+        assert [r[:2] for r in rows[1:]] == [[nm, lvl] for nm in names for lvl in levels]
+        rows = _lines(tmp_path / "loop____ssim.csv")
+        assert rows[0] == ["field"] + list(SSIM_COLUMNS) and [r[0] for r in rows[1:]] == names
+        rows = _lines(tmp_path / "loop____level_profile.csv")
+        assert rows[0] == ["level"] + list(PROFILE_COLUMNS) and [r[0] for r in rows[1:]] == levels
+        rows = _lines(tmp_path / "loop____ssim_levels.csv")
+        assert rows[0] == ["level"] + list(SSIM_COLUMNS) and [r[0] for r in rows[1:]] == levels
+        rows = _lines(tmp_path / "loop____energy_spectrum.csv")
+        assert rows[0] == ["bin"] + list(SPECTRUM_COLUMNS) and [r[0] for r in rows[1:]] == [str(k) for k in range(NK)]
+        rows = _lines(tmp_path / "loop____energy_spectrum_levels.csv")
+        assert rows[0] == ["level", "bin"] + list(SPECTRUM_COLUMNS)
+        assert [r[:2] for r in rows[1:]] == [[lvl, str(k)] for lvl in levels for k in range(NK)]
+        rows = _lines(tmp_path / "averages_ssim.csv")
+        assert len(rows) == 2 and rows[1][0] == "loop"
+        assert sorted(os.listdir(tmp_path / "run" / "fields")) == ["test_fields_f0.pkl", "test_fields_f1.pkl"]  # batch 0
+    finally:
+        _reset_config()
+
+
+def test_all_sections_together_write_each_sections_own_files_on_the_device(hip, tmp_path, monkeypatch):
+    """the device-loop form of test_eval.py's test of the same name: from one checkpoint, ``[EVAL] batch_size = 2`` with
+    ``reverse_interpolate``, the run with [DIAGNOSTICS], [SPECTRUM] and [SSIM] writes 14 files, each the bytes of the run
+    with only its own section, the metrics files those of every run.  Exact - it rests on the kernels giving the same bits
+    on every call and on the generator forward giving the same bits for the same batch shape."""
+    from gan_sr_wind_field_amd import process_data as pd
+    from test_eval import STEMS, _files
+
+    monkeypatch.chdir(tmp_path)
+    monkeypatch.setattr(pd, "DATA_ROOT", str(tmp_path / "data"))
+    ev = "\n[EVAL]\nbatch_size = 2\nreverse_interpolate = True\n"
+    text = {"diagnostics": "\n[DIAGNOSTICS]\nper_field = True\n", "spectrum": "\n[SPECTRUM]\nper_level = True\n",
+            "ssim": "\n[SSIM]\nper_level = True\nwindow_size = 7\nsigma = 1.0\n"}
+    _, folder = _run(tmp_path, "ckpt", ["--train"], "", interpolate_z=True)
+    load = {k + "_load_path": os.path.join(folder, f"{v}_6.pth")
+            for k, v in (("generator", "G"), ("discriminator", "D"), ("state", "state"))}
+    runs = {"plain": ev, **{k: ev + v for k, v in text.items()}, "all": ev + "".join(text.values())}
+    for name, section in runs.items():
+        _run(tmp_path, name, ["--test"], section, interpolate_z=True, **load)
+    got = {name: _files(name) for name in runs}
+    metrics = {"metrics.csv", "metrics_reverse_interpolate.csv"}
+    assert set(got["plain"]) == metrics and len(got["all"]) == 14, sorted(got["all"])
+    for sec, stem in STEMS.items():
+        own = {f for f in got[sec] if f.startswith(stem)}
+        assert len(own) == 4 and set(got[sec]) == metrics | own, (sec, sorted(got[sec]))
+        for f in own:
+            assert got["all"][f] == got[sec][f], f
+    for f in metrics:
+        assert len(got["plain"][f].splitlines()) > 1 and all(got[name][f] == got["plain"][f] for name in runs), f

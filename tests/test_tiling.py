@@ -266,7 +266,7 @@ def test_missing_tile_says_it_is_required(tmp_path):
 def test_generate_without_the_section_is_the_plain_forward():
     """test.py's switch: no section (or a CPU device) -> ``gan.G`` itself, no variance, no seam"""
     from gan_sr_wind_field_amd.config.config import Config
-    from gan_sr_wind_field_amd.test import _generate, _generate_fields
+    from gan_sr_wind_field_amd.test import _generate_fields
 
     class Gan:
         def G(self, lr, z):
@@ -287,7 +287,7 @@ def test_generate_without_the_section_is_the_plain_forward():
     try:
         sr, var, seam = _generate_fields(cfg, Gan(), lr, None)
         assert var is None and seam is None and torch.equal(sr, lr[:, :3] + 1)
-        sr, var = _generate(cfg, Gan(), lr, None)
+        sr, var = _generate_fields(cfg, Gan(), lr, None)[:2]
         assert var is None and torch.equal(sr, lr[:, :3] + 1)
     finally:
         Config(LOCAL_INI)

@@ -500,13 +500,14 @@ def test_host_and_device_loops_take_sr_from_g_tiled(hip, tmp_path):
             cfg.env.this_runs_folder = str(tmp_path / name)
             cfg.eval.present, cfg.eval.device_metrics, cfg.eval.batch_size = name == "device", True, bs
             loader = torch.utils.data.DataLoader(fields, batch_size=bs, shuffle=False)
-            out, seam = io.StringIO(), io.StringIO()
-            avg, avg_rev = ({k: 0.0 for k in tmod.METRIC_NAMES} for _ in range(2))
+            out = io.StringIO()
             counted["n"] = 0
-            with open(os.devnull, "w") as out_rev:
-                loop(cfg, gan, loader, False, uvw, n, out, out_rev, avg, avg_rev, None, seam)
+            with tmod._FieldMean("tile_seam", "mean_seam", "seam", uvw, name, "", str(tmp_path)) as seam:
+                loop(cfg, gan, loader, uvw, n, tmod._LevelSet(out, [seam]))
             assert counted["n"] == n // bs, (name, counted)
-            rows = [r.split(",") for r in seam.getvalue().strip().splitlines()]
+            text = open(seam.path()).read()
+            assert text.startswith("field,mean_seam\n")
+            rows = [r.split(",") for r in text.strip().splitlines()[1:]]
             assert [r[0] for r in rows] == [f"f{i}" for i in range(n)] == [r.split(",")[0] for r in out.getvalue().strip().splitlines()]
             for i in range(n):
                 p = pickle.load(open(os.path.join(cfg.env.this_runs_folder, "fields", f"test_fields_f{i}.pkl"), "rb"))

@@ -107,17 +107,17 @@ def bench_shape(tag, spec, args, dev):
         # device: batch 0 only = batch_size fields; host (one field per batch): every (fields / batch_size)-th field
         cfg.training.log_period = 10 ** 9 if on else args.fields // args.batch_size
         loader = torch.utils.data.DataLoader(fields, batch_size=args.batch_size if on else 1, shuffle=False)
-        avg, avg_rev = ({k: 0.0 for k in tmod.METRIC_NAMES} for _ in range(2))
         loop = tmod._device_loop if on else tmod._host_loop
         pickled["n"], pickled["ms"] = 0, 0.0
-        with open(os.devnull, "w") as o, open(os.devnull, "w") as o_rev:
+        with open(os.devnull, "w") as o:
+            flat = tmod._LevelSet(o)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            loop(cfg, gan, loader, False, uvw, args.fields, o, o_rev, avg, avg_rev)
+            loop(cfg, gan, loader, uvw, args.fields, flat)
             torch.cuda.synchronize()
             ms = (time.perf_counter() - t0) * 1e3
         assert pickled["n"] == args.batch_size, pickled
-        return ms / args.fields, (ms - pickled["ms"]) / args.fields, avg, pickled["ms"] / pickled["n"]
+        return ms / args.fields, (ms - pickled["ms"]) / args.fields, flat.avg, pickled["ms"] / pickled["n"]
 
     vb = spec["val_batch"]
     batches = [(LR[i:i + vb], HR[i:i + vb], Z[i:i + vb]) for i in range(0, args.fields - vb + 1, vb)]

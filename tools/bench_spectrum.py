@@ -109,7 +109,8 @@ def bench_loop(spec, args, dev):
     from gan_sr_wind_field_amd import test as tmod
     from gan_sr_wind_field_amd.process_data import synthetic_batch
 
-    gan, cfg = be.make(dev, spec["nz"], spec["dtype"], tempfile.mkdtemp(prefix="bench_spectrum_"))
+    folder = tempfile.mkdtemp(prefix="bench_spectrum_")
+    gan, cfg = be.make(dev, spec["nz"], spec["dtype"], folder)
     LR, HR, Z, x, y = synthetic_batch(args.fields, spec["lr"], spec["nz"], cfg.scale, seed=2001)
     gan.feed_xy_niter(x.to(dev), y.to(dev), torch.tensor(cfg.training.niter, device=dev), 1, 1)
     gan.G.eval()
@@ -120,15 +121,17 @@ def bench_loop(spec, args, dev):
     uvw = 30.0
 
     def loop_pass(on):
-        acc = tmod._Spectrum(os.devnull, None, uvw, 200.0) if on else None
+        from gan_sr_wind_field_amd import hip_ops
+
+        acc = [tmod._Spectrum(lambda HR, SR, TL, Z: hip_ops.level_spectra(HR, SR, TL, args.window), uvw, 200.0, False,
+                              cfg.name, "", folder)] if on else []
         loader = torch.utils.data.DataLoader(fields, batch_size=args.batch_size, shuffle=False)
-        avg, avg_rev = ({k: 0.0 for k in tmod.METRIC_NAMES} for _ in range(2))
-        with open(os.devnull, "w") as o, open(os.devnull, "w") as o_rev:
+        with open(os.devnull, "w") as o:
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            tmod._device_loop(cfg, gan, loader, False, uvw, args.fields, o, o_rev, avg, avg_rev, spec=acc)
-            if acc is not None:
-                acc.close()
+            tmod._device_loop(cfg, gan, loader, uvw, args.fields, tmod._LevelSet(o, acc))
+            for a in acc:
+                a.close()
             torch.cuda.synchronize()
             return (time.perf_counter() - t0) * 1e3 / args.fields
 
