@@ -746,6 +746,22 @@ class wind_field_GAN_3D(BaseGAN):
         return _level_sums("level_ssim", level_ssim_reference, self.cfg.scale, HR, SR, LR, (),
                            (sc.window_size, sc.sigma, sc.data_range))
 
+    # ------------------------------------------------------------------ wind-speed distribution ([DISTRIBUTION])
+    def level_distribution(self, HR, SR, LR, UVW_MAX):
+        """The count table of ``distribution.py`` per sample, z level and source (HR, SR, baseline) of a batch -> float64
+        (B, NZ, 3, NS, ND + 1) on the tensors' device, with the bins, sectors and calm threshold of ``[DISTRIBUTION]``
+        (its defaults with ``bin_width`` 1.0 without the section) and ``UVW_MAX`` to denormalise: the trilinear baseline
+        of ``LR`` is built here (``wsr_trilinear_xy`` on a GPU, ``F.interpolate`` on a CPU), the counts come from
+        ``hip_ops.level_distribution`` on a GPU and from ``distribution.level_distribution_reference`` on a CPU.
+        Reads no weights: the same inside ``ema_scope()``."""
+        from ..config.config import DistributionConfig
+        from ..distribution import distribution_tables, level_distribution_reference
+
+        dc = getattr(self.cfg, "distribution", None) or DistributionConfig
+        bin_width = dc.bin_width if dc.bin_width is not None else 1.0
+        tables = distribution_tables(UVW_MAX, bin_width, dc.speed_bins, dc.sectors, dc.calm)
+        return _level_sums("level_distribution", level_distribution_reference, self.cfg.scale, HR, SR, LR, (), (tables,))
+
     def make_new_labels(self, it):
         """Real / fake label vectors of this iteration (reference :627-678)."""
         t = self.cfg.training

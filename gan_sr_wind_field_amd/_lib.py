@@ -32,6 +32,7 @@ EXPORTS = [
     "wsr_spectral_energy_bwd",
     "wsr_gather_batch_filtered",
     "wsr_level_ssim_workspace_floats", "wsr_level_ssim",
+    "wsr_level_distribution_workspace_floats", "wsr_level_distribution",
     "wsr_last_tile_plan", "wsr_last_tile_instantiation",
 ]
 
@@ -170,6 +171,8 @@ def lib() -> C.CDLL:
                                       vp],   # additive export
         "wsr_level_ssim": [vp, i32, vp, i32, vp, i32, vp, i32, C.c_float, C.c_float, i32, i32, i32, i32, vp, vp,
                            vp],   # additive export
+        "wsr_level_distribution": [vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, i32, C.c_float, i32, i32, i32, i32, vp, vp,
+                                   vp],   # additive export
         "wsr_last_tile_plan": [C.POINTER(C.c_int32)],   # additive export (diagnostic)
         "wsr_last_tile_instantiation": [C.POINTER(C.c_int32)],   # additive export (diagnostic)
     }
@@ -192,6 +195,8 @@ def lib() -> C.CDLL:
         getattr(L, name).restype = C.c_int64
     L.wsr_level_ssim_workspace_floats.argtypes = [i32, i32, i32, i32, i32]
     L.wsr_level_ssim_workspace_floats.restype = C.c_int64
+    L.wsr_level_distribution_workspace_floats.argtypes = [i32, i32, i32, i32, i32, i32]
+    L.wsr_level_distribution_workspace_floats.restype = C.c_int64
     if L.wsr_abi_version() != 9:
         raise RuntimeError("libwindsr_hip.so ABI version mismatch")
     _lib = L

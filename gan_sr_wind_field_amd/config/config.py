@@ -44,13 +44,16 @@ Extension (optional keys, defaults keep reference behaviour):
             --test also writes the structural similarity of network and baseline with the truth on horizontal planes,
             per field, per wind component and per z level (ssim.py, csrc/ssim.hip); validation epochs add val_SSIM and
             Trilinear_SSIM to the metrics
+  [DISTRIBUTION] bin_width / speed_bins / sectors / calm / per_level
+            --test also writes the frequency distribution of the horizontal wind speed and the wind rose of the truth,
+            the network and the baseline, with the scores between them (distribution.py, csrc/distribution.hip)
 """
 from __future__ import annotations
 
 import ast
 import math
 from configparser import ConfigParser
-from typing import Any, List, Sequence, Tuple
+from typing import Any, List, Optional, Sequence, Tuple
 
 _B, _I, _F, _S, _W = "bool", "int", "float", "str", "word"  # (word: a lower-cased string)
 
@@ -640,6 +643,46 @@ class SsimConfig(OptionalSection):
         return bool(self.present)
 
 
+class DistributionConfig(OptionalSection):
+    """[DISTRIBUTION] (extension): the frequency distribution of the horizontal wind speed and the wind rose of HR, SR
+    and the trilinear baseline in ``run.py --test`` (distribution.py, csrc/distribution.hip); absent section = off, and
+    never printed by ``asINI``.  ``bin_width`` > 0: the width of a speed bin in m/s, required; ``speed_bins``: 2 .. 64,
+    the last one open-ended; ``sectors``: even, 4 .. 36, sector 0 centred on the grid's +y, counted clockwise; ``calm``
+    >= 0: horizontal speeds <= calm (m/s) have no direction and go to the calm class; ``per_level``: ``--test`` also
+    writes ``<name>____wind_distribution_levels.csv``."""
+
+    bin_width: Optional[float] = None
+    speed_bins: int = 32
+    sectors: int = 16
+    calm: float = 0.5
+    per_level: bool = False
+    _section, _printed = "DISTRIBUTION", False
+    _schema = (("bin_width", _F), ("speed_bins", _I), ("sectors", _I), ("calm", _F), ("per_level", _B))
+
+    setDistributionConfig = OptionalSection.load
+
+    def validate(self) -> None:
+        if not self.present:
+            return
+        from ..distribution import MAX_SECTORS, MAX_SPEED_BINS, MIN_SECTORS, MIN_SPEED_BINS
+        if self.bin_width is None:
+            raise ValueError("[DISTRIBUTION] bin_width must be given (m/s, > 0): it has no default")
+        if not (self.bin_width > 0 and math.isfinite(self.bin_width)):
+            raise ValueError(f"[DISTRIBUTION] bin_width must be a finite number > 0, not {self.bin_width}")
+        if not MIN_SPEED_BINS <= self.speed_bins <= MAX_SPEED_BINS:
+            raise ValueError(f"[DISTRIBUTION] speed_bins must be {MIN_SPEED_BINS} .. {MAX_SPEED_BINS}, not "
+                             f"{self.speed_bins}")
+        if self.sectors % 2 or not MIN_SECTORS <= self.sectors <= MAX_SECTORS:
+            raise ValueError(f"[DISTRIBUTION] sectors must be even and {MIN_SECTORS} .. {MAX_SECTORS}, not {self.sectors}")
+        if not (self.calm >= 0 and math.isfinite(self.calm)):
+            raise ValueError(f"[DISTRIBUTION] calm must be a finite number >= 0, not {self.calm}")
+
+    @property
+    def on(self) -> bool:
+        """``--test`` takes the count tables and writes the distribution files"""
+        return bool(self.present)
+
+
 class Config(IniConfig):
     name: str = "default_name"
     model: str = "default_model"
@@ -672,6 +715,7 @@ class Config(IniConfig):
     spectral_loss: SpectralLossConfig = SpectralLossConfig()
     degradation: DegradationConfig = DegradationConfig()
     ssim: SsimConfig = SsimConfig()
+    distribution: DistributionConfig = DistributionConfig()
     compute_dtype: str = "fp32"
     is_train: bool
     is_use: bool
@@ -685,6 +729,8 @@ class Config(IniConfig):
                  ("eval", lambda c: c.gan_config.interpolate_z), ("ensemble", None), ("tile", None),
                  ("diagnostics", None), ("spectrum", None), ("spectral_loss", None),
                  ("degradation", lambda c: c.scale), ("ssim", None))
+    # (the sections above are a pinned list; later extensions load and print behind them, by the same rules)
+    _optional_later = (("distribution", None),)
 
     def __init__(self, ini_path):
         parser = ConfigParser(allow_no_value=True)
@@ -703,7 +749,7 @@ class Config(IniConfig):
                 setattr(self, attr, None)
         if parser.has_section("DIST"):
             self.dist.setDistConfig(parser["DIST"])
-        for attr, given in self._optional:
+        for attr, given in self._optional + self._optional_later:
             sec = getattr(self, attr)
             sec.load(parser[sec._section] if parser.has_section(sec._section) else None)
             sec.validate(*(() if given is None else (given(self),)))
@@ -734,7 +780,7 @@ class Config(IniConfig):
         for sec in sections:
             if sec is not None:
                 out += "\n" + str(sec)
-        for attr, _ in self._optional:  # (absent: the text of a file without the extension, unchanged)
+        for attr, _ in self._optional + self._optional_later:  # (absent: the text of a file without the extension, unchanged)
             sec = getattr(self, attr)
             if sec.present and sec._printed:
                 out += "\n" + str(sec)

@@ -1509,3 +1509,59 @@ def level_ssim(HR: Tensor, SR: Tensor, TL: Tensor, win: int = 11, sigma: float =
     check(L.wsr_level_ssim(_p(HR), HR.shape[1], _p(SR), SR.shape[1], _p(TL), TL.shape[1], _p(taps), int(win), c1, c2, B, X,
                            Y, NZ, _p(ws), _p(out), _stream()), "level_ssim")
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# wind-speed distribution and wind rose ([DISTRIBUTION]; csrc/distribution.hip)
+# ---------------------------------------------------------------------------------------------------------------------
+DISTRIBUTION_MAX_SPEED_BINS = 64  # WSR_DISTRIBUTION_MAX_SPEED_BINS
+DISTRIBUTION_MAX_SECTORS = 36  # WSR_DISTRIBUTION_MAX_SECTORS
+DISTRIBUTION_LDS_COUNTERS = 15360  # WSR_DISTRIBUTION_LDS_COUNTERS
+_distribution_tables: dict = {}
+
+
+def distribution_level_chunk(NZ: int, speed_bins: int, sectors: int) -> int:
+    """The consecutive levels one workgroup of ``wsr_level_distribution`` counts"""
+    return min(int(NZ), DISTRIBUTION_LDS_COUNTERS // (int(speed_bins) * (int(sectors) + 1)))
+
+
+def _distribution_tables_on(device, tables) -> Tensor:
+    """``edge2``, ``bx``, ``by`` of a ``distribution.DistributionTables`` as one fp32 tensor on ``device``: uploaded once
+    per (device, parameters)"""
+    key = (device.index, tables.UVW_MAX, tables.bin_width, tables.speed_bins, tables.sectors, tables.calm)
+    t = _distribution_tables.get(key)
+    if t is None:
+        if len(_distribution_tables) > 64:
+            _distribution_tables.clear()
+        t = _distribution_tables[key] = torch.cat([tables.edge2, tables.bx, tables.by]).float().to(device).contiguous()
+    return t
+
+
+def level_distribution(HR: Tensor, SR: Tensor, TL: Optional[Tensor], tables, out: Optional[Tensor] = None) -> Tensor:
+    """The count table per sample, z level and source -> float64 (B, NZ, 3, NS, ND + 1): the number of voxels of every
+    horizontal plane of ``HR``, ``SR`` and the baseline ``TL`` (B, C >= 3, X, Y, NZ; channels 0 and 1 are read) in every
+    class (speed bin, direction sector or calm) of ``tables`` = ``distribution.distribution_tables(...)``, the classes
+    those of ``distribution.py`` voxel for voxel.  ``TL`` None: zeros in its slices.  Integer counting, no floating-point
+    atomics: the same bits on every call, equal to ``distribution.level_distribution_reference``.  ``out``: a float64
+    (B, NZ, 3, NS, ND + 1) slice to write into (``wsr_level_distribution``)."""
+    from . import distribution
+
+    _need_cuda(HR, SR, TL, out)
+    B, X, Y, NZ = _same_grid("level_distribution", HR, SR=SR, **({} if TL is None else {"TL": TL}))
+    ns, nd = int(tables.speed_bins), int(tables.sectors)
+    distribution.check_parameters(tables.bin_width, ns, nd, tables.calm, "level_distribution")
+    if tables.edge2.numel() != ns - 1 or tables.bx.numel() != nd // 2 or tables.by.numel() != nd // 2:
+        raise ValueError(f"level_distribution wants tables of {ns - 1} edges and {nd // 2} boundaries, got "
+                         f"{tables.edge2.numel()}, {tables.bx.numel()} and {tables.by.numel()}")
+    if B > 65535 or X * Y >= 2 ** 31 or X * Y * NZ >= 2 ** 31:
+        raise ValueError(f"level_distribution: at most 65535 samples, 2^31 - 1 columns and 2^31 - 1 voxels per sample, not "
+                         f"B = {B}, X = {X}, Y = {Y}, NZ = {NZ}")
+    out = _sums_out("level_distribution", out, (B, NZ, 3, ns, nd + 1), HR.device)
+    L = _lib.lib()
+    tab = _distribution_tables_on(HR.device, tables)
+    edge2, bx, by = tab[:ns - 1], tab[ns - 1:ns - 1 + nd // 2], tab[ns - 1 + nd // 2:]
+    ws = _workspace(L.wsr_level_distribution_workspace_floats(B, X, Y, NZ, ns, nd), HR.device)
+    check(L.wsr_level_distribution(_p(HR), HR.shape[1], _p(SR), SR.shape[1], _p(TL), 0 if TL is None else TL.shape[1],
+                                   _p(edge2), ns, _p(bx), _p(by), nd, float(tables.calm2), B, X, Y, NZ, _p(ws), _p(out),
+                                   _stream()), "level_distribution")
+    return out

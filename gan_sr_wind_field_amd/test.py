@@ -63,6 +63,23 @@ loop with ``ssim.level_ssim_reference`` on the host tensors - and write
     ./test_output/<cfg.name>____ssim_reverse_interpolate.csv      (+ ``averages_ssim_reverse_interpolate.csv``,
         ``..._ssim_levels_reverse_interpolate.csv``) with ``reverse_interpolate``: the same on the raw truth and the
         re-levelled SR and baseline
+
+With a ``[DISTRIBUTION]`` section both loops also add the count table speed bin x (direction sector, calm) per level and
+source (HR, SR, baseline) of every batch (``distribution.py``) into one (NZ, 3, NS, ND + 1) table - the device loop with
+ONE ``hip_ops.level_distribution`` launch per batch on the stored baseline (which it then builds for every batch), its
+table a device tensor read once after the last batch; the host loop with ``distribution.level_distribution_reference``
+on the host tensors - and write
+    ./test_output/<cfg.name>____wind_distribution.csv             one row ``bin,`` + ``SPEED_COLUMNS`` per speed bin,
+                                                                   summed over fields and levels
+    ./test_output/<cfg.name>____wind_rose.csv                     one row ``sector,`` + ``ROSE_COLUMNS`` per sector and
+                                                                   a last row ``calm``
+    ./test_output/<cfg.name>____wind_distribution_levels.csv      (``per_level``) one row ``level,`` + ``SUMMARY_COLUMNS``
+                                                                   per z level, summed over the fields
+    ./test_output/averages_distribution.csv                       one appended row per run: ``SUMMARY_COLUMNS`` of the
+                                                                   whole set
+    ./test_output/<cfg.name>____wind_distribution_reverse_interpolate.csv   (+ ``..._wind_rose_reverse_interpolate.csv``,
+        ``..._wind_distribution_levels_reverse_interpolate.csv``, ``averages_distribution_reverse_interpolate.csv``) with
+        ``reverse_interpolate``: the same on the raw truth and the re-levelled SR and baseline
 """
 from __future__ import annotations
 
@@ -79,6 +96,8 @@ import torch.nn as nn
 
 from .GAN_models.wind_field_GAN_3D import calculate_PSNR, wind_field_GAN_3D
 from .diagnostics import PROFILE_COLUMNS, level_sums_reference, profile_from_sums
+from .distribution import (ROSE_COLUMNS, SPEED_COLUMNS, SUMMARY_COLUMNS, distribution_from_counts, distribution_tables,
+                           level_distribution_reference)
 from .process_data import reverse_interpolate_z_axis
 from .ssim import SSIM_COLUMNS, columns_from_sums, level_ssim_reference, n_positions
 from .spectra import SPECTRUM_COLUMNS, grid_spacing, level_spectra_reference, mode_counts, spectrum_from_sums
@@ -349,6 +368,43 @@ class _Ssim(_LevelSums):
                     f.write(f"{lvl}," + ",".join(str(v) for v in row) + "\n")
 
 
+class _Distribution(_LevelSums):
+    """[DISTRIBUTION]: counts (B, NZ, 3, NS, ND + 1); the speed distribution and the wind rose of the test set, the row
+    of ``averages_distribution<suffix>.csv`` and, with ``per_level``, the summary scalars of every level.  No per-field
+    file.  ``bin_width``: in m/s."""
+
+    stem = "wind_"
+
+    def __init__(self, fn, bin_width, per_level, *where):
+        super().__init__(fn, *where)
+        self.bin_width, self.per_level = bin_width, per_level
+        self.averages_path = os.path.join(self.folder, f"averages_distribution{self.suffix}.csv")
+        _header(self.averages_path, "Name," + ",".join(SUMMARY_COLUMNS))
+
+    def close(self):
+        super().close()
+        table = None if self.total is None else self.total.cpu()  # the ONE read
+        dist = None if table is None else distribution_from_counts(table.sum(dim=0), self.bin_width)
+        for part, first, key, columns in (("distribution", "bin", "speed", SPEED_COLUMNS),
+                                          ("rose", "sector", "rose", ROSE_COLUMNS)):
+            with open(self.path(part), "w") as f:
+                f.write(first + "," + ",".join(columns) + "\n")
+                if dist is not None:
+                    n = len(dist[key][columns[0]])
+                    for row in range(n):
+                        label = "calm" if key == "rose" and row == n - 1 else str(row)
+                        f.write(label + "," + ",".join(str(dist[key][c][row]) for c in columns) + "\n")
+        if dist is not None:
+            with open(self.averages_path, "a") as f:
+                f.write(self.name + "," + ",".join(str(dist["summary"][k]) for k in SUMMARY_COLUMNS) + "\n")
+        if self.per_level:
+            with open(self.path("distribution_levels"), "w") as f:
+                f.write("level," + ",".join(SUMMARY_COLUMNS) + "\n")
+                for lvl in range(0 if table is None else table.shape[0]):
+                    summary = distribution_from_counts(table[lvl], self.bin_width)["summary"]
+                    f.write(f"{lvl}," + ",".join(str(summary[k]) for k in SUMMARY_COLUMNS) + "\n")
+
+
 def _outputs(cfg, gan, uvw, d, suffix, on_device, folder=OUT_DIR):
     """The extra outputs of one set of levels that ``cfg`` asks for, each yielded as soon as its files are open; the
     sums come from ``hip_ops`` with ``on_device`` (the device loop), else from the host references.  ``d``: the mean grid
@@ -372,6 +428,11 @@ def _outputs(cfg, gan, uvw, d, suffix, on_device, folder=OUT_DIR):
         ssim, par = hip_ops.level_ssim if on_device else level_ssim_reference, (cfg.ssim.window_size, cfg.ssim.sigma,
                                                                                  cfg.ssim.data_range)
         yield _Ssim(lambda HR, SR, TL, Z: ssim(HR, SR, TL, *par), par[0], cfg.ssim.per_level, *where)
+    if cfg.distribution.on:
+        dc = cfg.distribution
+        dist, tables = (hip_ops.level_distribution if on_device else level_distribution_reference,
+                        distribution_tables(uvw, dc.bin_width, dc.speed_bins, dc.sectors, dc.calm))
+        yield _Distribution(lambda HR, SR, TL, Z: dist(HR, SR, TL, tables), dc.bin_width, dc.per_level, *where)
 
 
 class _LevelSet:

@@ -748,6 +748,31 @@ int wsr_level_ssim(const float* hr, int32_t hr_c, const float* sr, int32_t sr_c,
                    const float* taps, int32_t win, float c1, float c2, int32_t B, int32_t X, int32_t Y, int32_t NZ,
                    float* workspace, double* out, void* stream);
 
+/* ---- wind-speed distribution and wind rose ([DISTRIBUTION]; csrc/distribution.hip) ----------------------------
+ * wsr_level_distribution: out (B, NZ, 3, ns, nd + 1) doubles, written completely: per sample, z level and source
+ * (0 hr, 1 sr, 2 tl; fp32 planar (B, c, X, Y, NZ), channels 0 = u and 1 = v read) the number of voxels of the plane in
+ * every class (speed bin j, sector): in fp32, every product and sum rounded, nothing contracted,
+ *    hs2 = u u + v v;   j = the number of i in [0, ns - 1) with hs2 >= edge2[i]   (edge2 ascending; a NaN: 0)
+ *    p = (-u, -v);   cross_k(q) = by[k] q.x - bx[k] q.y, k in [0, nd / 2);
+ *    second = cross_0(p) < 0 || (cross_0(p) == 0 && cross_1(p) > 0);
+ *    q = second ? -p : p;   cnt = the number of k with cross_k(q) >= 0;
+ *    sector = max(cnt, 1) - 1 + (second ? nd / 2 : 0);   sector = nd (calm) unless hs2 > calm2
+ * edge2 (ns - 1 floats), bx, by (nd / 2 floats each): device, fp32.  Every (b, z, source) slice sums to X * Y.  tl may
+ * be NULL: its slices are written as zeros.  Integer counting in LDS and in the workspace, no floating-point atomics:
+ * the same bits on every call.  A workgroup counts min(NZ, WSR_DISTRIBUTION_LDS_COUNTERS / (ns (nd + 1))) consecutive
+ * levels.
+ * workspace: wsr_level_distribution_workspace_floats(B, X, Y, NZ, ns, nd) 4-byte words (0 for arguments the entry
+ * refuses): the integer tables.  A null pointer (but tl), a channel count < 3, ns outside 2 .. 64, nd odd or outside
+ * 4 .. 36, a non-positive size: WSR_EINVAL; B > 65535, X * Y >= 2^31 or X * Y * NZ >= 2^31: WSR_EUNSUPPORTED; nothing is
+ * written in either case. */
+#define WSR_DISTRIBUTION_MAX_SPEED_BINS 64
+#define WSR_DISTRIBUTION_MAX_SECTORS 36
+#define WSR_DISTRIBUTION_LDS_COUNTERS 15360
+int64_t wsr_level_distribution_workspace_floats(int32_t B, int32_t X, int32_t Y, int32_t NZ, int32_t ns, int32_t nd);
+int wsr_level_distribution(const float* hr, int32_t hr_c, const float* sr, int32_t sr_c, const float* tl, int32_t tl_c,
+                           const float* edge2, int32_t ns, const float* bx, const float* by, int32_t nd, float calm2,
+                           int32_t B, int32_t X, int32_t Y, int32_t NZ, void* workspace, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
