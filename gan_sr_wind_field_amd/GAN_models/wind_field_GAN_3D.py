@@ -70,6 +70,9 @@ class wind_field_GAN_3D(BaseGAN):
         if self._spectral_on():  # ([SPECTRAL_LOSS]: one more logged term; absent section, exactly the keys above)
             self.train_G_loss_dict["spectral"] = torch.zeros(1)
             self.validation_G_loss_dict["spectral"] = torch.zeros(1)
+        if self._ssim_loss_on():  # ([SSIM_LOSS]: likewise, behind ``spectral`` when both sections are present)
+            self.train_G_loss_dict["ssim"] = torch.zeros(1)
+            self.validation_G_loss_dict["ssim"] = torch.zeros(1)
         self.D_loss_dict = _zeros_dict(("train_loss", "validation_loss"))
         self.hist_dict = {
             "val_grad_G_first_layer": torch.zeros(1), "val_grad_G_last_layer": torch.zeros(1),
@@ -332,12 +335,18 @@ class wind_field_GAN_3D(BaseGAN):
         """``[SPECTRAL_LOSS]`` is in the configuration: the generator loss carries the energy-spectrum term"""
         return bool(getattr(getattr(self.cfg, "spectral_loss", None), "on", False))
 
+    def _ssim_loss_on(self) -> bool:
+        """``[SSIM_LOSS]`` is in the configuration: the generator loss carries the SSIM term"""
+        return bool(getattr(getattr(self.cfg, "ssim_loss", None), "on", False))
+
     def log_G_losses(self, fake_HR, losses: dict, training_iteration: bool):
         target = self.train_G_loss_dict if training_iteration else self.validation_G_loss_dict
         for k in _G_LOSS_KEYS:
             target[k] = losses[k]
         if "spectral" in losses:
             target["spectral"] = losses["spectral"]
+        if "ssim" in losses:
+            target["ssim"] = losses["ssim"]
         if not training_iteration:
             self.metrics_dict["pix_loss_unscaled"] = losses["pix"] / self.cfg.training.pixel_loss_weight
             self.hist_dict["SR_pix_distribution"] = fake_HR.detach().cpu().numpy()
@@ -384,6 +393,12 @@ class wind_field_GAN_3D(BaseGAN):
             from ..spectral_loss import spectral_loss
             spec = spectral_loss(HR, fake_HR, self.cfg.spectral_loss)
             wkey = wkey + (self.cfg.spectral_loss.weight,)
+        # [SSIM_LOSS]: the SSIM term (ssim_loss.py), by the same rules: the next entry of the core vector, after ``spectral``
+        ssim_term = None
+        if self._ssim_loss_on():
+            from ..ssim_loss import ssim_loss
+            ssim_term = ssim_loss(HR, fake_HR, self.cfg.ssim_loss)
+            wkey = wkey + (self.cfg.ssim_loss.weight,)
         if getattr(self, "_loss_w", (None,))[0] != wkey:
             self._loss_w = (wkey, torch.tensor([float(v) for v in wkey[1:]], dtype=torch.float32).to(self.device))
         L = {}
@@ -395,10 +410,13 @@ class wind_field_GAN_3D(BaseGAN):
             Lc = torch.stack([v.reshape(()) for v in unweighted[:3]]) * wv[:3]
             Lp = torch.stack([v.reshape(()) for v in unweighted[3:]]) * wv[3:7]
             L.update(zip(keys, Lc.unbind() + Lp.unbind()))
-            if spec is not None:
-                Ls = spec.reshape(1) * wv[7:]
-                L["spectral"] = Ls.reshape(())
-                Lc = torch.cat([Lc, Ls])
+            at = 7
+            for name, extra in (("spectral", spec), ("ssim", ssim_term)):
+                if extra is not None:
+                    Ls = extra.reshape(1) * wv[at:at + 1]
+                    L[name] = Ls.reshape(())
+                    Lc = torch.cat([Lc, Ls])
+                    at += 1
             L["feature_D"] = L["feature_D"].reshape(1)  # (the reference's placeholder is torch.zeros(1): totals are (1,))
             return Lc, Lp
 

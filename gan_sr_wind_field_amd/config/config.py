@@ -40,6 +40,9 @@ Extension (optional keys, defaults keep reference behaviour):
   [DEGRADATION] kernel / sigma / channels
             the LR inputs of training, validation and --test are a box- or gaussian-filtered, then sampled copy of the
             full-resolution channels instead of every scale-th column (degradation.py, csrc/data_degrade.hip)
+  [SSIM_LOSS] weight / window_size / sigma / data_range
+            absent = off; present, the generator loss carries weight * (1 - mean SSIM) of SR against HR on horizontal
+            planes (ssim_loss.py, csrc/ssim_loss.hip), logged as ``ssim``
   [SSIM] window_size / sigma / data_range / per_level / validation
             --test also writes the structural similarity of network and baseline with the truth on horizontal planes,
             per field, per wind component and per z level (ssim.py, csrc/ssim.hip); validation epochs add val_SSIM and
@@ -562,6 +565,44 @@ class SpectralLossConfig(OptionalSection):
         return bool(self.present)
 
 
+class SsimLossConfig(OptionalSection):
+    """[SSIM_LOSS] (extension): a structural-similarity term of the generator loss (ssim_loss.py, csrc/ssim_loss.hip);
+    absent section = off, and not printed by ``asINI``.  ``weight`` (required, > 0: there is no reference default to
+    inherit) multiplies ``L_ssim`` = 1 - the mean over samples, levels, components and valid positions of l cs;
+    ``window_size``: the side of the gaussian window, odd, 3 .. 15 (at most the training patch, checked at the first
+    batch); ``sigma`` > 0: its standard deviation in HR grid cells; ``data_range`` > 0: the range of one normalised wind
+    component, behind C1 and C2.  The keys are independent of ``[SSIM]``, whose defaults the last three share."""
+
+    weight: float = None
+    window_size: int = 11
+    sigma: float = 1.5
+    data_range: float = 2.0
+    _section = "SSIM_LOSS"
+    _schema = (("weight", _F), ("window_size", _I), ("sigma", _F), ("data_range", _F))
+
+    setSsimLossConfig = OptionalSection.load
+
+    def validate(self) -> None:
+        if not self.present:
+            return
+        from ..ssim import MAX_WIN
+        if self.weight is None:
+            raise ValueError("[SSIM_LOSS] weight is required: the weight of the SSIM term in the generator loss")
+        if not (self.weight > 0 and math.isfinite(self.weight)):
+            raise ValueError(f"[SSIM_LOSS] weight must be a finite number > 0, not {self.weight}")
+        if self.window_size % 2 == 0 or not 3 <= self.window_size <= MAX_WIN:
+            raise ValueError(f"[SSIM_LOSS] window_size must be odd and 3 .. {MAX_WIN}, not {self.window_size}")
+        if not (self.sigma > 0 and math.isfinite(self.sigma)):
+            raise ValueError(f"[SSIM_LOSS] sigma must be a finite number > 0, not {self.sigma}")
+        if not (self.data_range > 0 and math.isfinite(self.data_range)):
+            raise ValueError(f"[SSIM_LOSS] data_range must be a finite number > 0, not {self.data_range}")
+
+    @property
+    def on(self) -> bool:
+        """the generator loss carries the SSIM term"""
+        return bool(self.present)
+
+
 class DegradationConfig(OptionalSection):
     """[DEGRADATION] (extension): anti-aliased LR inputs (degradation.py, csrc/data_degrade.hip); absent section = off -
     LR is every ``scale``-th HR column, as in the reference - and never printed by ``asINI``.  ``kernel`` (required):
@@ -716,6 +757,7 @@ class Config(IniConfig):
     degradation: DegradationConfig = DegradationConfig()
     ssim: SsimConfig = SsimConfig()
     distribution: DistributionConfig = DistributionConfig()
+    ssim_loss: SsimLossConfig = SsimLossConfig()
     compute_dtype: str = "fp32"
     is_train: bool
     is_use: bool
@@ -730,7 +772,7 @@ class Config(IniConfig):
                  ("diagnostics", None), ("spectrum", None), ("spectral_loss", None),
                  ("degradation", lambda c: c.scale), ("ssim", None))
     # (the sections above are a pinned list; later extensions load and print behind them, by the same rules)
-    _optional_later = (("distribution", None),)
+    _optional_later = (("distribution", None), ("ssim_loss", None))
 
     def __init__(self, ini_path):
         parser = ConfigParser(allow_no_value=True)

@@ -1512,6 +1512,72 @@ def level_ssim(HR: Tensor, SR: Tensor, TL: Tensor, win: int = 11, sigma: float =
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# SSIM loss of generator training ([SSIM_LOSS]; csrc/ssim_loss.hip)
+# ---------------------------------------------------------------------------------------------------------------------
+class _SsimPairSums(torch.autograd.Function):
+    """``wsr_ssim_pair_sums`` with ``wsr_ssim_pair_sums_bwd`` as backward: P (B, NZ, 3, 2) = [sum of l cs, sum of cs];
+    gradient flows only towards SR, from both columns.  Nothing is saved but the inputs: the backward recomputes."""
+
+    @staticmethod
+    def forward(ctx, hr: Tensor, sr: Tensor, taps: Tensor, win: int, c1: float, c2: float):
+        B, _, X, Y, NZ = sr.shape
+        L = _lib.lib()
+        out = torch.empty((B, NZ, 3, 2), dtype=torch.float64, device=sr.device)
+        ws = _workspace(L.wsr_ssim_pair_sums_workspace_floats(B, X, Y, NZ, win), sr.device)
+        check(L.wsr_ssim_pair_sums(_p(hr), hr.shape[1], _p(sr), sr.shape[1], _p(taps), win, c1, c2, B, X, Y, NZ, _p(ws),
+                                   _p(out), _stream()), "ssim_pair_sums")
+        ctx.meta = (win, c1, c2)
+        ctx.save_for_backward(hr, sr, taps)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable  # (the kernel's result is no graph: a double backward is refused)
+    def backward(ctx, g: Tensor):
+        if not ctx.needs_input_grad[1]:
+            return None, None, None, None, None, None
+        hr, sr, taps = ctx.saved_tensors
+        win, c1, c2 = ctx.meta
+        B, C_, X, Y, NZ = sr.shape
+        L = _lib.lib()
+        gout = g.to(torch.float64).contiguous()
+        dsr = torch.empty((B, 3, X, Y, NZ), dtype=torch.float32, device=g.device)
+        check(L.wsr_ssim_pair_sums_bwd(_p(hr), hr.shape[1], _p(sr), C_, _p(gout), _p(taps), win, c1, c2, B, X, Y, NZ,
+                                       _p(dsr), _stream()), "ssim_pair_sums_bwd")
+        if C_ > 3:  # (surplus channels are never read: their gradient is zero)
+            full = torch.zeros((B, C_, X, Y, NZ), dtype=torch.float32, device=g.device)
+            full[:, :3] = dsr
+            dsr = full
+        return None, dsr, None, None, None, None
+
+
+def ssim_pair_sums(HR: Tensor, SR: Tensor, win: int = 11, sigma: float = 1.5, data_range: float = 2.0) -> Tensor:
+    """Two sums per sample, z level and wind component of ``HR`` and ``SR`` (B, C >= 3, X, Y, NZ; channels 0..2 are read,
+    surplus ones never) -> float64 (B, NZ, 3, 2) = [sum of l cs, sum of cs] over the valid positions of the window
+    ``ssim.taps(win, sigma)``: the first two sums of ``level_ssim``, bit for bit (``wsr_ssim_pair_sums``).
+    Differentiable: both columns carry gradient, and only towards SR (``wsr_ssim_pair_sums_bwd``: one launch that
+    recomputes the moments and applies the adjoint of the valid window).  No atomics: the same bits on every call,
+    forward and backward."""
+    from . import ssim
+
+    _need_cuda(HR, SR)
+    for name, t in (("HR", HR), ("SR", SR)):
+        if t.dim() != 5 or t.shape[1] < 3 or t.numel() == 0 or not t.is_floating_point():
+            raise ValueError(f"ssim_pair_sums wants {name} as a floating-point (B, C >= 3, X, Y, NZ) tensor, got "
+                             f"{t.dtype} {tuple(t.shape)}")
+    B, _, X, Y, NZ = HR.shape
+    if (SR.shape[0],) + tuple(SR.shape[2:]) != (B, X, Y, NZ):
+        raise ValueError(f"ssim_pair_sums: SR {tuple(SR.shape)} does not match HR {tuple(HR.shape)}")
+    ssim.check_window(win, sigma, "ssim_pair_sums")
+    ssim.check_domain(X, Y, win, "ssim_pair_sums")
+    c1, c2 = ssim.constants(data_range)
+    if NZ > SSIM_MAX_NZ or B > 65535 or X > 32768 or Y > 32768 or X * Y * NZ >= 2 ** 31:
+        raise ValueError(f"ssim_pair_sums: at most {SSIM_MAX_NZ} levels, 65535 samples, 32768 points in x and y and "
+                         f"2^31 - 1 voxels per sample, not B = {B}, X = {X}, Y = {Y}, NZ = {NZ}")
+    taps = _ssim_taps_on(HR.device, win, sigma)
+    return _SsimPairSums.apply(HR.detach().contiguous().float(), SR.contiguous().float(), taps, int(win), c1, c2)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # wind-speed distribution and wind rose ([DISTRIBUTION]; csrc/distribution.hip)
 # ---------------------------------------------------------------------------------------------------------------------
 DISTRIBUTION_MAX_SPEED_BINS = 64  # WSR_DISTRIBUTION_MAX_SPEED_BINS

@@ -773,6 +773,34 @@ int wsr_level_distribution(const float* hr, int32_t hr_c, const float* sr, int32
                            const float* edge2, int32_t ns, const float* bx, const float* by, int32_t nd, float calm2,
                            int32_t B, int32_t X, int32_t Y, int32_t NZ, void* workspace, double* out, void* stream);
 
+/* ---- SSIM loss of generator training ([SSIM_LOSS]; csrc/ssim_loss.hip) -----------------------------------------
+ * wsr_ssim_pair_sums: out (B, NZ, 3, 2) doubles: per sample, z level and component c (channels 0..2 of hr
+ * (B, hr_c, X, Y, NZ) and sr (B, sr_c, ...), fp32 planar) the sums over the valid window positions of the plane of
+ * (l cs, cs), by the definitions, the arithmetic, the tile geometry and the summation order of wsr_level_ssim: both
+ * columns carry the bits of its ssim_sr and cs_sr on the same inputs, and equal the number of positions exactly when sr
+ * equals hr bit for bit.  workspace: wsr_ssim_pair_sums_workspace_floats(B, X, Y, NZ, win) floats (0 for arguments the
+ * entry refuses).  Nothing is saved for the backward.
+ * wsr_ssim_pair_sums_bwd: dsr (B, 3, X, Y, NZ) fp32, every element written: the vector-Jacobian product of both columns
+ * towards sr.  With gout (B, NZ, 3, 2) doubles (device) = (G0, G1) of a plane and, per valid position,
+ *    D1 = mu_a^2 + mu_s^2 + c1,  D2 = var_a + var_s + c2,  h = G0 l + G1
+ *    alpha = G0 cs (2 mu_a - 2 mu_s l) / D1 + h (2 mu_s cs - 2 mu_a) / D2,   beta = -h cs / D2,   gamma = 2 h / D2
+ *    dsr(p) = (g2^T alpha)(p) + 2 s(p) (g2^T beta)(p) + a(p) (g2^T gamma)(p)
+ *    (g2^T m)(px, py) = sum_{i, j} g(i) g(j) m(px - i, py - j) over the valid positions (px - i, py - j)
+ * One launch that recomputes the moments (the forward's operation sequence) around a tile of output pixels; fp32 without
+ * contraction, no atomics, no zero fill, the grid a function of the shape: the same bits on every call.
+ * wsr_ssim_pair_sums_bwd_tile: tile[0 .. 3) = (TX, TY, ZC), the output pixels and levels a workgroup of the backward
+ * owns, a function of (X, Y, NZ, win) alone (host only).
+ * The refusals of all three are those of wsr_level_ssim (without tl): WSR_EINVAL / WSR_EUNSUPPORTED, nothing launched,
+ * nothing written. */
+int64_t wsr_ssim_pair_sums_workspace_floats(int32_t B, int32_t X, int32_t Y, int32_t NZ, int32_t win);
+int wsr_ssim_pair_sums(const float* hr, int32_t hr_c, const float* sr, int32_t sr_c, const float* taps, int32_t win,
+                       float c1, float c2, int32_t B, int32_t X, int32_t Y, int32_t NZ, float* workspace, double* out,
+                       void* stream);
+int wsr_ssim_pair_sums_bwd(const float* hr, int32_t hr_c, const float* sr, int32_t sr_c, const double* gout,
+                           const float* taps, int32_t win, float c1, float c2, int32_t B, int32_t X, int32_t Y, int32_t NZ,
+                           float* dsr, void* stream);
+int wsr_ssim_pair_sums_bwd_tile(int32_t X, int32_t Y, int32_t NZ, int32_t win, int32_t* tile);
+
 #ifdef __cplusplus
 }
 #endif
