@@ -780,6 +780,22 @@ class wind_field_GAN_3D(BaseGAN):
         tables = distribution_tables(UVW_MAX, bin_width, dc.speed_bins, dc.sectors, dc.calm)
         return _level_sums("level_distribution", level_distribution_reference, self.cfg.scale, HR, SR, LR, (), (tables,))
 
+    # ------------------------------------------------------------------ fractions skill score ([FSS])
+    def level_fss(self, HR, SR, LR, UVW_MAX):
+        """The five sums of ``fss.py`` per sample, z level, threshold and neighbourhood of a batch -> float64
+        (B, NZ, NT, NN, 5) on the tensors' device, with the thresholds and scales of ``[FSS]`` (without the section:
+        thresholds 5, 10, 15, 20 m/s and the default scales) and ``UVW_MAX`` to denormalise: the trilinear baseline of
+        ``LR`` is built here (``wsr_trilinear_xy`` on a GPU, ``F.interpolate`` on a CPU), the sums come from
+        ``hip_ops.level_fss`` on a GPU and from ``fss.level_fss_reference`` on a CPU.  Reads no weights: the same inside
+        ``ema_scope()``."""
+        from ..config.config import FssConfig
+        from ..fss import fss_tables, level_fss_reference
+
+        fc = getattr(self.cfg, "fss", None) or FssConfig
+        thresholds = fc.thresholds if fc.thresholds is not None else [5.0, 10.0, 15.0, 20.0]
+        return _level_sums("level_fss", level_fss_reference, self.cfg.scale, HR, SR, LR, (),
+                           (fss_tables(UVW_MAX, thresholds), tuple(fc.scales)))
+
     def make_new_labels(self, it):
         """Real / fake label vectors of this iteration (reference :627-678)."""
         t = self.cfg.training

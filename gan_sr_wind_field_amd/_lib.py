@@ -34,6 +34,7 @@ EXPORTS = [
     "wsr_level_ssim_workspace_floats", "wsr_level_ssim",
     "wsr_level_distribution_workspace_floats", "wsr_level_distribution",
     "wsr_ssim_pair_sums_workspace_floats", "wsr_ssim_pair_sums", "wsr_ssim_pair_sums_bwd", "wsr_ssim_pair_sums_bwd_tile",
+    "wsr_level_fss_workspace_floats", "wsr_level_fss",
     "wsr_last_tile_plan", "wsr_last_tile_instantiation",
 ]
 
@@ -179,6 +180,8 @@ def lib() -> C.CDLL:
         "wsr_ssim_pair_sums_bwd": [vp, i32, vp, i32, vp, vp, i32, C.c_float, C.c_float, i32, i32, i32, i32, vp,
                                    vp],   # additive export
         "wsr_ssim_pair_sums_bwd_tile": [i32, i32, i32, i32, C.POINTER(C.c_int32)],   # additive export
+        "wsr_level_fss": [vp, i32, vp, i32, vp, i32, vp, i32, C.POINTER(C.c_int32), i32, i32, i32, i32, i32, vp, vp,
+                          vp],   # additive export
         "wsr_last_tile_plan": [C.POINTER(C.c_int32)],   # additive export (diagnostic)
         "wsr_last_tile_instantiation": [C.POINTER(C.c_int32)],   # additive export (diagnostic)
     }
@@ -205,6 +208,8 @@ def lib() -> C.CDLL:
     L.wsr_level_distribution_workspace_floats.restype = C.c_int64
     L.wsr_ssim_pair_sums_workspace_floats.argtypes = [i32, i32, i32, i32, i32]
     L.wsr_ssim_pair_sums_workspace_floats.restype = C.c_int64
+    L.wsr_level_fss_workspace_floats.argtypes = [i32, i32, i32, i32, i32, i32, i32]
+    L.wsr_level_fss_workspace_floats.restype = C.c_int64
     if L.wsr_abi_version() != 9:
         raise RuntimeError("libwindsr_hip.so ABI version mismatch")
     _lib = L

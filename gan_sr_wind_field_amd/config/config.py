@@ -50,6 +50,9 @@ Extension (optional keys, defaults keep reference behaviour):
   [DISTRIBUTION] bin_width / speed_bins / sectors / calm / per_level
             --test also writes the frequency distribution of the horizontal wind speed and the wind rose of the truth,
             the network and the baseline, with the scores between them (distribution.py, csrc/distribution.hip)
+  [FSS] thresholds / scales / per_level
+            --test also writes the fractions skill score of network and baseline against the truth per wind-speed
+            threshold and neighbourhood size, the useful scale and the contingency-table scores (fss.py, csrc/fss.hip)
 """
 from __future__ import annotations
 
@@ -59,6 +62,7 @@ from configparser import ConfigParser
 from typing import Any, List, Optional, Sequence, Tuple
 
 _B, _I, _F, _S, _W = "bool", "int", "float", "str", "word"  # (word: a lower-cased string)
+_L = "list"  # (a list literal of numbers; a single number is a list of one)
 
 
 def safe_list_from_string(text, target_type: type) -> list:
@@ -87,6 +91,12 @@ def _read(section, key: str, kind: str):
         return section.getfloat(key)
     if kind == "intlist":
         return safe_list_from_string(section.get(key), int)
+    if kind == _L:
+        try:
+            val = ast.literal_eval(section.get(key))
+        except Exception:
+            raise ValueError(f"{key}: not a list literal") from None
+        return list(val) if isinstance(val, (list, tuple)) else [val]
     if kind == _W:
         return section.get(key).strip().lower()
     return section.get(key)
@@ -321,7 +331,7 @@ class OptionalSection(IniConfig):
             try:
                 val = None if section is None else _read(section, key, kind)
             except ValueError:
-                what = {_B: "True or False", _I: "an integer", _F: "a number"}[kind]
+                what = {_B: "True or False", _I: "an integer", _F: "a number", _L: "a list of numbers"}[kind]
                 raise ValueError(f"[{self._section}] {key} must be {what}, not {section.get(key)!r}") from None
             setattr(self, key, getattr(type(self), key) if val is None else val)
 
@@ -724,6 +734,35 @@ class DistributionConfig(OptionalSection):
         return bool(self.present)
 
 
+class FssConfig(OptionalSection):
+    """[FSS] (extension): the fractions skill score of SR and of the trilinear baseline against HR in ``run.py --test``
+    (fss.py, csrc/fss.hip); absent section = off, and never printed by ``asINI``.  ``thresholds``: 1 .. 8 wind speeds in
+    m/s, each > 0, strictly ascending, required; ``scales``: 1 .. 8 odd neighbourhood sizes in grid cells, strictly
+    ascending, the first one 1, the last one <= 33; ``per_level``: ``--test`` also writes ``<name>____fss_levels.csv``."""
+
+    thresholds: Optional[list] = None
+    scales: tuple = (1, 3, 5, 9, 17, 33)
+    per_level: bool = False
+    _section, _printed = "FSS", False
+    _schema = (("thresholds", _L), ("scales", _L), ("per_level", _B))
+
+    setFssConfig = OptionalSection.load
+
+    def validate(self) -> None:
+        if not self.present:
+            return
+        from ..fss import check_scales, check_thresholds
+        if self.thresholds is None:
+            raise ValueError("[FSS] thresholds must be given (a list of wind speeds in m/s): it has no default")
+        self.thresholds = check_thresholds(self.thresholds, "[FSS]")
+        self.scales = check_scales(self.scales, "[FSS]")
+
+    @property
+    def on(self) -> bool:
+        """``--test`` takes the window sums and writes the score files"""
+        return bool(self.present)
+
+
 class Config(IniConfig):
     name: str = "default_name"
     model: str = "default_model"
@@ -757,6 +796,7 @@ class Config(IniConfig):
     degradation: DegradationConfig = DegradationConfig()
     ssim: SsimConfig = SsimConfig()
     distribution: DistributionConfig = DistributionConfig()
+    fss: FssConfig = FssConfig()
     ssim_loss: SsimLossConfig = SsimLossConfig()
     compute_dtype: str = "fp32"
     is_train: bool
@@ -772,7 +812,7 @@ class Config(IniConfig):
                  ("diagnostics", None), ("spectrum", None), ("spectral_loss", None),
                  ("degradation", lambda c: c.scale), ("ssim", None))
     # (the sections above are a pinned list; later extensions load and print behind them, by the same rules)
-    _optional_later = (("distribution", None), ("ssim_loss", None))
+    _optional_later = (("distribution", None), ("ssim_loss", None), ("fss", None))
 
     def __init__(self, ini_path):
         parser = ConfigParser(allow_no_value=True)

@@ -1631,3 +1631,64 @@ def level_distribution(HR: Tensor, SR: Tensor, TL: Optional[Tensor], tables, out
                                    _p(edge2), ns, _p(bx), _p(by), nd, float(tables.calm2), B, X, Y, NZ, _p(ws), _p(out),
                                    _stream()), "level_distribution")
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# fractions skill score ([FSS]; csrc/fss.hip)
+# ---------------------------------------------------------------------------------------------------------------------
+FSS_TILE = 32  # FS_TILE of csrc/fss_kernels.h: the positions of a workgroup are FSS_TILE x FSS_TILE
+_fss_tables: dict = {}
+
+
+def fss_level_chunk(B: int, X: int, Y: int, NZ: int, scales) -> int:
+    """The consecutive levels one workgroup of ``wsr_level_fss`` stages (``fs_geom`` of csrc/fss_kernels.h)"""
+    S = FSS_TILE + (int(scales[-1]) - 1)
+    CP = S if (S // 2) % 2 else S + 2
+    zc = min(26624 // (S * CP + 2), 16, int(NZ))
+    tiles = -(-int(X) // FSS_TILE) * -(-int(Y) // FSS_TILE)
+    while True:
+        nzc = -(-NZ // zc)
+        ZC = -(-NZ // nzc)
+        if ZC <= 2 or tiles * nzc * B >= 512:
+            return ZC
+        zc = (ZC + 1) // 2
+
+
+def _fss_thr2_on(device, tables) -> Tensor:
+    """``thr2`` of an ``fss.FssTables`` as an fp32 tensor on ``device``: uploaded once per (device, parameters)"""
+    key = (device.index, tables.UVW_MAX, tuple(tables.thresholds))
+    t = _fss_tables.get(key)
+    if t is None:
+        if len(_fss_tables) > 64:
+            _fss_tables.clear()
+        t = _fss_tables[key] = tables.thr2.float().to(device).contiguous()
+    return t
+
+
+def level_fss(HR: Tensor, SR: Tensor, TL: Optional[Tensor], tables, scales=(1, 3, 5, 9, 17, 33),
+              out: Optional[Tensor] = None) -> Tensor:
+    """The five sums of ``fss.py`` per sample, z level, threshold and neighbourhood -> float64 (B, NZ, NT, NN, 5): over
+    every horizontal plane of ``HR``, ``SR`` and the baseline ``TL`` (B, C >= 3, X, Y, NZ; channels 0 and 1 are read) the
+    sums of the squared box-window event counts and of their squared differences, for the thresholds of ``tables`` =
+    ``fss.fss_tables(...)`` and the odd neighbourhoods ``scales``.  ``TL`` None: zeros in entries 3 and 4.  Integer
+    counting, no floating-point atomics: the same bits on every call, equal to ``fss.level_fss_reference``.  ``out``: a
+    float64 (B, NZ, NT, NN, 5) slice to write into (``wsr_level_fss``)."""
+    from . import fss
+
+    _need_cuda(HR, SR, TL, out)
+    B, X, Y, NZ = _same_grid("level_fss", HR, SR=SR, **({} if TL is None else {"TL": TL}))
+    th = fss.check_thresholds(tables.thresholds, "level_fss")
+    sc = fss.check_scales(scales, "level_fss")
+    nt, nn = len(th), len(sc)
+    if tables.thr2.numel() != nt:
+        raise ValueError(f"level_fss wants a table of {nt} squared thresholds, got {tables.thr2.numel()}")
+    if B > 65535 or X * Y >= 2 ** 31 or X * Y * NZ >= 2 ** 31:
+        raise ValueError(f"level_fss: at most 65535 samples, 2^31 - 1 columns and 2^31 - 1 voxels per sample, not "
+                         f"B = {B}, X = {X}, Y = {Y}, NZ = {NZ}")
+    out = _sums_out("level_fss", out, (B, NZ, nt, nn, 5), HR.device)
+    L = _lib.lib()
+    thr2 = _fss_thr2_on(HR.device, tables)
+    ws = _workspace(L.wsr_level_fss_workspace_floats(B, X, Y, NZ, nt, nn, sc[-1]), HR.device)
+    check(L.wsr_level_fss(_p(HR), HR.shape[1], _p(SR), SR.shape[1], _p(TL), 0 if TL is None else TL.shape[1], _p(thr2), nt,
+                          (C.c_int32 * nn)(*sc), nn, B, X, Y, NZ, _p(out), _p(ws), _stream()), "level_fss")
+    return out

@@ -80,6 +80,20 @@ on the host tensors - and write
     ./test_output/<cfg.name>____wind_distribution_reverse_interpolate.csv   (+ ``..._wind_rose_reverse_interpolate.csv``,
         ``..._wind_distribution_levels_reverse_interpolate.csv``, ``averages_distribution_reverse_interpolate.csv``) with
         ``reverse_interpolate``: the same on the raw truth and the re-levelled SR and baseline
+
+With an ``[FSS]`` section both loops also add the five window sums per level, threshold and neighbourhood of every batch
+(``fss.py``) into one (NZ, NT, NN, 5) table - the device loop with ONE ``hip_ops.level_fss`` launch per batch on the stored
+baseline, its table a device tensor read once after the last batch; the host loop with ``fss.level_fss_reference`` on
+the host tensors - and write
+    ./test_output/<cfg.name>____fss.csv                           one row ``threshold,scale,`` + ``FSS_COLUMNS`` per
+                                                                   threshold and scale, pooled over fields and levels
+    ./test_output/<cfg.name>____exceedance.csv                    one row ``threshold,`` + ``EXCEEDANCE_COLUMNS`` per
+                                                                   threshold
+    ./test_output/<cfg.name>____fss_levels.csv                    (``per_level``) one row ``level,threshold,scale,`` +
+                                                                   ``FSS_COLUMNS`` per level, threshold and scale
+    ./test_output/<cfg.name>____fss_reverse_interpolate.csv       (+ ``..._exceedance_reverse_interpolate.csv``,
+        ``..._fss_levels_reverse_interpolate.csv``) with ``reverse_interpolate``: the same on the raw truth and the
+        re-levelled SR and baseline
 """
 from __future__ import annotations
 
@@ -98,6 +112,7 @@ from .GAN_models.wind_field_GAN_3D import calculate_PSNR, wind_field_GAN_3D
 from .diagnostics import PROFILE_COLUMNS, level_sums_reference, profile_from_sums
 from .distribution import (ROSE_COLUMNS, SPEED_COLUMNS, SUMMARY_COLUMNS, distribution_from_counts, distribution_tables,
                            level_distribution_reference)
+from .fss import EXCEEDANCE_COLUMNS, FSS_COLUMNS, fss_from_sums, fss_tables, level_fss_reference
 from .process_data import reverse_interpolate_z_axis
 from .ssim import SSIM_COLUMNS, columns_from_sums, level_ssim_reference, n_positions
 from .spectra import SPECTRUM_COLUMNS, grid_spacing, level_spectra_reference, mode_counts, spectrum_from_sums
@@ -405,6 +420,41 @@ class _Distribution(_LevelSums):
                     f.write(f"{lvl}," + ",".join(str(summary[k]) for k in SUMMARY_COLUMNS) + "\n")
 
 
+class _Fss(_LevelSums):
+    """[FSS]: sums (B, NZ, NT, NN, 5); the scores per threshold and scale and the contingency scores per threshold of
+    the test set, pooled over fields and levels, and, with ``per_level``, the scores of every level.  No per-field file.
+    ``d``: the mean grid spacing in metres."""
+
+    stem = ""
+
+    def __init__(self, fn, thresholds, scales, d, per_level, *where):
+        super().__init__(fn, *where)
+        self.thresholds, self.scales, self.d, self.per_level = thresholds, scales, d, per_level
+
+    def columns(self, table, levels):
+        return fss_from_sums(table, self.scales, self.thresholds, self.d,
+                             self.shape[0] * self.shape[1] * levels * self.nfields)
+
+    def close(self):
+        super().close()
+        table = None if self.total is None else self.total.cpu()  # the ONE read
+        col = None if table is None else self.columns(table.sum(dim=0), table.shape[0])
+        for part, key, first, columns in (("fss", "fss", ("threshold", "scale"), FSS_COLUMNS),
+                                          ("exceedance", "exceedance", ("threshold",), EXCEEDANCE_COLUMNS)):
+            with open(self.path(part), "w") as f:
+                f.write(",".join(first + columns) + "\n")
+                for row in range(0 if col is None else len(col[key]["threshold"])):
+                    f.write(",".join(str(col[key][c][row]) for c in first + columns) + "\n")
+        if self.per_level:
+            with open(self.path("fss_levels"), "w") as f:
+                first = ("threshold", "scale")
+                f.write("level," + ",".join(first + FSS_COLUMNS) + "\n")
+                for lvl in range(0 if table is None else table.shape[0]):
+                    rows = self.columns(table[lvl], 1)["fss"]
+                    for row in range(len(rows["threshold"])):
+                        f.write(f"{lvl}," + ",".join(str(rows[c][row]) for c in first + FSS_COLUMNS) + "\n")
+
+
 def _outputs(cfg, gan, uvw, d, suffix, on_device, folder=OUT_DIR):
     """The extra outputs of one set of levels that ``cfg`` asks for, each yielded as soon as its files are open; the
     sums come from ``hip_ops`` with ``on_device`` (the device loop), else from the host references.  ``d``: the mean grid
@@ -433,6 +483,11 @@ def _outputs(cfg, gan, uvw, d, suffix, on_device, folder=OUT_DIR):
         dist, tables = (hip_ops.level_distribution if on_device else level_distribution_reference,
                         distribution_tables(uvw, dc.bin_width, dc.speed_bins, dc.sectors, dc.calm))
         yield _Distribution(lambda HR, SR, TL, Z: dist(HR, SR, TL, tables), dc.bin_width, dc.per_level, *where)
+    if cfg.fss.on:
+        fc = cfg.fss
+        score, thr = hip_ops.level_fss if on_device else level_fss_reference, fss_tables(uvw, fc.thresholds)
+        yield _Fss(lambda HR, SR, TL, Z: score(HR, SR, TL, thr, fc.scales), fc.thresholds, fc.scales, d, fc.per_level,
+                   *where)
 
 
 class _LevelSet:
@@ -558,7 +613,7 @@ def test(cfg, dataset_test, reverse_interpolate: bool = False):
     log.info("beginning test")
     if cfg.diagnostics.on:  # (the coordinates of the whole test domain)
         gan.x, gan.y = (torch.from_numpy(np.asarray(v)).float().contiguous().to(dev) for v in (dataset_test.x, dataset_test.y))
-    d = grid_spacing(np.asarray(dataset_test.x), np.asarray(dataset_test.y)) if cfg.spectrum.on else None
+    d = grid_spacing(np.asarray(dataset_test.x), np.asarray(dataset_test.y)) if cfg.spectrum.on or cfg.fss.on else None
     on_device = cfg.eval.on and torch.device(dev).type == "cuda"
     with contextlib.ExitStack() as stack:  # (an exception in any batch closes every file)
         sets = []

@@ -801,6 +801,34 @@ int wsr_ssim_pair_sums_bwd(const float* hr, int32_t hr_c, const float* sr, int32
                            float* dsr, void* stream);
 int wsr_ssim_pair_sums_bwd_tile(int32_t X, int32_t Y, int32_t NZ, int32_t win, int32_t* tile);
 
+/* ---- fractions skill score ([FSS]; csrc/fss.hip) ---------------------------------------------------------------
+ * wsr_level_fss: out (B, NZ, nt, nn, 5) doubles, written completely: per sample, z level, threshold t and
+ * neighbourhood n = scales[k] five exact integers.  Sources 0 hr, 1 sr, 2 tl: fp32 planar (B, c, X, Y, NZ), channels
+ * 0 = u and 1 = v read.  In fp32, every product and sum rounded, nothing contracted, no sqrt:
+ *    hs2 = u u + v v;   event I_t = hs2 >= thr2[t]   (thr2 ascending; a NaN is no event, a tie and +Inf are events)
+ *    c_f,t,n(x, y) = the number of events of source f in the n x n box centred on (x, y) of the level's plane, cells
+ *                    outside the plane counting 0 (zero padding): an integer 0 .. n^2
+ *    summed over ALL X * Y positions:  [0] hr2 = sum c_hr^2   [1] sr2 = sum c_sr^2   [2] srd = sum (c_sr - c_hr)^2
+ *                                      [3] tl2 = sum c_tl^2   [4] tld = sum (c_tl - c_hr)^2
+ * thr2 (nt floats): device, fp32.  scales (nn int32): HOST, read during the call: odd, strictly ascending, the first
+ * one 1, the last one <= WSR_FSS_MAX_SCALE; a neighbourhood wider than the plane is allowed.  z is never windowed.  tl
+ * may be NULL: entries 3 and 4 are written as zeros.  The counts come from a table of running sums in LDS over a
+ * 32 x 32 tile with a halo of the largest radius; squares are added as 32-bit integers per workgroup and as 64-bit
+ * integers in the workspace, no floating-point atomics: the same bits on every call.
+ * workspace: wsr_level_fss_workspace_floats(B, X, Y, NZ, nt, nn, max_n) 4-byte words, max_n = scales[nn - 1] (0 for
+ * arguments the entry refuses), 8-byte aligned: the integer table.  A null pointer (but tl), a misaligned workspace, a
+ * channel count < 3, nt outside 1 .. 8, nn outside 1 .. 8, a scale that is even, not ascending, not 1 at the front or
+ * > 33, a non-positive size: WSR_EINVAL; B > 65535, X * Y >= 2^31 or X * Y * NZ >= 2^31: WSR_EUNSUPPORTED; nothing is
+ * written in either case. */
+#define WSR_FSS_MAX_THRESHOLDS 8
+#define WSR_FSS_MAX_SCALES 8
+#define WSR_FSS_MAX_SCALE 33
+int64_t wsr_level_fss_workspace_floats(int32_t B, int32_t X, int32_t Y, int32_t NZ, int32_t nt, int32_t nn,
+                                       int32_t max_n);
+int wsr_level_fss(const float* hr, int32_t hr_c, const float* sr, int32_t sr_c, const float* tl, int32_t tl_c,
+                  const float* thr2, int32_t nt, const int32_t* scales, int32_t nn, int32_t B, int32_t X, int32_t Y,
+                  int32_t NZ, double* out, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
