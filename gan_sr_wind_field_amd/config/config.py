@@ -39,7 +39,7 @@ Extension (optional keys, defaults keep reference behaviour):
             kinetic-energy spectra of SR and HR (spectral_loss.py, csrc/spectral_loss.hip), logged as ``spectral``
   [DEGRADATION] kernel / sigma / channels
             the LR inputs of training, validation and --test are a box- or gaussian-filtered, then sampled copy of the
-            full-resolution channels instead of every scale-th column (degradation.py, csrc/data_degrade.hip)
+            full-resolution channels instead of every scale-th column (degradation.py, csrc/data_gather.hip)
   [SSIM_LOSS] weight / window_size / sigma / data_range
             absent = off; present, the generator loss carries weight * (1 - mean SSIM) of SR against HR on horizontal
             planes (ssim_loss.py, csrc/ssim_loss.hip), logged as ``ssim``
@@ -614,7 +614,7 @@ class SsimLossConfig(OptionalSection):
 
 
 class DegradationConfig(OptionalSection):
-    """[DEGRADATION] (extension): anti-aliased LR inputs (degradation.py, csrc/data_degrade.hip); absent section = off -
+    """[DEGRADATION] (extension): anti-aliased LR inputs (degradation.py, csrc/data_gather.hip); absent section = off -
     LR is every ``scale``-th HR column, as in the reference - and never printed by ``asINI``.  ``kernel`` (required):
     ``box`` (a width-``scale`` mean centred on the sample point) or ``gaussian``; ``sigma`` (gaussian only, required
     there: no reference default to inherit): in HR grid cells, 0 < sigma <= 10; ``channels``: ``all`` LR channels, or

@@ -1,25 +1,32 @@
-// The kernels of csrc/ssim.hip ([SSIM]), kept in a header of their own so that a host program can run them block by
-// block on threads under the address and undefined-behaviour sanitisers (tools/ssim_host_check.cpp: a shim for
-// __global__, __shared__, threadIdx / blockIdx and __syncthreads).  Nothing here needs more of HIP than those.  No
-// thread leaves a kernel that has a barrier before the last barrier.
+// The forward SSIM kernels ([SSIM], [SSIM_LOSS]), kept in a header of their own so that a host program can run them block
+// by block on threads under the address and undefined-behaviour sanitisers (tools/ssim_host_check.cpp and
+// tools/ssim_loss_host_check.cpp, on the shim of tools/host_shim.h: __global__, __shared__, threadIdx / blockIdx and
+// __syncthreads).  Nothing here needs more of HIP than those.  No thread leaves a kernel that has a barrier before the
+// last barrier.
+//
+// Both kernels are templates on the field count NF.  NF = 3 (csrc/ssim.hip) takes HR, SR and TL: eight window sums and
+// four results per position, ssim_sr, cs_sr, ssim_tl, cs_tl.  NF = 2 (csrc/ssim_loss.hip) takes HR and SR: five window
+// sums and the first two results; the TL field, its three moments and its two results are compiled out.  Both run on the
+// tile geometry of ss_geom, which is sized for three fields, so a workgroup of either covers the same positions and the
+// two results of NF = 2 carry the bits of the first two of NF = 3.
 //
 // ssim_tile_kernel: one workgroup of 512 threads per (tile, component, sample).  A tile is TX x TY valid positions and
 // ZC consecutive levels; with the win - 1 halo it reads IX x IY = (TX + win - 1) x (TY + win - 1) columns.
 //
-//   stage    the tiles of HR, SR and TL into LDS, in[f][ix][iy][z]; the loop runs over (ix, iy, z) with z fastest, so a
+//   stage    the tiles of the fields into LDS, in[f][ix][iy][z]; the loop runs over (ix, iy, z) with z fastest, so a
 //            wave reads runs of the chunk's levels - and, when the chunk is all of NZ, the whole (y, z) run of a row of
 //            the tile, which is contiguous in memory
-//   x pass   for every (ox, iy, z) of the tile the eight sums over k of g[k] q(ox + k, iy, z),
-//            q = a, s, t, a a, s s, t t, a s, a t (HR's two shared by the SR and the TL pair), into LDS, mid[q][ox][iy][z]
-//   y pass   thread (slot, z) walks the positions slot, slot + nslots, ... of the tile: the eight sums over k of
-//            g[k] mid[q][ox][oy + k][z] in registers, then l, cs and l cs of both pairs, added to its four fp32 sums
-//   reduce   the slots of a level are added through LDS in slot order: ONE partial row of ZC x 4 floats per workgroup
+//   x pass   for every (ox, iy, z) of the tile the sums over k of g[k] q(ox + k, iy, z), q = the fields, their squares
+//            and HR times each other field (HR's two shared by the SR and the TL pair), into LDS, mid[q][ox][iy][z]
+//   y pass   thread (slot, z) walks the positions slot, slot + nslots, ... of the tile: the sums over k of
+//            g[k] mid[q][ox][oy + k][z] in registers, then l, cs and l cs of every pair, added to its fp32 sums
+//   reduce   the slots of a level are added through LDS in slot order: ONE partial row of ZC x NS floats per workgroup
 //
 // ssim_final_kernel adds the partial rows of a (sample, component, z chunk) in a fixed order in double.  No atomics, no
 // zero fill, the grid a function of the shape alone: two calls give the same bits.  Everything is evaluated without
-// contraction, products before sums, taps ascending; the SR pair goes through the operation sequence of the HR moments
-// (mu_s like mu_a, S_ss and S_as like S_aa), so with SR bit-equal to HR numerator and denominator of l and of cs hold
-// the same bits, both quotients are 1.0f and every ssim_sr and cs_sr sum is exactly npos.
+// contraction, products before sums, taps ascending; every pair goes through ss_l_cs with HR first (mu_s like mu_a, S_ss
+// and S_as like S_aa), so with SR bit-equal to HR numerator and denominator of l and of cs hold the same bits, both
+// quotients are 1.0f and every ssim_sr and cs_sr sum is exactly npos.
 #pragma once
 
 #pragma clang fp contract(off)
@@ -27,10 +34,11 @@
 namespace {
 
 constexpr int SS_BLOCK = 512;
-constexpr int SS_NS = WSR_SSIM_SUMS;          // ssim_sr, cs_sr, ssim_tl, cs_tl
+template <int NF> constexpr int ss_ns = NF == 3 ? 4 : 2;  // results per position: ssim_sr, cs_sr(, ssim_tl, cs_tl)
+template <int NF> constexpr int ss_nq = NF == 3 ? 8 : 5;  // windowed quantities per position
+static_assert(ss_ns<3> == WSR_SSIM_SUMS, "the four sums of wsr_level_ssim");
 constexpr int SS_MAX_WIN = WSR_SSIM_MAX_WIN;
 constexpr int SS_MAX_NZ = 256;
-constexpr int SS_NQ = 8;                      // windowed quantities per position
 constexpr int SS_LDS_FLOATS = 18400;          // in + mid; with 8 KiB of sums and the taps 81,856 B: two workgroups per CU
 constexpr int SS_MAX_T = 32;                  // positions per tile and axis, at most
 constexpr int SS_FBLOCK = 256, SS_FWAVES = SS_FBLOCK / 64;
@@ -45,10 +53,10 @@ struct SsGeom {
   int nslots;         // SS_BLOCK / ZC
 };
 
-// floats of LDS of a tile shape
+// floats of LDS of a tile shape, with three fields
 inline long ss_lds_floats(int TX, int TY, int ZC, int win) {
   const long IX = TX + win - 1, IY = TY + win - 1;
-  return 3 * IX * IY * ZC + (long)SS_NQ * TX * IY * ZC;
+  return 3 * IX * IY * ZC + (long)ss_nq<3> * TX * IY * ZC;
 }
 
 // 0: fine; WSR_EINVAL / WSR_EUNSUPPORTED as wsr_level_ssim documents them.  The tile: a chunk of min(NZ, 16) levels or
@@ -88,16 +96,35 @@ inline int ss_geom(SsGeom& g, int B, int X, int Y, int NZ, int win) {
   return 0;
 }
 
-// floats of the partial rows: part[((b * 3 + c) * nzc + zchunk) * ntxy + tile][z][4]
-inline long ss_workspace_floats(const SsGeom& g) { return (long)g.B * 3 * g.nzc * g.ntxy * g.ZC * SS_NS; }
+// floats of the partial rows: part[((b * 3 + c) * nzc + zchunk) * ntxy + tile][z][NS]
+template <int NF> inline long ss_workspace_floats(const SsGeom& g) {
+  return (long)g.B * 3 * g.nzc * g.ntxy * g.ZC * ss_ns<NF>;
+}
 
+// l, cs and their denominators d1, d2 of the pair (a, s) from the five window sums of a position: the means ma, ms and
+// the second moments aa, ss, as.  The one operation sequence of the forward of both field counts and of the backward.
+__device__ __forceinline__ void ss_l_cs(float ma, float ms, float aa, float ss, float as, float c1, float c2, float& l,
+                                        float& cs, float& d1, float& d2) {
+  const float maa = ma * ma, mss = ms * ms, mas = ma * ms;
+  const float va = aa - maa, vs = ss - mss, cv = as - mas;
+  d1 = (maa + mss) + c1;
+  d2 = (va + vs) + c2;
+  l = (2.f * mas + c1) / d1;
+  cs = (2.f * cv + c2) / d2;
+}
+
+// tl, tl_c: read with NF = 3 only
+template <int NF>
 __global__ __launch_bounds__(SS_BLOCK) void ssim_tile_kernel(const float* __restrict__ hr, int hr_c,
                                                              const float* __restrict__ sr, int sr_c,
                                                              const float* __restrict__ tl, int tl_c,
                                                              const float* __restrict__ taps,
                                                              float c1, float c2, SsGeom g, float* __restrict__ part) {
+  constexpr int NS = ss_ns<NF>, NQ = ss_nq<NF>;
+  // mid[q]: the means of the fields, their second moments, then HR times SR (and HR times TL)
+  constexpr int Q_MA = 0, Q_MS = 1, Q_MT = 2, Q_AA = NF, Q_SS = NF + 1, Q_TT = NF + 2, Q_AS = 2 * NF, Q_AT = 2 * NF + 1;
   __shared__ float lds[SS_LDS_FLOATS];
-  __shared__ float sums[SS_NS][SS_BLOCK];
+  __shared__ float sums[NS][SS_BLOCK];
   __shared__ float gt[SS_MAX_WIN + 1];
   const int t = threadIdx.x, c = blockIdx.y, b = blockIdx.z;
   const int tile = (int)(blockIdx.x / (unsigned)g.nzc), zchunk = (int)(blockIdx.x - (unsigned)tile * g.nzc);
@@ -110,14 +137,13 @@ __global__ __launch_bounds__(SS_BLOCK) void ssim_tile_kernel(const float* __rest
   const int nxi = nxo + win - 1, nyi = nyo + win - 1;   // columns it reads: x0 + nxi <= X, y0 + nyi <= Y
   const int vol = g.X * g.Y * g.NZ;                     // (< 2^31: checked on the host)
   const int fin = g.IX * IY * ZC;                       // floats of one staged field
-  float* mid = lds + 3 * fin;
+  float* mid = lds + NF * fin;
   const int fmid = g.TX * IY * ZC;
 
   if (t < win) gt[t] = taps[t];
   {  // ---- stage
     const float* ph = hr + ((long)b * hr_c + c) * vol;
     const float* ps = sr + ((long)b * sr_c + c) * vol;
-    const float* pt = tl + ((long)b * tl_c + c) * vol;
     const int run = nyi * nz, n = nxi * run;
     for (int e = t; e < n; e += SS_BLOCK) {
       const int ix = e / run, r = e - ix * run;
@@ -126,7 +152,7 @@ __global__ __launch_bounds__(SS_BLOCK) void ssim_tile_kernel(const float* __rest
       const int dst = (ix * IY + iy) * ZC + z;
       lds[dst] = ph[src];
       lds[fin + dst] = ps[src];
-      lds[2 * fin + dst] = pt[src];
+      if constexpr (NF == 3) lds[2 * fin + dst] = (tl + ((long)b * tl_c + c) * vol)[src];
     }
   }
   __syncthreads();
@@ -136,66 +162,65 @@ __global__ __launch_bounds__(SS_BLOCK) void ssim_tile_kernel(const float* __rest
       const int ox = e / run, r = e - ox * run;
       const int iy = r / nz, z = r - iy * nz;
       const int o = (ox * IY + iy) * ZC + z;
-      float ma = 0.f, ms = 0.f, mt = 0.f, aa = 0.f, ss = 0.f, tt = 0.f, as = 0.f, at = 0.f;
+      float m[NQ];
+#pragma unroll
+      for (int j = 0; j < NQ; ++j) m[j] = 0.f;
       for (int k = 0; k < win; ++k) {
         const int i = o + k * IY * ZC;
-        const float w = gt[k], a = lds[i], s = lds[fin + i], u = lds[2 * fin + i];
-        ma += w * a;
-        ms += w * s;
-        mt += w * u;
-        aa += w * (a * a);
-        ss += w * (s * s);
-        tt += w * (u * u);
-        as += w * (a * s);
-        at += w * (a * u);
+        const float w = gt[k], a = lds[i], s = lds[fin + i];
+        m[Q_MA] += w * a;
+        m[Q_MS] += w * s;
+        m[Q_AA] += w * (a * a);
+        m[Q_SS] += w * (s * s);
+        m[Q_AS] += w * (a * s);
+        if constexpr (NF == 3) {
+          const float u = lds[2 * fin + i];
+          m[Q_MT] += w * u;
+          m[Q_TT] += w * (u * u);
+          m[Q_AT] += w * (a * u);
+        }
       }
-      mid[o] = ma;
-      mid[fmid + o] = ms;
-      mid[2 * fmid + o] = mt;
-      mid[3 * fmid + o] = aa;
-      mid[4 * fmid + o] = ss;
-      mid[5 * fmid + o] = tt;
-      mid[6 * fmid + o] = as;
-      mid[7 * fmid + o] = at;
+#pragma unroll
+      for (int j = 0; j < NQ; ++j) mid[j * fmid + o] = m[j];
     }
   }
   __syncthreads();
-  float acc[SS_NS] = {0.f, 0.f, 0.f, 0.f};
+  float acc[NS];
+#pragma unroll
+  for (int j = 0; j < NS; ++j) acc[j] = 0.f;
   const int slot = t / ZC, z = t - slot * ZC;
   if (slot < g.nslots && z < nz) {  // ---- y pass
     const int npos = nxo * nyo;
     for (int p = slot; p < npos; p += g.nslots) {
       const int ox = p / nyo, oy = p - ox * nyo;
       const int o = (ox * IY + oy) * ZC + z;
-      float q[SS_NQ];
+      float q[NQ];
 #pragma unroll
-      for (int j = 0; j < SS_NQ; ++j) q[j] = 0.f;
+      for (int j = 0; j < NQ; ++j) q[j] = 0.f;
       for (int k = 0; k < win; ++k) {
         const float w = gt[k];
         const int i = o + k * ZC;
 #pragma unroll
-        for (int j = 0; j < SS_NQ; ++j) q[j] += w * mid[j * fmid + i];
+        for (int j = 0; j < NQ; ++j) q[j] += w * mid[j * fmid + i];
       }
-      const float ma = q[0], ms = q[1], mt = q[2];
-      const float maa = ma * ma, mss = ms * ms, mtt = mt * mt, mas = ma * ms, mat = ma * mt;
-      const float va = q[3] - maa, vs = q[4] - mss, vt = q[5] - mtt, cs_ = q[6] - mas, ct_ = q[7] - mat;
-      const float ls = (2.f * mas + c1) / ((maa + mss) + c1);
-      const float cs = (2.f * cs_ + c2) / ((va + vs) + c2);
-      const float lt = (2.f * mat + c1) / ((maa + mtt) + c1);
-      const float ct = (2.f * ct_ + c2) / ((va + vt) + c2);
-      acc[0] += ls * cs;
+      float l, cs, d1, d2;
+      ss_l_cs(q[Q_MA], q[Q_MS], q[Q_AA], q[Q_SS], q[Q_AS], c1, c2, l, cs, d1, d2);
+      acc[0] += l * cs;
       acc[1] += cs;
-      acc[2] += lt * ct;
-      acc[3] += ct;
+      if constexpr (NF == 3) {
+        ss_l_cs(q[Q_MA], q[Q_MT], q[Q_AA], q[Q_TT], q[Q_AT], c1, c2, l, cs, d1, d2);
+        acc[2] += l * cs;
+        acc[3] += cs;
+      }
     }
   }
 #pragma unroll
-  for (int j = 0; j < SS_NS; ++j) sums[j][t] = acc[j];
+  for (int j = 0; j < NS; ++j) sums[j][t] = acc[j];
   __syncthreads();
   // ---- reduce: item (level, sum) over the slots in order
-  float* row = part + ((((long)b * 3 + c) * g.nzc + zchunk) * g.ntxy + tile) * (ZC * SS_NS);
-  for (int item = t; item < nz * SS_NS; item += SS_BLOCK) {
-    const int lvl = item / SS_NS, j = item - lvl * SS_NS;
+  float* row = part + ((((long)b * 3 + c) * g.nzc + zchunk) * g.ntxy + tile) * (ZC * NS);
+  for (int item = t; item < nz * NS; item += SS_BLOCK) {
+    const int lvl = item / NS, j = item - lvl * NS;
     float s = sums[j][lvl];
     for (int sl = 1; sl < g.nslots; ++sl) s += sums[j][sl * ZC + lvl];
     row[item] = s;
@@ -204,17 +229,19 @@ __global__ __launch_bounds__(SS_BLOCK) void ssim_tile_kernel(const float* __rest
 
 // out[b][z][c][j] = the ntxy partial rows of (b, c, z chunk) in double: 64 (level, sum) items per workgroup of 4 waves,
 // wave w adds rows w, w + 4, ... in order, the four wave sums are then added in order
+template <int NF>
 __global__ __launch_bounds__(SS_FBLOCK) void ssim_final_kernel(const float* __restrict__ part, SsGeom g,
                                                                double* __restrict__ out) {
+  constexpr int NS = ss_ns<NF>;
   __shared__ double sh[SS_FWAVES][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int c = blockIdx.y % 3, zchunk = blockIdx.y / 3, b = blockIdx.z;
   const int item = blockIdx.x * 64 + lane;
   const int z0 = zchunk * g.ZC;
   const int nz = g.NZ - z0 < g.ZC ? g.NZ - z0 : g.ZC;
-  const int stride = g.ZC * SS_NS;
+  const int stride = g.ZC * NS;
   const float* rows = part + (((long)b * 3 + c) * g.nzc + zchunk) * g.ntxy * stride;
-  const bool live = item < nz * SS_NS;
+  const bool live = item < nz * NS;
   double s = 0.0;
   if (live)
     for (int r = wave; r < g.ntxy; r += SS_FWAVES) s += (double)rows[(long)r * stride + item];
@@ -224,8 +251,8 @@ __global__ __launch_bounds__(SS_FBLOCK) void ssim_final_kernel(const float* __re
     double a = sh[0][lane];
 #pragma unroll
     for (int w = 1; w < SS_FWAVES; ++w) a += sh[w][lane];
-    const int lvl = item / SS_NS, j = item - lvl * SS_NS;
-    out[(((long)b * g.NZ + z0 + lvl) * 3 + c) * SS_NS + j] = a;
+    const int lvl = item / NS, j = item - lvl * NS;
+    out[(((long)b * g.NZ + z0 + lvl) * 3 + c) * NS + j] = a;
   }
 }
 

@@ -1,17 +1,17 @@
 // The SSIM loss of generator training ([SSIM_LOSS]; ssim_loss.py holds the definition): per sample, z level and wind
 // component the sums over the valid window positions of l cs and of cs for the pair (HR, SR), P (B, NZ, 3, 2) in double
 // (wsr_ssim_pair_sums), and the vector-Jacobian product of both columns towards SR (wsr_ssim_pair_sums_bwd).  All tensors
-// fp32 planar (B, C, X, Y, NZ), z innermost; only channels 0..2 are read.  csrc/ssim.hip is not touched: the forward is
-// its tile kernel without the TL field, on the same tile geometry, so both columns carry the bits of wsr_level_ssim's
-// ssim_sr and cs_sr.  The backward is one launch that recomputes the moments around a tile of output pixels; nothing is
-// saved by the forward.  The kernels, and what each pass does, are in ssim_loss_kernels.h.
+// fp32 planar (B, C, X, Y, NZ), z innermost; only channels 0..2 are read.  The forward is the tile and final kernels of
+// csrc/ssim.hip instantiated for two fields (ssim_kernels.h), on the same tile geometry, so both columns carry the bits
+// of wsr_level_ssim's ssim_sr and cs_sr.  The backward is one launch that recomputes the moments around a tile of output
+// pixels; nothing is saved by the forward.  Its kernel, and what each pass does, is in ssim_loss_kernels.h.
 #include "common.h"
 #include "ssim_loss_kernels.h"
 
 extern "C" int64_t wsr_ssim_pair_sums_workspace_floats(int32_t B, int32_t X, int32_t Y, int32_t NZ, int32_t win) {
   SsGeom g{};
   if (ss_geom(g, B, X, Y, NZ, win) != 0) return 0;
-  return ssl_workspace_floats(g);
+  return ss_workspace_floats<2>(g);
 }
 
 extern "C" int wsr_ssim_pair_sums(const float* hr, int32_t hr_c, const float* sr, int32_t sr_c, const float* taps,
@@ -22,10 +22,10 @@ extern "C" int wsr_ssim_pair_sums(const float* hr, int32_t hr_c, const float* sr
   SsGeom g{};
   if (const int rc = ss_geom(g, B, X, Y, NZ, win)) return rc;
   const hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(ssl_tile_kernel, dim3((unsigned)(g.ntxy * g.nzc), 3u, (unsigned)B), dim3(SS_BLOCK), 0, st, hr, hr_c,
-                     sr, sr_c, taps, c1, c2, g, workspace);
+  hipLaunchKernelGGL(ssim_tile_kernel<2>, dim3((unsigned)(g.ntxy * g.nzc), 3u, (unsigned)B), dim3(SS_BLOCK), 0, st, hr,
+                     hr_c, sr, sr_c, (const float*)nullptr, 0, taps, c1, c2, g, workspace);
   WSR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(ssl_final_kernel, dim3((unsigned)((g.ZC * SSL_NS + 63) / 64), (unsigned)(3 * g.nzc), (unsigned)B),
+  hipLaunchKernelGGL(ssim_final_kernel<2>, dim3((unsigned)((g.ZC * ss_ns<2> + 63) / 64), (unsigned)(3 * g.nzc), (unsigned)B),
                      dim3(SS_FBLOCK), 0, st, workspace, g, out);
   WSR_LAUNCH_CHECK();
   return 0;

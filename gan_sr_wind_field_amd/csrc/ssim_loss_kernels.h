@@ -1,14 +1,10 @@
-// The kernels of csrc/ssim_loss.hip ([SSIM_LOSS]), in a header of their own so that a host program can run them block by
-// block on threads under the address and undefined-behaviour sanitisers (tools/ssim_loss_host_check.cpp), as
+// The backward kernel of csrc/ssim_loss.hip ([SSIM_LOSS]), in a header of its own so that a host program can run it
+// block by block on threads under the address and undefined-behaviour sanitisers (tools/ssim_loss_host_check.cpp), as
 // ssim_kernels.h is.  No thread leaves a kernel that has a barrier before the last barrier.
 //
-// Forward.  ssl_tile_kernel is ssim_tile_kernel (ssim_kernels.h) with the TL field and its three moments dropped: the
-// tile geometry (ss_geom), the stage, the x pass into LDS, the y pass in registers, the slot-ordered reduce and the
-// operation sequence of every moment, of l and of cs are those of that kernel, so the two sums of a workgroup - the
-// sum of l cs and the sum of cs - carry the bits of its ssim_sr and cs_sr.  ssl_final_kernel adds the partial rows in
-// the order of ssim_final_kernel, in double.
+// The forward is ssim_tile_kernel<2> and ssim_final_kernel<2> of ssim_kernels.h.
 //
-// Backward.  ssl_bwd_kernel: one workgroup of 512 threads per (pixel tile, z chunk, component, sample); it recomputes,
+// ssl_bwd_kernel: one workgroup of 512 threads per (pixel tile, z chunk, component, sample); it recomputes,
 // nothing is saved by the forward.  A tile is TX x TY OUTPUT PIXELS and ZC levels.  A pixel lies in the windows of the
 // win x win positions up and left of it, and a position reads the win x win pixels down and right of it, so the tile
 // needs MX x MY = (TX + win - 1) x (TY + win - 1) positions and JX x JY = (TX + 2 (win - 1)) x (TY + 2 (win - 1)) pixels,
@@ -17,8 +13,8 @@
 //   stage     HR and SR of the clipped pixel range, in[f][jx][jy][z]
 //   x pass    for every (position column mx, pixel row jy, z) the five sums over k of g[k] q(mx + k, jy, z),
 //             q = a, s, a a, s s, a s, into mid[q][mx][jy][z]
-//   y pass    for every (mx, my, z) the five sums over k of g[k] mid[q][mx][my + k][z]: the moments of the forward, by
-//             its operation sequence; then l, cs, h = G0 l + G1 and
+//   y pass    for every (mx, my, z) the five sums over k of g[k] mid[q][mx][my + k][z]: the moments of the forward, then
+//             l, cs and their denominators by the forward's ss_l_cs; h = G0 l + G1 and
 //                 alpha = G0 cs (2 mu_a - 2 mu_s l) / D1 + h (2 mu_s cs - 2 mu_a) / D2
 //                 beta  = -h cs / D2,     gamma = 2 h / D2
 //             into co[3][mx][my][z]; a position outside the plane's valid range holds three zeros
@@ -36,140 +32,9 @@
 
 namespace {
 
-constexpr int SSL_NS = 2;   // the sum of l cs, the sum of cs
-constexpr int SSL_NQ = 5;   // windowed quantities per position
 constexpr int SSL_BW_LDS_FLOATS = 20000;  // in + mid + co; with the taps 80,064 B: two workgroups per CU
 constexpr int SSL_MAX_T = 32;
 
-// ---------------------------------------------------------------------------------------------------- forward
-// floats of the partial rows: part[((b * 3 + c) * nzc + zchunk) * ntxy + tile][z][2]
-inline long ssl_workspace_floats(const SsGeom& g) { return (long)g.B * 3 * g.nzc * g.ntxy * g.ZC * SSL_NS; }
-
-__global__ __launch_bounds__(SS_BLOCK) void ssl_tile_kernel(const float* __restrict__ hr, int hr_c,
-                                                            const float* __restrict__ sr, int sr_c,
-                                                            const float* __restrict__ taps, float c1, float c2, SsGeom g,
-                                                            float* __restrict__ part) {
-  __shared__ float lds[SS_LDS_FLOATS];
-  __shared__ float sums[SSL_NS][SS_BLOCK];
-  __shared__ float gt[SS_MAX_WIN + 1];
-  const int t = threadIdx.x, c = blockIdx.y, b = blockIdx.z;
-  const int tile = (int)(blockIdx.x / (unsigned)g.nzc), zchunk = (int)(blockIdx.x - (unsigned)tile * g.nzc);
-  const int tx = tile / g.nty, ty = tile - tx * g.nty;
-  const int win = g.win, ZC = g.ZC, IY = g.IY;
-  const int x0 = tx * g.TX, y0 = ty * g.TY, z0 = zchunk * ZC;
-  const int nxo = g.PX - x0 < g.TX ? g.PX - x0 : g.TX;
-  const int nyo = g.PY - y0 < g.TY ? g.PY - y0 : g.TY;
-  const int nz = g.NZ - z0 < ZC ? g.NZ - z0 : ZC;
-  const int nxi = nxo + win - 1, nyi = nyo + win - 1;
-  const int vol = g.X * g.Y * g.NZ;
-  const int fin = g.IX * IY * ZC;
-  float* mid = lds + 2 * fin;
-  const int fmid = g.TX * IY * ZC;
-
-  if (t < win) gt[t] = taps[t];
-  {  // ---- stage
-    const float* ph = hr + ((long)b * hr_c + c) * vol;
-    const float* ps = sr + ((long)b * sr_c + c) * vol;
-    const int run = nyi * nz, n = nxi * run;
-    for (int e = t; e < n; e += SS_BLOCK) {
-      const int ix = e / run, r = e - ix * run;
-      const int iy = r / nz, z = r - iy * nz;
-      const int src = ((x0 + ix) * g.Y + (y0 + iy)) * g.NZ + z0 + z;
-      const int dst = (ix * IY + iy) * ZC + z;
-      lds[dst] = ph[src];
-      lds[fin + dst] = ps[src];
-    }
-  }
-  __syncthreads();
-  {  // ---- x pass
-    const int run = nyi * nz, n = nxo * run;
-    for (int e = t; e < n; e += SS_BLOCK) {
-      const int ox = e / run, r = e - ox * run;
-      const int iy = r / nz, z = r - iy * nz;
-      const int o = (ox * IY + iy) * ZC + z;
-      float ma = 0.f, ms = 0.f, aa = 0.f, ss = 0.f, as = 0.f;
-      for (int k = 0; k < win; ++k) {
-        const int i = o + k * IY * ZC;
-        const float w = gt[k], a = lds[i], s = lds[fin + i];
-        ma += w * a;
-        ms += w * s;
-        aa += w * (a * a);
-        ss += w * (s * s);
-        as += w * (a * s);
-      }
-      mid[o] = ma;
-      mid[fmid + o] = ms;
-      mid[2 * fmid + o] = aa;
-      mid[3 * fmid + o] = ss;
-      mid[4 * fmid + o] = as;
-    }
-  }
-  __syncthreads();
-  float acc[SSL_NS] = {0.f, 0.f};
-  const int slot = t / ZC, z = t - slot * ZC;
-  if (slot < g.nslots && z < nz) {  // ---- y pass
-    const int npos = nxo * nyo;
-    for (int p = slot; p < npos; p += g.nslots) {
-      const int ox = p / nyo, oy = p - ox * nyo;
-      const int o = (ox * IY + oy) * ZC + z;
-      float q[SSL_NQ];
-#pragma unroll
-      for (int j = 0; j < SSL_NQ; ++j) q[j] = 0.f;
-      for (int k = 0; k < win; ++k) {
-        const float w = gt[k];
-        const int i = o + k * ZC;
-#pragma unroll
-        for (int j = 0; j < SSL_NQ; ++j) q[j] += w * mid[j * fmid + i];
-      }
-      const float ma = q[0], ms = q[1];
-      const float maa = ma * ma, mss = ms * ms, mas = ma * ms;
-      const float va = q[2] - maa, vs = q[3] - mss, cs_ = q[4] - mas;
-      const float ls = (2.f * mas + c1) / ((maa + mss) + c1);
-      const float cs = (2.f * cs_ + c2) / ((va + vs) + c2);
-      acc[0] += ls * cs;
-      acc[1] += cs;
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < SSL_NS; ++j) sums[j][t] = acc[j];
-  __syncthreads();
-  // ---- reduce: item (level, sum) over the slots in order
-  float* row = part + ((((long)b * 3 + c) * g.nzc + zchunk) * g.ntxy + tile) * (ZC * SSL_NS);
-  for (int item = t; item < nz * SSL_NS; item += SS_BLOCK) {
-    const int lvl = item / SSL_NS, j = item - lvl * SSL_NS;
-    float s = sums[j][lvl];
-    for (int sl = 1; sl < g.nslots; ++sl) s += sums[j][sl * ZC + lvl];
-    row[item] = s;
-  }
-}
-
-// out[b][z][c][j] = the ntxy partial rows of (b, c, z chunk) in double, in the order of ssim_final_kernel
-__global__ __launch_bounds__(SS_FBLOCK) void ssl_final_kernel(const float* __restrict__ part, SsGeom g,
-                                                              double* __restrict__ out) {
-  __shared__ double sh[SS_FWAVES][64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int c = blockIdx.y % 3, zchunk = blockIdx.y / 3, b = blockIdx.z;
-  const int item = blockIdx.x * 64 + lane;
-  const int z0 = zchunk * g.ZC;
-  const int nz = g.NZ - z0 < g.ZC ? g.NZ - z0 : g.ZC;
-  const int stride = g.ZC * SSL_NS;
-  const float* rows = part + (((long)b * 3 + c) * g.nzc + zchunk) * g.ntxy * stride;
-  const bool live = item < nz * SSL_NS;
-  double s = 0.0;
-  if (live)
-    for (int r = wave; r < g.ntxy; r += SS_FWAVES) s += (double)rows[(long)r * stride + item];
-  sh[wave][lane] = s;
-  __syncthreads();
-  if (wave == 0 && live) {
-    double a = sh[0][lane];
-#pragma unroll
-    for (int w = 1; w < SS_FWAVES; ++w) a += sh[w][lane];
-    const int lvl = item / SSL_NS, j = item - lvl * SSL_NS;
-    out[(((long)b * g.NZ + z0 + lvl) * 3 + c) * SSL_NS + j] = a;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------------- backward
 struct SslBwdGeom {
   int B, X, Y, NZ, win;
   int PX, PY;         // valid positions per axis
@@ -183,7 +48,7 @@ struct SslBwdGeom {
 // floats of LDS of a backward tile shape: in (2 fields), mid (5 x-pass sums; later the 3 xT-pass sums), co (3 maps)
 inline long ssl_bwd_lds_floats(int TX, int TY, int ZC, int win) {
   const long MX = TX + win - 1, MY = TY + win - 1, JX = MX + win - 1, JY = MY + win - 1;
-  return (2 * JX * JY + (long)SSL_NQ * MX * JY + 3 * MX * MY) * ZC;
+  return (2 * JX * JY + (long)ss_nq<2> * MX * JY + 3 * MX * MY) * ZC;
 }
 
 // 0: fine; the refusals of ss_geom.  The tile: of the chunks min(NZ, 16), 8, 4, 2, 1 and the (TX, TY) up to 32 x 32 (and
@@ -254,7 +119,7 @@ __global__ __launch_bounds__(SS_BLOCK) void ssl_bwd_kernel(const float* __restri
   const int fco = g.MX * MY * ZC;    // ... of one coefficient map
   const int fadj = g.TX * MY * ZC;   // ... of one xT-pass sum (3 fadj <= 5 fmid)
   float* mid = lds + 2 * fin;
-  float* co = mid + SSL_NQ * fmid;
+  float* co = mid + ss_nq<2> * fmid;
   float* adj = mid;
 
   if (t < win) gt[t] = taps[t];
@@ -305,22 +170,19 @@ __global__ __launch_bounds__(SS_BLOCK) void ssl_bwd_kernel(const float* __restri
       float al = 0.f, be = 0.f, ga = 0.f;
       if (mx >= pxlo && mx < qxhi && my >= pylo && my < qyhi) {
         const int o = (mx * JY + my) * ZC + z;
-        float q[SSL_NQ];
+        float q[ss_nq<2>];
 #pragma unroll
-        for (int j = 0; j < SSL_NQ; ++j) q[j] = 0.f;
+        for (int j = 0; j < ss_nq<2>; ++j) q[j] = 0.f;
         for (int k = 0; k < win; ++k) {
           const float w = gt[k];
           const int i = o + k * ZC;
 #pragma unroll
-          for (int j = 0; j < SSL_NQ; ++j) q[j] += w * mid[j * fmid + i];
+          for (int j = 0; j < ss_nq<2>; ++j) q[j] += w * mid[j * fmid + i];
         }
         const float ma = q[0], ms = q[1];
-        const float maa = ma * ma, mss = ms * ms, mas = ma * ms;
-        const float va = q[2] - maa, vs = q[3] - mss, cv = q[4] - mas;
-        const float d1 = (maa + mss) + c1, d2 = (va + vs) + c2;
-        const float l = (2.f * mas + c1) / d1;
-        const float cs = (2.f * cv + c2) / d2;
-        const long gi = ((((long)b * g.NZ + z0 + z) * 3 + c) * SSL_NS);
+        float l, cs, d1, d2;
+        ss_l_cs(ma, ms, q[2], q[3], q[4], c1, c2, l, cs, d1, d2);
+        const long gi = ((((long)b * g.NZ + z0 + z) * 3 + c) * ss_ns<2>);
         const float g0 = (float)gout[gi], g1 = (float)gout[gi + 1];
         const float h = g0 * l + g1;
         al = (g0 * cs) * (2.f * ma - (2.f * ms) * l) / d1 + h * ((2.f * ms) * cs - 2.f * ma) / d2;

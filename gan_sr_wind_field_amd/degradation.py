@@ -1,7 +1,7 @@
 """Anti-aliased LR degradation ([DEGRADATION], opt-in): the low-resolution input is a blurred, then sampled copy of the
 full-resolution channels instead of ``HR[:, ::s, ::s, :]``.  One definition for the CPU datasets
 (``process_data.CustomizedDataset``, :func:`degrade_lr`) and the device-resident gather (``device_data.ResidentStore``,
-csrc/data_degrade.hip); both read the weight tables of :func:`axis_weights`, so their batches agree bit for bit.
+csrc/data_gather.hip); both read the weight tables of :func:`axis_weights`, so their batches agree bit for bit.
 
 Taps ``t[-R..R]``, symmetric and centred ON the sample point ``s * i`` (the LR voxels stay where the trilinear
 baseline, the tiling and the network expect them):
@@ -28,7 +28,7 @@ from typing import Optional
 
 import numpy as np
 
-MAX_RADIUS = 32  # (WSR_DEGRADE_MAX_R of csrc/data_degrade.hip)
+MAX_RADIUS = 32  # (WSR_DEGRADE_MAX_R of csrc/data_gather.hip)
 KERNELS = ("box", "gaussian")
 CHANNELS = ("all", "wind")
 

@@ -550,7 +550,7 @@ int wsr_ragan_loss(const float* u, const float* v, const float* lu, const float*
 int wsr_gather_batch(const float* store, int64_t n_samples, const int32_t* desc, int32_t B, int32_t Cin, int32_t s,
                      int32_t S, int32_t X, int32_t Y, int32_t NZ, float* lr, float* hr, float* z, void* stream);
 
-/* wsr_gather_batch with the anti-aliased LR degradation of [DEGRADATION] (degradation.py; csrc/data_degrade.hip), still
+/* wsr_gather_batch with the anti-aliased LR degradation of [DEGRADATION] (degradation.py; csrc/data_gather.hip), still
  * one launch for lr, hr and z.  hr, z and the lr planes read from store channels >= n_filt are the copies of
  * wsr_gather_batch.  An lr plane read from a store channel < n_filt is, in the slice frame before rotation and mirrors
  * (W x H = S x S, or X x Y when S = 0), with f the store channel inside the slice,

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""The cost of ``[DEGRADATION]`` (degradation.py, csrc/data_degrade.hip) at the C1c data shape, one process, one device.
+"""The cost of ``[DEGRADATION]`` (degradation.py, csrc/data_gather.hip) at the C1c data shape, one process, one device.
 
 Shape: the cluster ini as shipped (batch 32, 128x128x10 samples, ``interpolate_z``, z channel - 4 input channels -,
 ``enable_slicing`` with 64x64 slices, x4, rotation and mirrors on), on five days of synthetic HARMONIE-SIMRA-format data

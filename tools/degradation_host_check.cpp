@@ -1,7 +1,8 @@
-// Runs the kernel of csrc/data_degrade.hip block by block on 256 host threads, for the address and undefined-behaviour
-// sanitisers: a shim for __global__, threadIdx / blockIdx, min and max.  Every buffer is a heap allocation of exactly the
-// size the C ABI documents - the store, the descriptor table, the two weight tables and the three outputs - so a read
-// outside the store or a table and a write outside an output are reported.  The kernel's vector types are clang's.
+// Runs the filtered kernel of csrc/data_gather.hip (wsr_gather_batch_filtered) block by block on 256 host threads, for
+// the address and undefined-behaviour sanitisers, on the shim of tools/host_shim.h with min and max added.  Every buffer
+// is a heap allocation of exactly the size the C ABI documents - the store, the descriptor table, the two weight tables
+// and the three outputs - so a read outside the store or a table and a write outside an output are reported.  The
+// kernel's vector types are clang's.
 //
 //   clang++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -pthread \
 //       tools/degradation_host_check.cpp -o degradation_host_check
@@ -12,58 +13,16 @@
 // zero outside the slice like degradation.axis_weights; the store is random with negative zeros sprinkled in.  With a
 // last argument the operands and results are written as raw arrays - desc (int32), store, wx, wy, lr, hr, z (float32) -
 // for a comparison with degradation.degrade_lr and the rotation / mirror code of CustomizedDataset.__getitem__.
-#include <math.h>
-#include <pthread.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-
 #include <algorithm>
-#include <functional>
-#include <limits>
-#include <vector>
 
-#include "../include/windsr_hip.h"
+#include "host_shim.h"
 
-struct Dim3 {
-  unsigned x = 1, y = 1, z = 1;
-};
-static thread_local Dim3 threadIdx, blockIdx;
 using std::max;
 using std::min;
-#define __global__
-#define __launch_bounds__(n)
 
-#include "../gan_sr_wind_field_amd/csrc/data_degrade_kernels.h"
+#include "../gan_sr_wind_field_amd/csrc/data_gather_kernels.h"
 
 namespace {
-
-constexpr int NT = GD_BLOCK;
-unsigned g_blocks;
-std::function<void()> g_body;
-
-void* worker(void* arg) {
-  threadIdx.x = (unsigned)(intptr_t)arg;
-  for (unsigned bx = 0; bx < g_blocks; ++bx) {
-    blockIdx.x = bx;
-    g_body();
-  }
-  return nullptr;
-}
-
-void launch(unsigned blocks, std::function<void()> body) {
-  g_blocks = blocks;
-  g_body = std::move(body);
-  pthread_t th[NT];
-  for (int t = 0; t < NT; ++t) pthread_create(&th[t], nullptr, worker, (void*)(intptr_t)t);
-  for (int t = 0; t < NT; ++t) pthread_join(th[t], nullptr);
-}
-
-uint64_t g_rng = 0x9e3779b97f4a7c15ull;
-double uniform() {  // (-1, 1)
-  g_rng = g_rng * 6364136223846793005ull + 1442695040888963407ull;
-  return ((double)(g_rng >> 11) / 9007199254740992.0) * 2.0 - 1.0;
-}
 
 std::vector<float> triangle_weights(int n, int s, int R) {
   const int rows = (n + s - 1) / s, T = 2 * R + 1;
@@ -80,10 +39,6 @@ std::vector<float> triangle_weights(int n, int s, int R) {
     }
   }
   return w;
-}
-
-template <class T> void dump(FILE* f, const T* p, size_t n) {
-  if (f && fwrite(p, sizeof(T), n, f) != n) abort();
 }
 
 }  // namespace
@@ -109,8 +64,8 @@ int main(int argc, char** argv) {
         desc.insert(desc.end(), row, row + 6);
       }
   const int B = (int)(desc.size() / 6);
-  DegradeGeom g{};
-  if (gd_geom(g, n_samples, B, Cin, s, S, X, Y, NZ, R, n_filt) != 0) {
+  GatherGeom g{};
+  if (gb_geom(g, n_samples, B, Cin, s, S, X, Y, NZ, R, n_filt) != 0) {
     fprintf(stderr, "refused\n");
     return 2;
   }
@@ -123,9 +78,9 @@ int main(int argc, char** argv) {
 
   const auto run = [&](auto vtag) {
     constexpr int V = decltype(vtag)::value;
-    const long blocks = gd_plan<V>(g);
-    launch((unsigned)blocks, [&] {
-      gather_batch_filtered_kernel<V>(store.data(), desc.data(), wx.data(), wy.data(), g, lr.data(), hr.data(), z.data());
+    const long blocks = gb_plan<V>(g);
+    launch(GB_BLOCK, (unsigned)blocks, 1, 1, [&] {
+      gather_batch_kernel<V, true>(store.data(), desc.data(), wx.data(), wy.data(), g, lr.data(), hr.data(), z.data());
     });
   };
   if (NZ % 4 == 0)

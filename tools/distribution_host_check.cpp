@@ -3,8 +3,9 @@
 //   ./distribution_host_check B X Y NZ speed_bins sectors calm hr_c sr_c tl_c      (tl_c 0: no baseline)
 //
 // Runs the three kernels of csrc/distribution.hip block by block on host threads, for the address and
-// undefined-behaviour sanitisers: a shim for __global__, __shared__ (a static array, one block at a time), threadIdx /
-// blockIdx, __syncthreads (a pthread barrier) and the LDS and global integer adds (__atomic_fetch_add).  Every buffer is a
+// undefined-behaviour sanitisers: the shim of tools/host_shim.h (__global__, __shared__ as a static array, one block at a
+// time, threadIdx / blockIdx, __syncthreads as a pthread barrier) with the LDS and global integer adds
+// (__atomic_fetch_add).  Every buffer is a
 // heap allocation of exactly the size the C ABI documents - the three fields, the tables (speed_bins - 1 and twice
 // sectors / 2 floats), the workspace and the counts - so an access outside one of them is reported; the LDS arrays are
 // statics of the kernels' own sizes.
@@ -15,66 +16,14 @@
 // vectors on a bin edge, zeros, NaN and +-Inf.  The program computes the same table with a plain loop over the
 // definition of distribution.py and exits non-zero on any differing count, on a slice that does not sum to X * Y and on
 // a count of the absent baseline that is not zero.
-#include <math.h>
-#include <pthread.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
+#include "host_shim.h"
 
-#include <functional>
-#include <limits>
-#include <vector>
-
-#include "../include/windsr_hip.h"
-
-struct Dim3 {
-  unsigned x = 1, y = 1, z = 1;
-};
-static thread_local Dim3 threadIdx, blockIdx;
-static Dim3 gridDim;
-static pthread_barrier_t g_barrier;
-static inline void __syncthreads() { pthread_barrier_wait(&g_barrier); }
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __launch_bounds__(n)
-#define __shared__ static
 #define DS_LDS_ADD(p, v) __atomic_fetch_add((p), (v), __ATOMIC_RELAXED)
 #define DS_GLOBAL_ADD(p, v) __atomic_fetch_add((p), (v), __ATOMIC_RELAXED)
 
 #include "../gan_sr_wind_field_amd/csrc/distribution_kernels.h"
 
 namespace {
-
-std::function<void()> g_body;
-
-void* worker(void* arg) {
-  threadIdx.x = (unsigned)(intptr_t)arg;
-  for (unsigned bz = 0; bz < gridDim.z; ++bz)
-    for (unsigned by = 0; by < gridDim.y; ++by)
-      for (unsigned bx = 0; bx < gridDim.x; ++bx) {
-        blockIdx.x = bx, blockIdx.y = by, blockIdx.z = bz;
-        g_body();
-        pthread_barrier_wait(&g_barrier);  // (LDS is one static array: a block at a time)
-      }
-  return nullptr;
-}
-
-void launch(int nt, unsigned gx, unsigned gy, unsigned gz, std::function<void()> body) {
-  gridDim.x = gx, gridDim.y = gy, gridDim.z = gz;
-  g_body = std::move(body);
-  pthread_barrier_init(&g_barrier, nullptr, (unsigned)nt);
-  std::vector<pthread_t> th((size_t)nt);
-  for (int t = 0; t < nt; ++t) pthread_create(&th[t], nullptr, worker, (void*)(intptr_t)t);
-  for (int t = 0; t < nt; ++t) pthread_join(th[t], nullptr);
-  pthread_barrier_destroy(&g_barrier);
-}
-
-uint64_t g_rng = 0x9e3779b97f4a7c15ull;
-double uniform() {  // (-1, 1)
-  g_rng = g_rng * 6364136223846793005ull + 1442695040888963407ull;
-  return ((double)(g_rng >> 11) / 9007199254740992.0) * 2.0 - 1.0;
-}
 
 // the definition of distribution.py for one voxel -> the index j * (nd + 1) + sector
 int classify(float u, float v, const std::vector<float>& edge2, const std::vector<float>& bx, const std::vector<float>& by,

@@ -3,9 +3,9 @@
 //   ./fss_host_check B X Y NZ hr_c sr_c tl_c nt scale [scale ...]      (tl_c 0: no baseline; nt thresholds 1 .. 8)
 //
 // Runs the three kernels of csrc/fss.hip block by block on host threads, for the address and undefined-behaviour
-// sanitisers: a shim for __global__, __shared__ (a static array, one block at a time), threadIdx / blockIdx,
-// __syncthreads (a pthread barrier), the LDS and global integer adds (__atomic_fetch_add) and the wave sum (every host
-// thread is a wave of its own: the sum is its value, and every thread is a leader).  Every buffer is a heap allocation
+// sanitisers: the shim of tools/host_shim.h (__global__, __shared__ as a static array, one block at a time, threadIdx /
+// blockIdx, __syncthreads as a pthread barrier) with the LDS and global integer adds (__atomic_fetch_add) and the wave sum
+// (every host thread is a wave of its own: the sum is its value, and every thread is a leader).  Every buffer is a heap allocation
 // of exactly the size the C ABI documents - the three fields, the nt thresholds, the workspace and the sums - so an
 // access outside one of them is reported; the LDS arrays are statics of the kernels' own sizes.
 //
@@ -15,70 +15,14 @@
 // tests: a tie with the threshold 8 (u = 0.25, v = 0), values next to it, zeros, NaN and +-Inf.  The program computes
 // the same sums with a plain loop over the definition of fss.py (every box clipped to the plane, position by position)
 // and exits non-zero on any differing sum and on an entry of the absent baseline that is not zero.
-#include <math.h>
-#include <pthread.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
+#include "host_shim.h"
 
-#include <functional>
-#include <limits>
-#include <vector>
-
-#include "../include/windsr_hip.h"
-
-struct Dim3 {
-  unsigned x = 1, y = 1, z = 1;
-};
-static thread_local Dim3 threadIdx, blockIdx;
-static Dim3 gridDim;
-static pthread_barrier_t g_barrier;
-static inline void __syncthreads() { pthread_barrier_wait(&g_barrier); }
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __launch_bounds__(n)
-#define __shared__ static
 #define FS_LDS_ADD(p, v) __atomic_fetch_add((p), (v), __ATOMIC_RELAXED)
 #define FS_GLOBAL_ADD(p, v) __atomic_fetch_add((p), (v), __ATOMIC_RELAXED)
 #define FS_WAVE_SUM(v) (v)
 #define FS_WAVE_LEADER(t) true
 
 #include "../gan_sr_wind_field_amd/csrc/fss_kernels.h"
-
-namespace {
-
-std::function<void()> g_body;
-
-void* worker(void* arg) {
-  threadIdx.x = (unsigned)(intptr_t)arg;
-  for (unsigned bz = 0; bz < gridDim.z; ++bz)
-    for (unsigned by = 0; by < gridDim.y; ++by)
-      for (unsigned bx = 0; bx < gridDim.x; ++bx) {
-        blockIdx.x = bx, blockIdx.y = by, blockIdx.z = bz;
-        g_body();
-        pthread_barrier_wait(&g_barrier);  // (LDS is one static array: a block at a time)
-      }
-  return nullptr;
-}
-
-void launch(int nt, unsigned gx, unsigned gy, unsigned gz, std::function<void()> body) {
-  gridDim.x = gx, gridDim.y = gy, gridDim.z = gz;
-  g_body = std::move(body);
-  pthread_barrier_init(&g_barrier, nullptr, (unsigned)nt);
-  std::vector<pthread_t> th((size_t)nt);
-  for (int t = 0; t < nt; ++t) pthread_create(&th[t], nullptr, worker, (void*)(intptr_t)t);
-  for (int t = 0; t < nt; ++t) pthread_join(th[t], nullptr);
-  pthread_barrier_destroy(&g_barrier);
-}
-
-uint64_t g_rng = 0x9e3779b97f4a7c15ull;
-double uniform() {  // (-1, 1)
-  g_rng = g_rng * 6364136223846793005ull + 1442695040888963407ull;
-  return ((double)(g_rng >> 11) / 9007199254740992.0) * 2.0 - 1.0;
-}
-
-}  // namespace
 
 int main(int argc, char** argv) {
   if (argc < 10) {

@@ -1,8 +1,7 @@
-// Runs the two kernels of csrc/ssim.hip block by block on host threads, for the address and undefined-behaviour
-// sanitisers: a shim for __global__, __shared__ (a static array, one block at a time), threadIdx / blockIdx and
-// __syncthreads (a pthread barrier).  Every buffer is a heap allocation of exactly the size the C ABI documents - the
-// three fields, the taps (win floats), the workspace and the sums - so an access outside one of them is reported; the LDS
-// arrays are statics of the kernels' own sizes.
+// Runs the two kernels of csrc/ssim.hip (ssim_kernels.h with three fields) block by block on host threads, for the address
+// and undefined-behaviour sanitisers, on the shim of tools/host_shim.h.  Every buffer is a heap allocation of exactly the
+// size the C ABI documents - the three fields, the taps (win floats), the workspace and the sums - so an access outside
+// one of them is reported; the LDS arrays are statics of the kernels' own sizes.
 //
 //   clang++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -pthread \
 //       tools/ssim_host_check.cpp -o ssim_host_check
@@ -12,70 +11,9 @@
 // that every result is finite and that the TL pair's sums equal the number of positions exactly.  With a last argument
 // the operands and results are written as raw arrays - hr, sr, tl, taps (float32), out (float64) - for a comparison
 // with ssim.level_ssim_reference.
-#include <math.h>
-#include <pthread.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-
-#include <functional>
-#include <limits>
-#include <vector>
-
-#include "../include/windsr_hip.h"
-
-struct Dim3 {
-  unsigned x = 1, y = 1, z = 1;
-};
-static thread_local Dim3 threadIdx, blockIdx;
-static Dim3 gridDim;
-static pthread_barrier_t g_barrier;
-static inline void __syncthreads() { pthread_barrier_wait(&g_barrier); }
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __launch_bounds__(n)
-#define __shared__ static
+#include "host_shim.h"
 
 #include "../gan_sr_wind_field_amd/csrc/ssim_kernels.h"
-
-namespace {
-
-std::function<void()> g_body;
-
-void* worker(void* arg) {
-  threadIdx.x = (unsigned)(intptr_t)arg;
-  for (unsigned bz = 0; bz < gridDim.z; ++bz)
-    for (unsigned by = 0; by < gridDim.y; ++by)
-      for (unsigned bx = 0; bx < gridDim.x; ++bx) {
-        blockIdx.x = bx, blockIdx.y = by, blockIdx.z = bz;
-        g_body();
-        pthread_barrier_wait(&g_barrier);  // (LDS is one static array: a block at a time)
-      }
-  return nullptr;
-}
-
-void launch(int nt, unsigned gx, unsigned gy, unsigned gz, std::function<void()> body) {
-  gridDim.x = gx, gridDim.y = gy, gridDim.z = gz;
-  g_body = std::move(body);
-  pthread_barrier_init(&g_barrier, nullptr, (unsigned)nt);
-  std::vector<pthread_t> th((size_t)nt);
-  for (int t = 0; t < nt; ++t) pthread_create(&th[t], nullptr, worker, (void*)(intptr_t)t);
-  for (int t = 0; t < nt; ++t) pthread_join(th[t], nullptr);
-  pthread_barrier_destroy(&g_barrier);
-}
-
-uint64_t g_rng = 0x9e3779b97f4a7c15ull;
-double uniform() {  // (-1, 1)
-  g_rng = g_rng * 6364136223846793005ull + 1442695040888963407ull;
-  return ((double)(g_rng >> 11) / 9007199254740992.0) * 2.0 - 1.0;
-}
-
-template <class T> void dump(FILE* f, const T* p, size_t n) {
-  if (f && fwrite(p, sizeof(T), n, f) != n) abort();
-}
-
-}  // namespace
 
 int main(int argc, char** argv) {
   if (argc < 10) {
@@ -94,8 +32,8 @@ int main(int argc, char** argv) {
   const float nan = std::numeric_limits<float>::quiet_NaN();
   // exact-size heap buffers, filled with NaN: the surplus channels and the unwritten workspace must never be read
   std::vector<float> hr((size_t)B * hr_c * vol, nan), sr((size_t)B * sr_c * vol, nan), tl((size_t)B * tl_c * vol, nan);
-  std::vector<float> taps((size_t)win), ws((size_t)ss_workspace_floats(g), nan);
-  std::vector<double> out((size_t)B * NZ * 3 * SS_NS, (double)nan);
+  std::vector<float> taps((size_t)win), ws((size_t)ss_workspace_floats<3>(g), nan);
+  std::vector<double> out((size_t)B * NZ * 3 * ss_ns<3>, (double)nan);
   for (int b = 0; b < B; ++b)
     for (int c = 0; c < 3; ++c)
       for (size_t i = 0; i < vol; ++i) {
@@ -112,16 +50,16 @@ int main(int argc, char** argv) {
   }
   const float c1 = (float)(0.02 * 0.02), c2 = (float)(0.06 * 0.06);
   launch(SS_BLOCK, (unsigned)(g.ntxy * g.nzc), 3, (unsigned)B, [&] {
-    ssim_tile_kernel(hr.data(), hr_c, sr.data(), sr_c, tl.data(), tl_c, taps.data(), c1, c2, g, ws.data());
+    ssim_tile_kernel<3>(hr.data(), hr_c, sr.data(), sr_c, tl.data(), tl_c, taps.data(), c1, c2, g, ws.data());
   });
-  launch(SS_FBLOCK, (unsigned)((g.ZC * SS_NS + 63) / 64), (unsigned)(3 * g.nzc), (unsigned)B,
-         [&] { ssim_final_kernel(ws.data(), g, out.data()); });
+  launch(SS_FBLOCK, (unsigned)((g.ZC * ss_ns<3> + 63) / 64), (unsigned)(3 * g.nzc), (unsigned)B,
+         [&] { ssim_final_kernel<3>(ws.data(), g, out.data()); });
 
   const double npos = (double)g.PX * g.PY;
   size_t bad = 0, off = 0;  // every sum written and finite; TL = HR: exactly npos
   for (size_t i = 0; i < out.size(); ++i) {
     bad += !isfinite(out[i]);
-    if (i % SS_NS >= 2) off += out[i] != npos;
+    if (i % ss_ns<3> >= 2) off += out[i] != npos;
   }
   if (argc > 10) {
     FILE* fp = fopen(argv[10], "wb");

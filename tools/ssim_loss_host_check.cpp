@@ -1,6 +1,5 @@
-// Runs the kernels of csrc/ssim_loss.hip block by block on host threads, for the address and undefined-behaviour
-// sanitisers: a shim for __global__, __shared__ (a static array, one block at a time), threadIdx / blockIdx and
-// __syncthreads (a pthread barrier), as tools/ssim_host_check.cpp is for csrc/ssim.hip.  Every buffer is a heap
+// Runs the kernels of csrc/ssim_loss.hip (ssim_kernels.h with two fields, ssim_loss_kernels.h) block by block on host
+// threads, for the address and undefined-behaviour sanitisers, on the shim of tools/host_shim.h.  Every buffer is a heap
 // allocation of exactly the size the C ABI documents - the two fields, the taps (win floats), the workspace, the sums,
 // gout and dsr - so an access outside one of them is reported; the LDS arrays are statics of the kernels' own sizes.
 //
@@ -15,64 +14,11 @@
 // pixels, the three coefficients, then for each pixel the sum over the positions whose window holds it), and, with SR a
 // copy of HR, that every sum equals the number of positions exactly.  The built-in shapes hold a plane that is one
 // tile, planes of several tiles with clipped border tiles, and a partial last z chunk.
-#include <math.h>
-#include <pthread.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-
-#include <functional>
-#include <limits>
-#include <vector>
-
-#include "../include/windsr_hip.h"
-
-struct Dim3 {
-  unsigned x = 1, y = 1, z = 1;
-};
-static thread_local Dim3 threadIdx, blockIdx;
-static Dim3 gridDim;
-static pthread_barrier_t g_barrier;
-static inline void __syncthreads() { pthread_barrier_wait(&g_barrier); }
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __launch_bounds__(n)
-#define __shared__ static
+#include "host_shim.h"
 
 #include "../gan_sr_wind_field_amd/csrc/ssim_loss_kernels.h"
 
 namespace {
-
-std::function<void()> g_body;
-
-void* worker(void* arg) {
-  threadIdx.x = (unsigned)(intptr_t)arg;
-  for (unsigned bz = 0; bz < gridDim.z; ++bz)
-    for (unsigned by = 0; by < gridDim.y; ++by)
-      for (unsigned bx = 0; bx < gridDim.x; ++bx) {
-        blockIdx.x = bx, blockIdx.y = by, blockIdx.z = bz;
-        g_body();
-        pthread_barrier_wait(&g_barrier);  // (LDS is one static array: a block at a time)
-      }
-  return nullptr;
-}
-
-void launch(int nt, unsigned gx, unsigned gy, unsigned gz, std::function<void()> body) {
-  gridDim.x = gx, gridDim.y = gy, gridDim.z = gz;
-  g_body = std::move(body);
-  pthread_barrier_init(&g_barrier, nullptr, (unsigned)nt);
-  std::vector<pthread_t> th((size_t)nt);
-  for (int t = 0; t < nt; ++t) pthread_create(&th[t], nullptr, worker, (void*)(intptr_t)t);
-  for (int t = 0; t < nt; ++t) pthread_join(th[t], nullptr);
-  pthread_barrier_destroy(&g_barrier);
-}
-
-uint64_t g_rng = 0x9e3779b97f4a7c15ull;
-double uniform() {  // (-1, 1)
-  g_rng = g_rng * 6364136223846793005ull + 1442695040888963407ull;
-  return ((double)(g_rng >> 11) / 9007199254740992.0) * 2.0 - 1.0;
-}
 
 // 0: fine
 int run(int B, int X, int Y, int NZ, int win, double sigma, int hr_c, int sr_c) {
@@ -86,8 +32,8 @@ int run(int B, int X, int Y, int NZ, int win, double sigma, int hr_c, int sr_c) 
   const float nan = std::numeric_limits<float>::quiet_NaN();
   // exact-size heap buffers, filled with NaN: the surplus channels and the unwritten workspace must never be read
   std::vector<float> hr((size_t)B * hr_c * vol, nan), sr((size_t)B * sr_c * vol, nan), same((size_t)B * 3 * vol);
-  std::vector<float> taps((size_t)win), ws((size_t)ssl_workspace_floats(g), nan), dsr((size_t)B * 3 * vol, nan);
-  std::vector<double> out((size_t)B * NZ * 3 * SSL_NS, (double)nan), out_same(out.size(), (double)nan), gout(out.size());
+  std::vector<float> taps((size_t)win), ws((size_t)ss_workspace_floats<2>(g), nan), dsr((size_t)B * 3 * vol, nan);
+  std::vector<double> out((size_t)B * NZ * 3 * ss_ns<2>, (double)nan), out_same(out.size(), (double)nan), gout(out.size());
   for (int b = 0; b < B; ++b)
     for (int c = 0; c < 3; ++c)
       for (size_t i = 0; i < vol; ++i) {
@@ -104,17 +50,17 @@ int run(int B, int X, int Y, int NZ, int win, double sigma, int hr_c, int sr_c) 
     for (int k = 0; k < win; ++k) gd[k] = (double)(taps[k] = (float)(gd[k] / sum));
   }
   const float c1 = (float)(0.02 * 0.02), c2 = (float)(0.06 * 0.06);
-  const unsigned fgrid = (unsigned)((g.ZC * SSL_NS + 63) / 64);
+  const unsigned fgrid = (unsigned)((g.ZC * ss_ns<2> + 63) / 64);
   launch(SS_BLOCK, (unsigned)(g.ntxy * g.nzc), 3, (unsigned)B,
-         [&] { ssl_tile_kernel(hr.data(), hr_c, sr.data(), sr_c, taps.data(), c1, c2, g, ws.data()); });
-  launch(SS_FBLOCK, fgrid, (unsigned)(3 * g.nzc), (unsigned)B, [&] { ssl_final_kernel(ws.data(), g, out.data()); });
+         [&] { ssim_tile_kernel<2>(hr.data(), hr_c, sr.data(), sr_c, nullptr, 0, taps.data(), c1, c2, g, ws.data()); });
+  launch(SS_FBLOCK, fgrid, (unsigned)(3 * g.nzc), (unsigned)B, [&] { ssim_final_kernel<2>(ws.data(), g, out.data()); });
   launch(SS_BLOCK, (unsigned)(gb.ntxy * gb.nzc), 3, (unsigned)B, [&] {
     ssl_bwd_kernel(hr.data(), hr_c, sr.data(), sr_c, gout.data(), taps.data(), c1, c2, gb, dsr.data());
   });
   // SR a copy of HR (three channels): every sum is the number of positions
   launch(SS_BLOCK, (unsigned)(g.ntxy * g.nzc), 3, (unsigned)B,
-         [&] { ssl_tile_kernel(hr.data(), hr_c, same.data(), 3, taps.data(), c1, c2, g, ws.data()); });
-  launch(SS_FBLOCK, fgrid, (unsigned)(3 * g.nzc), (unsigned)B, [&] { ssl_final_kernel(ws.data(), g, out_same.data()); });
+         [&] { ssim_tile_kernel<2>(hr.data(), hr_c, same.data(), 3, nullptr, 0, taps.data(), c1, c2, g, ws.data()); });
+  launch(SS_FBLOCK, fgrid, (unsigned)(3 * g.nzc), (unsigned)B, [&] { ssim_final_kernel<2>(ws.data(), g, out_same.data()); });
 
   // ---- the definition, in double
   const int PX = g.PX, PY = g.PY;
@@ -128,7 +74,7 @@ int run(int B, int X, int Y, int NZ, int win, double sigma, int hr_c, int sr_c) 
         const float* pa = hr.data() + ((size_t)b * hr_c + c) * vol;
         const float* ps = sr.data() + ((size_t)b * sr_c + c) * vol;
         auto at = [&](const float* p, int x, int y) { return (double)p[((size_t)x * Y + y) * NZ + z]; };
-        const size_t gi = (((size_t)b * NZ + z) * 3 + c) * SSL_NS;
+        const size_t gi = (((size_t)b * NZ + z) * 3 + c) * ss_ns<2>;
         const double G0 = (double)(float)gout[gi], G1 = (double)(float)gout[gi + 1];
         double s0 = 0.0, s1 = 0.0;
         for (int qx = 0; qx < PX; ++qx)
