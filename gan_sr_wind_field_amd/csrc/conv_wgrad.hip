@@ -253,6 +253,12 @@ int wsr_wgrad_tile_bf16(const wsr_conv_t* c, const void* x, const void* dy, floa
                         long part_stride, int n_parts, int* plan, void* stream, const void* x2, int x2_ctot,
                         int x2_c0);  // conv_wgrad_tile.hip
 
+int wsr_wgrad_tile_bf16_lat4(const wsr_conv_t* c, const void* x, const void* dy, float* parts, long part_stride,
+                             long class_stride, int n_parts, int* plan, void* stream);  // conv_wgrad_tile.hip
+
+int wsr_wgrad_tile_bf16_bias(const wsr_conv_t* c, const void* x, const void* dy, float* parts, long part_stride, int n_parts,
+                             float* bias_parts, int* plan, void* stream);  // conv_wgrad_tile.hip
+
 int wsr_wgrad_tile_f32(const wsr_conv_t* c, const void* x, const void* dy, float* dw, long part_stride, int n_parts,
                        int* plan, void* stream, const void* x2, int x2_ctot, int x2_c0);  // conv_wgrad_tile_f32.hip
 
@@ -335,4 +341,48 @@ extern "C" int wsr_conv3d_wgrad_parts_x2(const wsr_conv_t* c, const void* x, con
   if (!conv_geom_ok_split(c, x2_c0) || !x || !x2 || !dy || !parts || n_parts <= 0 || x2_ctot <= 0) return WSR_EINVAL;
   if (part_stride < (int64_t)c->Cout * c->KX * c->KY * c->KZ * c->Cin) return WSR_EINVAL;
   return wgrad_any(c, x, dy, parts, 0, 0, (long)part_stride, n_parts, nullptr, stream, x2, x2_ctot, x2_c0);
+}
+
+// The four xy-parity classes of one lattice-form filter gradient (lat = 2: the parity convs of a sub-pixel up-conv;
+// lat = 3: one z-class of a strided conv in parity form) in ONE launch.  `c` describes class (0, 0): lat_ox = lat_oy = 0,
+// (px, py) the low pads of that class (lat_phases 0 or 4).
+static int lat4_desc(const wsr_conv_t* c, wsr_conv_t* t) {
+  if (!c || (c->lat_phases != 0 && c->lat_phases != 4)) return 0;
+  *t = *c;
+  t->lat_phases = 0;
+  return conv_geom_ok(t) && (t->lat == 2 || t->lat == 3) && t->lat_ox == 0 && t->lat_oy == 0 && t->px >= 1 && t->py >= 1;
+}
+
+extern "C" int wsr_conv3d_wgrad_nparts_lat4(const wsr_conv_t* c, int32_t* n_parts) {
+  wsr_conv_t t;
+  if (!n_parts || !lat4_desc(c, &t)) return WSR_EINVAL;
+  int plan = 0;
+  const int rc = wsr_wgrad_tile_bf16_lat4(&t, nullptr, nullptr, nullptr, 0, -1, 0, &plan, nullptr);
+  *n_parts = plan;
+  return rc;
+}
+
+extern "C" int wsr_conv3d_wgrad_parts_lat4(const wsr_conv_t* c, const void* x, const void* dy, float* parts,
+                                           int64_t part_stride, int64_t class_stride, int32_t n_parts, void* stream) {
+  wsr_conv_t t;
+  if (!lat4_desc(c, &t) || !x || !dy || !parts || n_parts <= 0) return WSR_EINVAL;
+  if (part_stride < (int64_t)t.Cout * t.KX * t.KY * t.KZ * t.Cin || class_stride < part_stride * n_parts) return WSR_EINVAL;
+  return wsr_wgrad_tile_bf16_lat4(&t, x, dy, parts, (long)part_stride, (long)class_stride, n_parts, nullptr, stream);
+}
+
+// Filter gradient of a 1x1x1 conv with a bias (the generator's LFF convs) in the deterministic form, the bias gradient's
+// partial sums taken by the same launch from the dy fragments it holds anyway.
+extern "C" int wsr_conv3d_wgrad_nparts_bias(const wsr_conv_t* c, int32_t* n_parts) {
+  if (!conv_geom_ok(c) || !n_parts) return WSR_EINVAL;
+  int plan = 0;
+  const int rc = wsr_wgrad_tile_bf16_bias(c, nullptr, nullptr, nullptr, 0, 0, nullptr, &plan, nullptr);
+  *n_parts = plan;
+  return rc;
+}
+
+extern "C" int wsr_conv3d_wgrad_parts_bias(const wsr_conv_t* c, const void* x, const void* dy, float* parts,
+                                           int64_t part_stride, int32_t n_parts, float* bias_parts, void* stream) {
+  if (!conv_geom_ok(c) || !x || !dy || !parts || !bias_parts || n_parts <= 0) return WSR_EINVAL;
+  if (part_stride < (int64_t)c->Cout * c->KX * c->KY * c->KZ * c->Cin) return WSR_EINVAL;
+  return wsr_wgrad_tile_bf16_bias(c, x, dy, parts, (long)part_stride, n_parts, bias_parts, nullptr, stream);
 }

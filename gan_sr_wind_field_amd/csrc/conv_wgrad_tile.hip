@@ -66,6 +66,11 @@ struct WgtArgs {
   int xl_m, xl_ox, xl_oy;       // x is the sub-lattice (m*x + ox, m*y + oy, mz*z + oz) of a tensor m (mz) times as large
   int xl_mz, xl_oz;             // (filter gradients of the stride-2 down-sampling convs in parity form, wsr_conv_t.lat = 3)
   int prio;                     // 1: waves 4..7 at s_setprio 1 in the tile loop (tuning switch)
+  int nphase;                   // 4: the four xy-parity classes (a, b) of one lattice-form conv in ONE launch, the class two bits
+                                // of the workgroup index: low pads (px - a, py - b), lattice offsets (a, b) of dy (yl_m = 2) or
+                                // (px - a, py - b) of x (xl_m = 2); else 1
+  long class_stride;            // ... and its sums at dw + class*class_stride + s*part_stride
+  float* bias_parts;            // BIAS instantiation (1x1x1): split s of c-chunk 0 stores sum_v dy[v, n] at bias_parts[s*Cout + n]
   int S_forced;                 // > 0: the number of spatial splits the caller was told (wsr_conv3d_wgrad_nparts)
   int plan_only;                // host side: compute the launch geometry (S) and return without launching
   unsigned long long* stamps;  // -DWSR_CT_STAMPS builds: [workgroup][8] clock samples (else unused)
@@ -125,8 +130,15 @@ constexpr int wgt_rby(int tn) { return tn == 1 ? 32 : (tn <= 4 ? 128 : 256); }
 constexpr int wgt_xk(int spw, int tn) { return spw * tn * 4 >= 192 ? 5 : 6; }
 constexpr int wgt_yk(int spw, int tn) { return spw * tn * 4 >= 192 ? 4 : 5; }
 
-template <int TN, int SPW, int CT, bool Z16>
-__global__ __launch_bounds__(512) void wgrad_tile_kernel(const WgtArgs a) {
+// BIAS (the 1x1x1 instantiation <8, 1, 8> only: the LFF convs): wave w also keeps the column sums of n-tile w - the
+// bias gradient - as one more accumulator tile, fed by one MFMA per K-step whose x operand is a fragment of ones and
+// whose dy operand is n-tile w's fragment of the tile in LDS: no second pass over dy in HBM (it was
+// wsr_chan_sum_partials').  The wave holds that fragment among its eight already, but picking register set `wave` costs
+// 28 selects per K-step and their masks in scalar registers: 43.2 us per LFF launch against 40.4 with the fragment read
+// once more (two transposing reads on top of 18 per K-step) and 39.4 without the sums.
+template <int TN, int SPW, int CT, bool Z16, bool BIAS>
+__device__ __forceinline__ void wgrad_tile_body(const WgtArgs& a) {
+  static_assert(!BIAS || (TN == 8 && SPW == 1), "one n-tile per wave");
   constexpr int WAVES = 8, NT = 512;
   constexpr int XRPU = 32;            // x rows (32 B) per 1 KB DMA unit
   constexpr int XK = wgt_xk(SPW, TN), YK = wgt_yk(SPW, TN);  // DMA units per wave per tile (checked on the host)
@@ -151,6 +163,17 @@ __global__ __launch_bounds__(512) void wgrad_tile_kernel(const WgtArgs a) {
   // ---- which chunk pair / spatial slice ------------------------------------------
   int bid = xcd_remap(blockIdx.x, gridDim.x);
   int cc, nc, s0;
+  // classes of a merged lattice launch sit side by side in the grid (up-conv form: they gather the same x halo)
+  int cls = 0;
+  if (a.nphase == 4) {
+    cls = bid & 3;
+    bid >>= 2;
+  }
+  const int px = a.px - (cls >> 1), py = a.py - (cls & 1);
+  const int yl_ox = a.nphase == 4 ? (a.yl_m == 2 ? cls >> 1 : 0) : a.yl_ox;
+  const int yl_oy = a.nphase == 4 ? (a.yl_m == 2 ? cls & 1 : 0) : a.yl_oy;
+  const int xl_ox = a.nphase == 4 ? (a.xl_m == 2 ? px : 0) : a.xl_ox;
+  const int xl_oy = a.nphase == 4 ? (a.xl_m == 2 ? py : 0) : a.xl_oy;
   if (a.n_active > 0) {  // pairs the triangular structure leaves empty are not launched at all
     const int pr = bid % a.n_active;
     s0 = bid / a.n_active;
@@ -196,7 +219,7 @@ __global__ __launch_bounds__(512) void wgrad_tile_kernel(const WgtArgs a) {
   // element offset from the tile's first (halo) voxel, channel included.  Per tile only a scalar base, the
   // add, and - for tiles that touch the volume border - three range checks remain.
   const int U = a.ups ? 1 : 0;
-  const int parx = U ? ((-a.px) & 1) : 0, pary = U ? ((-a.py) & 1) : 0;  // parity of x0 - px (TX, TY even when up-sampled)
+  const int parx = U ? ((-px) & 1) : 0, pary = U ? ((-py) & 1) : 0;  // parity of x0 - px (TX, TY even when up-sampled)
   const int XUP = (L + XRPU - 1) / XRPU;  // 1 KB units per c-tile plane of the x image
   const int XU = XUP * CT;
   const int YU = (M + YRPU - 1) / YRPU;   // ... of the dy image
@@ -254,12 +277,12 @@ __global__ __launch_bounds__(512) void wgrad_tile_kernel(const WgtArgs a) {
     const unsigned dstx = buf_lds + buf * a.buf_bytes;
     const unsigned dsty = dstx + a.xs_bytes;
     {  // x image with halo: halo voxel h sits at (x0 - px + hx, ...) of the (up-sampled) input
-      const int lox = a.px - x0, loy = a.py - y0, loz = a.pz - z0;  // first in-range halo coordinate
+      const int lox = px - x0, loy = py - y0, loz = a.pz - z0;  // first in-range halo coordinate
       const int sx_ = a.Xi << U, sy_ = a.Yi << U;
       const bool inner = lox <= 0 && Lx - lox <= sx_ && loy <= 0 && Ly - loy <= sy_ && loz <= 0 && Lz - loz <= a.Zi;
       // (xl_m = xl_mz = 1 unless the input sits on a lattice; then U = 0)
-      const long base = ((((long)b * a.Xi * a.xl_m + (long)((x0 - a.px - parx) >> U) * a.xl_m + a.xl_ox) * (a.Yi * a.xl_m) +
-                          (long)((y0 - a.py - pary) >> U) * a.xl_m + a.xl_oy) * (a.Zi * a.xl_mz) +
+      const long base = ((((long)b * a.Xi * a.xl_m + (long)((x0 - px - parx) >> U) * a.xl_m + xl_ox) * (a.Yi * a.xl_m) +
+                          (long)((y0 - py - pary) >> U) * a.xl_m + xl_oy) * (a.Zi * a.xl_mz) +
                          (long)(z0 - a.pz) * a.xl_mz + a.xl_oz) * x_ctot + x_off;
       const unsigned short* bp = xt + base;
 #pragma unroll
@@ -285,7 +308,7 @@ __global__ __launch_bounds__(512) void wgrad_tile_kernel(const WgtArgs a) {
     {  // dy image: tile voxels only
       const int hix = a.Xo - x0, hiy = a.Yo - y0, hiz = a.Zo - z0;
       const bool inner = a.TX <= hix && a.TY <= hiy && a.TZ <= hiz;
-      const long base = ((((long)b * a.Xo * a.yl_m + x0 * a.yl_m + a.yl_ox) * (a.Yo * a.yl_m) + y0 * a.yl_m + a.yl_oy) *
+      const long base = ((((long)b * a.Xo * a.yl_m + x0 * a.yl_m + yl_ox) * (a.Yo * a.yl_m) + y0 * a.yl_m + yl_oy) *
                              a.Zo + z0) * a.out_ctot + a.out_off + n0;
       const unsigned short* bp = a.dy + base;
 #pragma unroll
@@ -324,6 +347,7 @@ __global__ __launch_bounds__(512) void wgrad_tile_kernel(const WgtArgs a) {
   for (int j = 0; j < SPW; ++j)
 #pragma unroll
     for (int i = 0; i < TN; ++i) acc[j][i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  f32x4_t accb = f32x4_t{0.f, 0.f, 0.f, 0.f};  // BIAS: every column = sum over the voxels of dy[v, n0 + 16*wave + row]
 
   // tr-read lane roles: 16-lane group G supplies rows (voxels) 4G+q (+16), columns 4p..4p+3 of a 16-wide tile
   const int G = lane >> 4, q = (lane & 15) >> 2, p = lane & 3;
@@ -489,6 +513,12 @@ __global__ __launch_bounds__(512) void wgrad_tile_kernel(const WgtArgs a) {
 #pragma unroll
           for (int i = SPW; i < TN; ++i) afn[i] = af_of(kn, i);
         }
+        if constexpr (BIAS) {  // n-tile `wave` of this K-step against ones
+          const uint4 afw = af_of(kc, wave);
+          const uint4 ones = make_uint4(0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u);  // bf16 1.0 x 8
+          accb = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, afw), __builtin_bit_cast(bf16x8_t, ones),
+                                                         accb, 0, 0, 0);
+        }
         if constexpr (R == 1) ring[0] = nb;
         kc = kn;
       };
@@ -520,7 +550,7 @@ __global__ __launch_bounds__(512) void wgrad_tile_kernel(const WgtArgs a) {
 
   // ---- this workgroup's partial sums: acc[j][i][r] -> n = n0+16i+4G+r, c = c0+16ct+(lane&15); stored to the
   // split's own copy (deterministic two-pass form) or added to the shared one
-  float* const dwp = a.dw + (long)s0 * a.part_stride;
+  float* const dwp = a.dw + (long)cls * a.class_stride + (long)s0 * a.part_stride;
   const bool store = a.part_stride > 0;
 #pragma unroll
   for (int j = 0; j < SPW; ++j) {
@@ -543,6 +573,15 @@ __global__ __launch_bounds__(512) void wgrad_tile_kernel(const WgtArgs a) {
       }
     }
   }
+  if constexpr (BIAS) {  // column 0 of the extra tile: lanes 0, 16, 32, 48 hold rows 4G .. 4G+3
+    if (cc == 0 && (lane & 15) == 0) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int n = n0 + 16 * wave + 4 * G + r;
+        if (n < a.Cout) a.bias_parts[(long)s0 * a.Cout + n] = accb[r];
+      }
+    }
+  }
   WG_STAMP(3);
   WG_STAMP(7);
 #ifdef WSR_CT_STAMPS
@@ -551,6 +590,15 @@ __global__ __launch_bounds__(512) void wgrad_tile_kernel(const WgtArgs a) {
     a.stamps[(size_t)blockIdx.x * 8 + 5] = (unsigned long long)st_tiles;
   }
 #endif
+}
+
+template <int TN, int SPW, int CT, bool Z16>
+__global__ __launch_bounds__(512) void wgrad_tile_kernel(const WgtArgs a) {
+  wgrad_tile_body<TN, SPW, CT, Z16, false>(a);
+}
+template <bool Z16>
+__global__ __launch_bounds__(512) void wgrad_tile_bias_kernel(const WgtArgs a) {
+  wgrad_tile_body<8, 1, 8, Z16, true>(a);
 }
 
 static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
@@ -643,8 +691,14 @@ int launch_tile(WgtArgs& a, hipStream_t st) {
   // dense-block and the 5x5x5 wgrad: launches of <= 256 workgroups are fastest, a launch just over a
   // multiple of 256 is up to 1.6x slower (a nearly empty extra round), and more, smaller workgroups
   // only add accumulator flushes (each flush is worth ~6 tiles of MFMA work at the atomic rate).
-  int S = 256 / combos;
-  if (S < 1) S = 1;
+  // (a merged lattice launch holds the four classes side by side: S splits PER CLASS, each with the tile list a
+  // single-class launch of the same S walks - the same numbers added in the same order)
+  const int nphase = a.nphase == 4 ? 4 : 1;
+  int S = 256 / (combos * nphase);
+  if (S < 1) {
+    if (nphase > 1) return WSR_EUNSUPPORTED;  // the caller launches the classes one by one
+    S = 1;
+  }
   if (S > a.ntiles) S = a.ntiles;
   a.S = S;
   if (WSR_ENV_SET("WSR_WGRAD_S")) {  // tuning aid
@@ -655,19 +709,28 @@ int launch_tile(WgtArgs& a, hipStream_t st) {
   if (a.part_stride > 0 && a.S_forced != a.S) return WSR_EINVAL;  // the caller sized `parts` for another split
   const bool z16 = a.TZ % 16 == 0;
   auto kern = z16 ? wgrad_tile_kernel<TN, SPW, CT, true> : wgrad_tile_kernel<TN, SPW, CT, false>;
-  static bool attr_done[2] = {false, false};  // raise the dynamic-LDS cap once per instantiation
-  if (!attr_done[z16]) {
+  int ki = z16;
+  if (a.bias_parts) {
+    if constexpr (TN == 8 && SPW == 1) {
+      kern = z16 ? wgrad_tile_bias_kernel<true> : wgrad_tile_bias_kernel<false>;
+      ki += 2;
+    } else {
+      return WSR_EUNSUPPORTED;
+    }
+  }
+  static bool attr_done[4] = {false, false, false, false};  // raise the dynamic-LDS cap once per instantiation
+  if (!attr_done[ki]) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        160 * 1024);
     if (e != hipSuccess) return (int)e;
-    attr_done[z16] = true;
+    attr_done[ki] = true;
   }
 #ifdef WSR_CT_STAMPS
   a.stamps = getenv("WSR_CT_STAMPS_PTR") ? (unsigned long long*)strtoull(getenv("WSR_CT_STAMPS_PTR"), nullptr, 0) : nullptr;
   a.ablate = WSR_ENV_INT("WSR_CT_ABL", 0);
 #endif
   a.prio = WSR_ENV_INT("WSR_CT_PRIO", 0);
-  hipLaunchKernelGGL(kern, dim3((unsigned)(combos * a.S)), dim3(WAVES * 64), lds, st, a);
+  hipLaunchKernelGGL(kern, dim3((unsigned)(combos * a.S * nphase)), dim3(WAVES * 64), lds, st, a);
   WSR_LAUNCH_CHECK();
   return 0;
 }
@@ -682,8 +745,40 @@ int run_tile(WgtArgs& a, int taps, int Cout, int Cin, hipStream_t st);
 // wsr_conv3d_wgrad then falls back to the per-tap split-K kernel.
 // part_stride > 0: deterministic form with n_parts (as returned by a plan call) split copies; plan != nullptr: only
 // report the number of spatial splits (*plan) the launch would use.
+static int wgrad_tile_bf16_any(const wsr_conv_t* c, const void* x, const void* dy, float* dw, int tri_base, int tri_step,
+                               long part_stride, int n_parts, int* plan, void* stream, const void* x2, int x2_ctot,
+                               int x2_c0, long class_stride, float* bias_parts = nullptr, bool want_bias = false);
+
 int wsr_wgrad_tile_bf16(const wsr_conv_t* c, const void* x, const void* dy, float* dw, int tri_base, int tri_step,
                         long part_stride, int n_parts, int* plan, void* stream, const void* x2, int x2_ctot, int x2_c0) {
+  return wgrad_tile_bf16_any(c, x, dy, dw, tri_base, tri_step, part_stride, n_parts, plan, stream, x2, x2_ctot, x2_c0, 0);
+}
+
+// All four xy-parity classes of one lattice-form filter gradient in ONE launch (wsr_conv3d_wgrad_parts_lat4): `c` is the
+// class-(0, 0) conv with lat_ox = lat_oy = 0 and the base low pads (class (a, b) runs with px - a, py - b), sums of class
+// 2a + b at parts + (2a + b)*class_stride + s*part_stride.  WSR_EUNSUPPORTED: launch the classes one by one.
+int wsr_wgrad_tile_bf16_lat4(const wsr_conv_t* c, const void* x, const void* dy, float* parts, long part_stride,
+                             long class_stride, int n_parts, int* plan, void* stream) {
+  if ((c->lat != 2 && c->lat != 3) || c->lat_ox || c->lat_oy || c->px < 1 || c->py < 1) return WSR_EUNSUPPORTED;
+  if (c->lat == 3 && (c->px != 1 || c->py != 1)) return WSR_EUNSUPPORTED;  // x lattice offset of class (a, b) = (1 - a, 1 - b)
+  if (c->lat == 2 && c->lat_mz > 1) return WSR_EUNSUPPORTED;
+  return wgrad_tile_bf16_any(c, x, dy, parts, 0, 0, part_stride, n_parts, plan, stream, nullptr, 0, 0, class_stride);
+}
+
+// The 1x1x1 filter gradient with the bias gradient's partial sums taken in the same launch (wsr_conv3d_wgrad_parts_bias):
+// split s also stores sum_v dy[v, n] at bias_parts[s*Cout + n].  WSR_EUNSUPPORTED: not the 1x1x1 tile instantiation.
+int wsr_wgrad_tile_bf16_bias(const wsr_conv_t* c, const void* x, const void* dy, float* parts, long part_stride, int n_parts,
+                             float* bias_parts, int* plan, void* stream) {
+  return wgrad_tile_bf16_any(c, x, dy, parts, 0, 0, part_stride, n_parts, plan, stream, nullptr, 0, 0, 0, bias_parts, true);
+}
+
+// class_stride > 0 (or a plan call with class_stride < 0): the merged four-class form
+static int wgrad_tile_bf16_any(const wsr_conv_t* c, const void* x, const void* dy, float* dw, int tri_base, int tri_step,
+                               long part_stride, int n_parts, int* plan, void* stream, const void* x2, int x2_ctot,
+                               int x2_c0, long class_stride, float* bias_parts, bool want_bias) {
+  // (the fused bias sums live in the 1x1x1 instantiation alone; anything else keeps its own channel-sum pass)
+  if (want_bias && (c->KX * c->KY * c->KZ != 1 || c->lat || c->upsample_xy || c->Cout < 64 || c->Cin < 64 || x2 || tri_step > 0))
+    return WSR_EUNSUPPORTED;
   if (c->dtype != WSR_BF16 || (c->sx | c->sy | c->sz) != 1) return WSR_EUNSUPPORTED;
   if (x2 && (c->lat || c->upsample_xy || tri_step > 0 || x2_c0 <= 0 || x2_c0 >= c->Cin || x2_c0 % 32 || x2_ctot % 8 ||
              c->Cin - x2_c0 > x2_ctot))
@@ -716,6 +811,9 @@ int wsr_wgrad_tile_bf16(const wsr_conv_t* c, const void* x, const void* dy, floa
   }
   a.tri_base = tri_base; a.tri_step = tri_step;
   a.part_stride = part_stride; a.S_forced = n_parts; a.plan_only = plan ? 1 : 0;
+  a.bias_parts = bias_parts;
+  a.nphase = class_stride != 0 ? 4 : 1;
+  a.class_stride = class_stride > 0 ? class_stride : 0;
   if (taps == 1 && !c->lat && !c->upsample_xy && c->Zi % 16 != 0 && (c->px | c->py | c->pz) == 0) {
     // A 1x1x1 conv has no halo: its filter gradient is a GEMM over the voxel INDEX, whatever the volume's shape.  The
     // tile picker wants 16-level tiles (the reference's 10-level patches left it no tile that fits two LDS buffers:

@@ -85,6 +85,13 @@ STRIDED_WGRAD = __import__("os").environ.get("WSR_STRIDED_WGRAD", "1") != "0"
 SUBPIXEL = __import__("os").environ.get("WSR_SUBPIXEL", "1") != "0"
 #: ... and their filter gradients too (WSR_SUBPIXEL_WGRAD=0: the 27-tap gradient through the up-sampling gather)
 SUBPIXEL_WGRAD = __import__("os").environ.get("WSR_SUBPIXEL_WGRAD", "1") != "0"
+#: the four xy-parity classes of a lattice-form filter gradient (up-convs; one z-class of a strided conv) in ONE launch
+#: with 256 / (4 x chunk pairs) splits per class: a quarter of the launches, prologues, flushes and split copies
+#: (WSR_WGRAD_LAT4=0: one launch per class)
+WGRAD_LAT4 = __import__("os").environ.get("WSR_WGRAD_LAT4", "1") != "0"
+#: bias gradient of the LFF convs (1x1x1) as one more accumulator tile of their filter-gradient launch, which holds the
+#: dy fragments anyway (WSR_LFF_BIAS_FUSED=0: a channel-sum pass of its own over dy, wsr_chan_sum_partials)
+LFF_BIAS_FUSED = __import__("os").environ.get("WSR_LFF_BIAS_FUSED", "1") != "0"
 
 
 def compute_dtype_of(flag) -> torch.dtype:
@@ -449,22 +456,35 @@ class ProgramBase:
 
     def wgrad(self, s: ConvSite, x: Tensor, x_off: int, g: Tensor, g_off: int, flat: Tensor, space: GradSpace,
               scratch: Tensor, scale: float = 1.0, dst: Optional[Tensor] = None, x2: Optional[Tensor] = None,
-              x2_c0: int = 0) -> None:
+              x2_c0: int = 0, bias_dst: Optional[Tensor] = None) -> bool:
         """master-layout gradient slot of s.weight (or ``dst``) = scale * wgrad(x[window], g[window]);
-        ``x2``: the conv's input channels >= ``x2_c0`` live in this second tensor (see SPLIT_CAT)"""
+        ``x2``: the conv's input channels >= ``x2_c0`` live in this second tensor (see SPLIT_CAT).
+        ``bias_dst`` (Cout floats): the bias gradient scale * sum_v g[v, :] goes there too when the kernel can take it in
+        the same launch (LFF_BIAS_FUSED) - True is returned then; False: the caller sums the channels itself."""
         B = x.shape[0]
         cin_p = self.cp(s.cin)
         d = self._desc(s, B, tuple(x.shape[1:4]), x.shape[-1], x_off, g.shape[-1], g_off, cin=cin_p)
         out = space.view(flat, s.weight) if dst is None else dst
+        fused = False
         if x2 is not None and not DETERMINISTIC:
             raise RuntimeError("a two-tensor filter gradient needs the deterministic form (set WSR_SPLIT_CAT=0)")
         if DETERMINISTIC:
             # (the split count is a property of the un-split conv's geometry: asked with the concatenated width)
             dq = d if x2 is None else self._desc(s, B, tuple(x.shape[1:4]), cin_p, 0, g.shape[-1], g_off, cin=cin_p)
             n = self._wgrad_nparts(("w", s.name, B) + tuple(x.shape[1:4]), dq)
+            if (bias_dst is not None and LFF_BIAS_FUSED and x2 is None
+                    and self._wgrad_nparts(("wb", s.name, B) + tuple(x.shape[1:4]), d, bias=True) == n):
+                fused = True
+                self._arena_reserve(n * s.cout * s.taps * cin_p + n * s.cout + 64, x.device)
+                bp = self._arena_take(n * s.cout, x.device).view(n, s.cout)
             parts = self._arena_take(n * s.cout * s.taps * cin_p, x.device).view(n, s.cout, s.taps, cin_p)
-            run = lambda: ops.conv_wgrad_parts(d, x, g, parts, n, x2=x2, x2_c0=x2_c0)  # noqa: E731
+            if fused:
+                run = lambda: ops.conv_wgrad_parts_bias(d, x, g, parts, n, bp)  # noqa: E731
+            else:
+                run = lambda: ops.conv_wgrad_parts(d, x, g, parts, n, x2=x2, x2_c0=x2_c0)  # noqa: E731
             self._pending_unpack.append((parts[0], out, scale, n, parts[0].numel()))
+            if fused:  # one output row, n split copies: the ordered sum rides on the filter gradients' reduce
+                self._pending_unpack.append((bp[0].view(1, 1, s.cout), bias_dst.view(1, s.cout, 1), scale, n, s.cout))
         else:
             dwp = self._arena_take(s.cout * s.taps * cin_p, x.device)
             run = lambda: ops.conv_wgrad(d, x, g, dwp)  # noqa: E731
@@ -473,6 +493,7 @@ class ProgramBase:
             self.launch_probe("wgrad:" + s.name, run)
         else:
             run()
+        return fused
 
     def wgrad_dense(self, convs: Sequence[ConvSite], buf: Tensor, gd: Tensor, flat: Tensor, space: GradSpace,
                     scratch: Tensor) -> None:
@@ -634,14 +655,28 @@ class ProgramBase:
         n = int(self._scratch_elems_total * 1.3) + 4096
         self._arena = torch.zeros(n, dtype=torch.float32, device=dev)
 
-    def _wgrad_nparts(self, key, desc, tri_base: int = 0, tri_step: int = 0) -> int:
+    def _wgrad_nparts(self, key, desc, tri_base: int = 0, tri_step: int = 0, bias: bool = False) -> int:
         if self._env_gen != ops.ENV_GEN[0]:  # the tuning switches were re-read: plans and job tables start over
             self._nparts.clear()
             self._unpack_tables.clear()
             self._env_gen = ops.ENV_GEN[0]
         n = self._nparts.get(key)
         if n is None:
-            n = self._nparts[key] = ops.conv_wgrad_nparts(desc, tri_base, tri_step)
+            n = self._nparts[key] = (ops.conv_wgrad_nparts_bias(desc) if bias
+                                     else ops.conv_wgrad_nparts(desc, tri_base, tri_step))
+        return n
+
+    def _wgrad_nparts_lat4(self, key, desc) -> int:
+        """splits per class of the merged four-class launch, 0: declined (or switched off) - one launch per class"""
+        if not WGRAD_LAT4:
+            return 0
+        if self._env_gen != ops.ENV_GEN[0]:
+            self._nparts.clear()
+            self._unpack_tables.clear()
+            self._env_gen = ops.ENV_GEN[0]
+        n = self._nparts.get(key)
+        if n is None:
+            n = self._nparts[key] = ops.conv_wgrad_nparts_lat4(desc)
         return n
 
     def _arena_reserve(self, n_total: int, dev) -> None:
@@ -939,7 +974,19 @@ class GeneratorProgram(ProgramBase):
         runs = []
         descs = [ops.make_desc(ConvGeom(site.cin, site.cout, s.kernel, (1, 1, 1), s.pad), self.dt, B, xyz, inp.shape[-1],
                                0, g.shape[-1], 0, cin=cin_p, lat=(ph >> 1, ph & 1, 0)) for ph, s in enumerate(par)]
-        if DETERMINISTIC:  # (the launches below are deferred: no recycling flush between the slices)
+        n4 = 0
+        if DETERMINISTIC and len({(s.kernel, s.pad[2]) for s in par}) == 1:  # all four classes in one launch
+            d4 = ops.make_desc(ConvGeom(site.cin, site.cout, par[0].kernel, (1, 1, 1), par[0].pad), self.dt, B, xyz,
+                               inp.shape[-1], 0, g.shape[-1], 0, cin=cin_p, lat=(0, 0, 4))
+            n4 = self._wgrad_nparts_lat4(("wpar4", site.name, B) + xyz, d4)
+        if n4 > 0:
+            one = site.cout * par[0].taps * cin_p
+            parts = self._arena_take(4 * n4 * one, inp.device).view(4, n4, site.cout, par[0].taps, cin_p)
+            runs.append(lambda: ops.conv_wgrad_parts_lat4(d4, inp, g, parts, n4))
+            for ph in range(4):
+                self._pending_unpack.append((parts[ph, 0], dwp[ph], 1.0, n4, one))
+            par = ()
+        elif DETERMINISTIC:  # (the launches below are deferred: no recycling flush between the slices)
             self._arena_reserve(sum((self._wgrad_nparts(("wpar", site.name, ph, B) + xyz, d) * site.cout * s.taps * cin_p
                                      + 63) // 64 * 64 for ph, (s, d) in enumerate(zip(par, descs))), inp.device)
         for ph, s in enumerate(par):
@@ -1329,13 +1376,14 @@ class GeneratorProgram(ProgramBase):
                     first, lastb = j == 0, j == nb - 1
                     go = cur if first else oth               # the block's output gradient sits in go[..., :nf]
                     sc = rdb_scale * (rr_scale if first else 1.0)
-                    self.wgrad(lff, buf, 0, go, 0, flat, sp, scratch, scale=sc)
-                    rows = ops.chan_sum_rows(nf, go.numel() // go.shape[-1])
-                    if not rows:
-                        raise RuntimeError("LFF bias gradient outside the two-pass sum (set WSR_GD_PINGPONG=0)")
-                    pr = self._arena_take(rows * nf, dev).view(rows, nf)
-                    ops.chan_sum_partials(go, 0, nf, pr)
-                    self._pending_unpack.append((pr[0].view(1, 1, nf), sp.view(flat, lff.bias).view(1, nf, 1), sc, rows, nf))
+                    if not self.wgrad(lff, buf, 0, go, 0, flat, sp, scratch, scale=sc, bias_dst=sp.view(flat, lff.bias)):
+                        rows = ops.chan_sum_rows(nf, go.numel() // go.shape[-1])
+                        if not rows:
+                            raise RuntimeError("LFF bias gradient outside the two-pass sum (set WSR_GD_PINGPONG=0)")
+                        pr = self._arena_take(rows * nf, dev).view(rows, nf)
+                        ops.chan_sum_partials(go, 0, nf, pr)
+                        self._pending_unpack.append((pr[0].view(1, 1, nf), sp.view(flat, lff.bias).view(1, nf, 1), sc, rows,
+                                                     nf))
                     nc = len(convs)
                     last = nf + (nc - 1) * gc
                     self.dgrad(lff, go, 0, oth, 0, (X, Y, nz), alpha=sc, accumulate=nf, acc_src=go if first else None,
@@ -1415,10 +1463,12 @@ class GeneratorProgram(ProgramBase):
                 buf = bufs[bi]
                 tr("rdb_go", bi, go[..., :nf])
                 # LFF (1x1x1, bias): out = rdb_scale * (LFF(buf) + b) + x
-                self.wgrad(lff, buf, 0, go, 0, flat, sp, scratch, scale=rdb_scale)
                 gb = sp.view(flat, lff.bias)
-                rows = ops.chan_sum_rows(nf, go.numel() // go.shape[-1]) if DETERMINISTIC else 0
-                if rows:
+                fused = self.wgrad(lff, buf, 0, go, 0, flat, sp, scratch, scale=rdb_scale, bias_dst=gb)
+                rows = ops.chan_sum_rows(nf, go.numel() // go.shape[-1]) if DETERMINISTIC and not fused else 0
+                if fused:
+                    pass  # (the filter-gradient launch took the sums: nothing reads go a second time)
+                elif rows:
                     # first pass now (go is overwritten below), the sum over the partial rows rides on the ordered
                     # reduce of the filter gradients: a job with one output row and `rows` split copies
                     pr = self._arena_take(rows * nf, dev).view(rows, nf)
@@ -1625,6 +1675,14 @@ class DiscriminatorProgram(ProgramBase):
             for zc in range(sz):
                 kzp = 3 if sz == 1 else (1 if zc == 0 else 2)
                 pz, mz, oz = (1, 1, 0) if sz == 1 else ((0, 2, 0) if zc == 0 else (1, 2, 1))
+                # the four xy classes of this z-class in one launch (None in place of the class: all of them)
+                g = ConvGeom(s.cin, s.cout, (2, 2, kzp), (1, 1, 1), (1, 1, pz))
+                d = ops.make_desc(g, self.dt, B, oxyz, inp.shape[-1], 0, gy.shape[-1], 0, cin=cin_p,
+                                  lat=(0, 0, 4, mz, oz, True))
+                n4 = self._wgrad_nparts_lat4(("wstr4", s.name, zc, B) + oxyz, d)
+                if n4 > 0:
+                    jobs.append((zc, None, g, d, n4))
+                    continue
                 for ph in range(4):
                     a_, b_ = ph >> 1, ph & 1
                     g = ConvGeom(s.cin, s.cout, (2, 2, kzp), (1, 1, 1), (1 - a_, 1 - b_, pz))
@@ -1637,8 +1695,16 @@ class DiscriminatorProgram(ProgramBase):
             self._dparity_bad.add(bad_key)
             return False
         # (the launches are deferred: no recycling flush between the slices)
-        self._arena_reserve(sum((n * s.cout * g.taps * cin_p + 63) // 64 * 64 for _, _, g, _, n in jobs), inp.device)
+        self._arena_reserve(sum(((1 if ph is not None else 4) * n * s.cout * g.taps * cin_p + 63) // 64 * 64
+                                for _, ph, g, _, n in jobs), inp.device)
         for zc, ph, g, d, n in jobs:
+            if ph is None:
+                one = s.cout * g.taps * cin_p
+                parts = self._arena_take(4 * n * one, inp.device).view(4, n, s.cout, g.taps, cin_p)
+                runs.append(lambda d=d, parts=parts, n=n: ops.conv_wgrad_parts_lat4(d, inp, gy, parts, n))
+                for c4 in range(4):
+                    self._pending_unpack.append((parts[c4, 0], tw[zc][c4], 1.0, n, one))
+                continue
             parts = self._arena_take(n * s.cout * g.taps * cin_p, inp.device).view(n, s.cout, g.taps, cin_p)
             runs.append(lambda d=d, parts=parts, n=n: ops.conv_wgrad_parts(d, inp, gy, parts, n))
             self._pending_unpack.append((parts[0], tw[zc][ph], 1.0, n, parts[0].numel()))

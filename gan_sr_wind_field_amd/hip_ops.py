@@ -427,6 +427,53 @@ def conv_wgrad_parts(desc: ConvDesc, x: Tensor, dy: Tensor, parts: Tensor, n_par
     return parts
 
 
+def conv_wgrad_nparts_bias(desc: ConvDesc) -> int:
+    """split copies of the 1x1x1 filter-gradient launch that also takes the bias gradient's partial sums
+    (``wsr_conv3d_wgrad_parts_bias``); 0 when the conv is not that kernel's shape (host-side query)"""
+    n = C.c_int32(0)
+    rc = _lib.lib().wsr_conv3d_wgrad_nparts_bias(C.byref(desc), C.byref(n))
+    if rc == _lib.WSR_EUNSUPPORTED:
+        return 0
+    check(rc, "conv3d_wgrad_nparts_bias")
+    return int(n.value)
+
+
+def conv_wgrad_parts_bias(desc: ConvDesc, x: Tensor, dy: Tensor, parts: Tensor, n_parts: int, bias_parts: Tensor) -> Tensor:
+    """:func:`conv_wgrad_parts` of a 1x1x1 conv; split s also stores the channel sums of its share of ``dy`` to row s
+    of ``bias_parts`` (n_parts, Cout) fp32 (added later by a ``wsr_unpack_wgrad_reduce_multi`` job of n_parts rows)"""
+    _need_cuda(x, dy, parts, bias_parts)
+    if parts.dtype != torch.float32 or not parts.is_contiguous() or parts.shape[0] != n_parts:
+        raise ValueError("conv_wgrad_parts_bias wants a contiguous fp32 (n_parts, Cout, taps, Cin) buffer")
+    if (bias_parts.dtype != torch.float32 or not bias_parts.is_contiguous()
+            or tuple(bias_parts.shape) != (n_parts, desc.Cout)):
+        raise ValueError("conv_wgrad_parts_bias wants a contiguous fp32 (n_parts, Cout) bias buffer")
+    check(_lib.lib().wsr_conv3d_wgrad_parts_bias(C.byref(desc), _p(x), _p(dy), _p(parts), parts[0].numel(), n_parts,
+                                                 _p(bias_parts), _stream()), "conv3d_wgrad_parts_bias")
+    return parts
+
+
+def conv_wgrad_nparts_lat4(desc: ConvDesc) -> int:
+    """splits PER CLASS of the merged four-class launch of a lattice-form filter gradient (``desc``: class (0, 0),
+    see ``wsr_conv3d_wgrad_parts_lat4``); 0 when the merged form declines the shape (host-side query)"""
+    n = C.c_int32(0)
+    rc = _lib.lib().wsr_conv3d_wgrad_nparts_lat4(C.byref(desc), C.byref(n))
+    if rc == _lib.WSR_EUNSUPPORTED:
+        return 0
+    check(rc, "conv3d_wgrad_nparts_lat4")
+    return int(n.value)
+
+
+def conv_wgrad_parts_lat4(desc: ConvDesc, x: Tensor, dy: Tensor, parts: Tensor, n_parts: int) -> Tensor:
+    """The four xy-parity classes of one lattice-form filter gradient in one launch: ``parts`` (4, n_parts, Cout,
+    taps, Cin) fp32, class (a, b) at index 2a + b, one partial sum per split of each class (plain stores)."""
+    _need_cuda(x, dy, parts)
+    if parts.dtype != torch.float32 or not parts.is_contiguous() or parts.dim() != 5 or parts.shape[:2] != (4, n_parts):
+        raise ValueError("conv_wgrad_parts_lat4 wants a contiguous fp32 (4, n_parts, Cout, taps, Cin) buffer")
+    check(_lib.lib().wsr_conv3d_wgrad_parts_lat4(C.byref(desc), _p(x), _p(dy), _p(parts), parts[0, 0].numel(),
+                                                 parts[0].numel(), n_parts, _stream()), "conv3d_wgrad_parts_lat4")
+    return parts
+
+
 def pack_filter(w: Tensor, dt: torch.dtype, *, transpose: bool = False, kpad: Optional[int] = None,
                 out: Optional[Tensor] = None) -> Tensor:
     """fp32 master ``(Cout, Cin, KX, KY, KZ)`` -> compute copy ``[rows][taps][kpad]`` of ``dt``."""

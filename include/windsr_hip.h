@@ -273,6 +273,26 @@ int wsr_conv3d_wgrad_parts(const wsr_conv_t* c, const void* x, const void* dy, f
  * lattice (WSR_EUNSUPPORTED otherwise).                                                                        */
 int wsr_conv3d_wgrad_parts_x2(const wsr_conv_t* c, const void* x, const void* x2, int32_t x2_ctot, int32_t x2_c0,
                               const void* dy, float* parts, int64_t part_stride, int32_t n_parts, void* stream);
+/* The four xy-parity classes of one lattice-form filter gradient in ONE launch (lat = 2: the parity convs of a
+ * sub-pixel up-sampling conv; lat = 3: one z-class of a strided conv in parity form; the classes share the tap
+ * shape).  `c` describes class (0, 0): lat_ox = lat_oy = 0, (px, py) >= 1 its low pads ((1, 1) for lat = 3),
+ * lat_phases 0 or 4.  Class (a, b) runs exactly as wsr_conv3d_wgrad_parts would with low pads (px - a, py - b) and
+ * lattice offsets (a, b) (lat = 2) or (px - a, py - b) (lat = 3), and split s of it STORES its sums to
+ * parts + (2a + b)*class_stride + s*part_stride.  n_parts = splits PER CLASS as wsr_conv3d_wgrad_nparts_lat4
+ * reports them; a per-class launch with the same number of splits gives the same bits.  WSR_EUNSUPPORTED: the
+ * shape does not fit the merged form - launch the classes one by one.                                           */
+int wsr_conv3d_wgrad_nparts_lat4(const wsr_conv_t* c, int32_t* n_parts);
+int wsr_conv3d_wgrad_parts_lat4(const wsr_conv_t* c, const void* x, const void* dy, float* parts, int64_t part_stride,
+                                int64_t class_stride, int32_t n_parts, void* stream);
+/* wsr_conv3d_wgrad_parts for a 1x1x1 conv with a bias (the generator's LFF convs), the bias gradient's partial sums
+ * taken in the same launch: split s also STORES sum_v dy[v, n] to bias_parts[s*Cout + n] (n_parts rows of Cout
+ * floats; wsr_unpack_wgrad_reduce_multi adds the rows in order as a job of one output row).  The filter gradient is
+ * wsr_conv3d_wgrad_parts' bit for bit.  n_parts as wsr_conv3d_wgrad_nparts_bias reports it (the same number as
+ * wsr_conv3d_wgrad_nparts); WSR_EUNSUPPORTED from either: not the bf16 1x1x1 tile kernel's shape (Cout, Cin >= 64,
+ * stride 1, no lattice) - use wsr_conv3d_wgrad_parts and wsr_chan_sum_partials.                                    */
+int wsr_conv3d_wgrad_nparts_bias(const wsr_conv_t* c, int32_t* n_parts);
+int wsr_conv3d_wgrad_parts_bias(const wsr_conv_t* c, const void* x, const void* dy, float* parts, int64_t part_stride,
+                                int32_t n_parts, float* bias_parts, void* stream);
 /* Filter gradients of ALL growth convs of a residual dense block in one launch
  * (torch_blocks.py:256-267: conv i reads channels [0, tri_base + i*tri_step) of the
  * dense buffer and writes tri_step channels).  c describes the stacked conv: Cin =
