@@ -796,6 +796,25 @@ class wind_field_GAN_3D(BaseGAN):
         return _level_sums("level_fss", level_fss_reference, self.cfg.scale, HR, SR, LR, (),
                            (fss_tables(UVW_MAX, thresholds), tuple(fc.scales)))
 
+    # ------------------------------------------------------------------ hub-height wind resource ([HUB_HEIGHT])
+    def hub_height(self, HR, SR, LR, Z, terrain, UVW_MAX, with_columns: bool = False):
+        """The 18 sums of ``hub_height.py`` per sample and height above ground of a batch -> float64 (B, NH, 18) on the
+        tensors' device, with ``with_columns`` followed by the planes (B, NH, 7, X, Y); heights, interpolation and power
+        curve of ``[HUB_HEIGHT]`` (without the section: 50, 100 and 150 m and its defaults) and ``UVW_MAX`` to
+        denormalise.  ``Z`` is the raw altitude (B, 1, X, Y, NZ), ``terrain`` the ground altitude (X, Y).  The trilinear
+        baseline of ``LR`` is built here (``wsr_trilinear_xy`` on a GPU, ``F.interpolate`` on a CPU), the sums come from
+        ``hip_ops.hub_height`` on a GPU and from ``hub_height.hub_height_reference`` on a CPU.  Reads no weights: the
+        same inside ``ema_scope()``."""
+        from ..config.config import HubHeightConfig, default_power_curve
+        from ..hub_height import hub_height_reference, hub_height_tables
+
+        hc = getattr(self.cfg, "hub_height", None) or HubHeightConfig
+        heights = hc.heights if hc.heights is not None else [50.0, 100.0, 150.0]
+        speeds, power = (hc.curve_speeds, hc.curve_power) if hc.curve_speeds is not None else default_power_curve()
+        tables = hub_height_tables(UVW_MAX, heights, speeds, power)
+        return _level_sums("hub_height", hub_height_reference, self.cfg.scale, HR, SR, LR,
+                           (Z, terrain.to(HR.device)), (tables, hc.interp, with_columns))
+
     def make_new_labels(self, it):
         """Real / fake label vectors of this iteration (reference :627-678)."""
         t = self.cfg.training

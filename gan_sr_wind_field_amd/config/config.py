@@ -53,6 +53,10 @@ Extension (optional keys, defaults keep reference behaviour):
   [FSS] thresholds / scales / per_level
             --test also writes the fractions skill score of network and baseline against the truth per wind-speed
             threshold and neighbourhood size, the useful scale and the contingency-table scores (fss.py, csrc/fss.hip)
+  [HUB_HEIGHT] heights / interp / air_density / curve_speeds / curve_power / per_field / write_maps
+            --test also writes the wind speed, the wind power density and a turbine's capacity factor at fixed heights
+            above ground for the truth, the network and the baseline
+            (hub_height.py, csrc/hub_height.hip)
 """
 from __future__ import annotations
 
@@ -763,6 +767,63 @@ class FssConfig(OptionalSection):
         return bool(self.present)
 
 
+def default_power_curve():
+    """The default of [HUB_HEIGHT] curve_speeds / curve_power: 0 at 3 m/s, (v^3 - 27) / (1728 - 27) at 4 .. 12 m/s, 1 at
+    12 and at 25 m/s, 0 at 26 m/s -> (speeds, power)"""
+    speeds = [3.0] + [float(v) for v in range(4, 13)] + [25.0, 26.0]
+    power = [0.0] + [(v ** 3 - 27.0) / (1728.0 - 27.0) for v in range(4, 13)] + [1.0, 0.0]
+    return speeds, power
+
+
+class HubHeightConfig(OptionalSection):
+    """[HUB_HEIGHT] (extension): the wind speed, the wind power density and a turbine's capacity factor at fixed heights
+    above ground for HR, SR and the trilinear baseline in ``run.py --test`` (hub_height.py, csrc/hub_height.hip); absent
+    section = off, and never printed by ``asINI``.  ``heights``: 1 .. 8 heights in metres above ground, each > 0,
+    strictly ascending, required; ``interp``: ``linear`` (in height) or ``log`` (in ln height); ``air_density`` > 0 in
+    kg/m^3; ``curve_speeds`` / ``curve_power``: the power curve, 2 .. 32 knots, speeds in m/s >= 0 and strictly
+    ascending, power a fraction of rated in [0, 1], piecewise linear with the end values outside (default:
+    ``default_power_curve``); ``per_field``: ``--test`` also writes ``<name>____hub_height_fields.csv``; ``write_maps``:
+    ``--test`` also writes ``<name>____hub_height_maps.npz``."""
+
+    heights: Optional[list] = None
+    interp: str = "log"
+    air_density: float = 1.225
+    curve_speeds: Optional[list] = None
+    curve_power: Optional[list] = None
+    per_field: bool = False
+    write_maps: bool = False
+    _section, _printed = "HUB_HEIGHT", False
+    _schema = (("heights", _L), ("interp", _W), ("air_density", _F), ("curve_speeds", _L), ("curve_power", _L),
+               ("per_field", _B), ("write_maps", _B))
+
+    def load(self, section) -> None:
+        super().load(section)
+        if self.curve_speeds is None and self.curve_power is None:
+            self.curve_speeds, self.curve_power = default_power_curve()
+
+    setHubHeightConfig = load
+
+    def validate(self) -> None:
+        if not self.present:
+            return
+        from ..hub_height import check_curve, check_heights, check_interp
+        if self.heights is None:
+            raise ValueError("[HUB_HEIGHT] heights must be given (a list of heights in metres above ground): it has no "
+                             "default")
+        self.heights = check_heights(self.heights, "[HUB_HEIGHT]")
+        check_interp(self.interp, "[HUB_HEIGHT]")
+        if not (self.air_density > 0 and math.isfinite(self.air_density)):
+            raise ValueError(f"[HUB_HEIGHT] air_density must be a finite number > 0, not {self.air_density}")
+        if self.curve_speeds is None or self.curve_power is None:
+            raise ValueError("[HUB_HEIGHT] curve_speeds and curve_power must be given together")
+        self.curve_speeds, self.curve_power = check_curve(self.curve_speeds, self.curve_power, "[HUB_HEIGHT]")
+
+    @property
+    def on(self) -> bool:
+        """``--test`` takes the hub-height sums and writes the hub-height files"""
+        return bool(self.present)
+
+
 class Config(IniConfig):
     name: str = "default_name"
     model: str = "default_model"
@@ -797,6 +858,7 @@ class Config(IniConfig):
     ssim: SsimConfig = SsimConfig()
     distribution: DistributionConfig = DistributionConfig()
     fss: FssConfig = FssConfig()
+    hub_height: HubHeightConfig = HubHeightConfig()
     ssim_loss: SsimLossConfig = SsimLossConfig()
     compute_dtype: str = "fp32"
     is_train: bool
@@ -812,7 +874,7 @@ class Config(IniConfig):
                  ("diagnostics", None), ("spectrum", None), ("spectral_loss", None),
                  ("degradation", lambda c: c.scale), ("ssim", None))
     # (the sections above are a pinned list; later extensions load and print behind them, by the same rules)
-    _optional_later = (("distribution", None), ("ssim_loss", None), ("fss", None))
+    _optional_later = (("distribution", None), ("ssim_loss", None), ("fss", None), ("hub_height", None))
 
     def __init__(self, ini_path):
         parser = ConfigParser(allow_no_value=True)

@@ -1739,3 +1739,71 @@ def level_fss(HR: Tensor, SR: Tensor, TL: Optional[Tensor], tables, scales=(1, 3
     check(L.wsr_level_fss(_p(HR), HR.shape[1], _p(SR), SR.shape[1], _p(TL), 0 if TL is None else TL.shape[1], _p(thr2), nt,
                           (C.c_int32 * nn)(*sc), nn, B, X, Y, NZ, _p(out), _p(ws), _stream()), "level_fss")
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# hub-height wind resource ([HUB_HEIGHT]; csrc/hub_height.hip)
+# ---------------------------------------------------------------------------------------------------------------------
+HUB_HEIGHT_BLOCK = 256  # HH_BLOCK of csrc/hub_height_kernels.h
+_hub_height_tables: dict = {}
+
+
+def hub_height_columns_per_chunk(NZ: int, nh: int) -> int:
+    """The consecutive columns one workgroup of ``wsr_hub_height`` stages at a time (``hh_geom`` of
+    csrc/hub_height_kernels.h)"""
+    return min(HUB_HEIGHT_BLOCK // int(NZ), HUB_HEIGHT_BLOCK // int(nh))
+
+
+def _hub_height_arrays(device, tables):
+    """The heights and the curve of a ``hub_height.HubHeightTables`` as the float arrays the entry reads during the call
+    (they travel as kernel arguments): built once per (device, parameters)"""
+    key = (device.index, tables.UVW_MAX, tuple(tables.heights_m), tuple(tables.curve_speeds), tuple(tables.curve_power))
+    a = _hub_height_tables.get(key)
+    if a is None:
+        if len(_hub_height_tables) > 64:
+            _hub_height_tables.clear()
+        a = _hub_height_tables[key] = tuple((C.c_float * t.numel())(*t.float().tolist())
+                                            for t in (tables.heights, tables.curve_v, tables.curve_p))
+    return a
+
+
+def hub_height(HR: Tensor, SR: Tensor, TL: Optional[Tensor], Z: Tensor, terrain: Tensor, tables, interp: str,
+               with_columns: bool = False, out: Optional[Tensor] = None):
+    """The 18 sums of ``hub_height.py`` per sample and height above ground -> float64 (B, NH, 18): every column of
+    ``HR``, ``SR`` and the baseline ``TL`` (B, C >= 3, X, Y, NZ; channels 0 and 1 are read) interpolated from its levels
+    ``Z`` (B, 1, X, Y, NZ; raw altitude, ascending) above the ground ``terrain`` (X, Y) to the heights of ``tables`` =
+    ``hub_height.hub_height_tables(...)``, ``interp`` ``linear`` or ``log``; sums over the columns the height lies
+    inside.  ``TL`` None: zeros in its sums.  ``with_columns``: also the planes (B, NH, 7, X, Y) fp32 - V and P of HR,
+    SR and TL and the validity - as a second result.  One pass, no atomics: the same bits on every call.  ``out``: a
+    float64 (B, NH, 18) slice to write into (``wsr_hub_height``)."""
+    from . import hub_height as hh
+
+    _need_cuda(HR, SR, TL, Z, terrain, out)
+    B, X, Y, NZ = _same_grid("hub_height", HR, SR=SR, **({} if TL is None else {"TL": TL}))
+    _planar5("hub_height", "Z", Z)
+    if tuple(Z.shape) != (B, 1, X, Y, NZ):
+        raise ValueError(f"hub_height wants the levels Z as ({B}, 1, {X}, {Y}, {NZ}), got {tuple(Z.shape)}")
+    if terrain.dtype != torch.float32 or tuple(terrain.shape) != (X, Y) or not terrain.is_contiguous():
+        raise ValueError(f"hub_height wants terrain as a contiguous fp32 ({X}, {Y}) tensor, got {terrain.dtype} "
+                         f"{tuple(terrain.shape)}")
+    hh.check_interp(interp, "hub_height")
+    hs = hh.check_heights(tables.heights_m, "hub_height")
+    cs, _ = hh.check_curve(tables.curve_speeds, tables.curve_power, "hub_height")
+    nh, nk = len(hs), len(cs)
+    if tables.heights.numel() != nh or tables.curve_v.numel() != nk or tables.curve_p.numel() != nk:
+        raise ValueError(f"hub_height wants tables of {nh} heights and {nk} knots, got {tables.heights.numel()}, "
+                         f"{tables.curve_v.numel()} and {tables.curve_p.numel()}")
+    if not 2 <= NZ <= hh.MAX_NZ:
+        raise ValueError(f"hub_height stages whole columns in LDS: 2 .. {hh.MAX_NZ} levels, not {NZ}")
+    if B > 65535 or X > 32768 or Y > 32768 or X * Y * NZ >= 2 ** 31:
+        raise ValueError(f"hub_height: at most 65535 samples, 32768 rows and columns and 2^31 - 1 voxels per sample, not "
+                         f"B = {B}, X = {X}, Y = {Y}, NZ = {NZ}")
+    out = _sums_out("hub_height", out, (B, nh, hh.NS), HR.device)
+    cols = torch.empty((B, nh, hh.PLANES, X, Y), dtype=torch.float32, device=HR.device) if with_columns else None
+    L = _lib.lib()
+    heights, curve_v, curve_p = _hub_height_arrays(HR.device, tables)
+    ws = _workspace(L.wsr_hub_height_workspace_floats(B, X, Y, NZ, nh), HR.device)
+    check(L.wsr_hub_height(_p(HR), HR.shape[1], _p(SR), SR.shape[1], _p(TL), 0 if TL is None else TL.shape[1], _p(Z),
+                           _p(terrain), heights, nh, curve_v, curve_p, nk, int(interp == "log"), B, X, Y, NZ, _p(ws),
+                           _p(out), _p(cols), _stream()), "hub_height")
+    return (out, cols) if with_columns else out

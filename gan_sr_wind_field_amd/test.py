@@ -94,6 +94,22 @@ the host tensors - and write
     ./test_output/<cfg.name>____fss_reverse_interpolate.csv       (+ ``..._exceedance_reverse_interpolate.csv``,
         ``..._fss_levels_reverse_interpolate.csv``) with ``reverse_interpolate``: the same on the raw truth and the
         re-levelled SR and baseline
+
+With a ``[HUB_HEIGHT]`` section both loops also add the 18 sums per height above ground of every batch
+(``hub_height.py``) into one (NH, 18) table - the device loop with ONE ``hip_ops.hub_height`` launch per batch on the stored
+baseline, the raw altitude of the batch and the ground altitude of the test domain (uploaded once), its table a device
+tensor read once after the last batch; the host loop with ``hub_height.hub_height_reference`` on the host tensors - and
+write
+    ./test_output/<cfg.name>____hub_height.csv                    one row of ``HUB_COLUMNS`` per height
+    ./test_output/<cfg.name>____hub_height_fields.csv             (``per_field``) one row ``field,`` + ``HUB_COLUMNS`` per
+                                                                   field and height
+    ./test_output/averages_hub_height.csv                         one appended row ``Name,`` + ``HUB_COLUMNS`` per height
+    ./test_output/<cfg.name>____hub_height_maps.npz               (``write_maps``) ``heights`` (NH,), ``x``, ``y``,
+        ``valid_fraction`` (NH, X, Y), ``speed`` (NH, 3, X, Y) in m/s and ``capacity_factor`` (NH, 3, X, Y) of HR, SR and
+        the baseline: means over the fields in which the column was valid, nan where it never was
+    ./test_output/<cfg.name>____hub_height_reverse_interpolate.csv   (+ ``..._fields_reverse_interpolate.csv``,
+        ``averages_hub_height_reverse_interpolate.csv``, ``..._maps_reverse_interpolate.npz``) with
+        ``reverse_interpolate``: the same on the raw truth, the re-levelled SR and baseline and the raw altitudes
 """
 from __future__ import annotations
 
@@ -113,6 +129,8 @@ from .diagnostics import PROFILE_COLUMNS, level_sums_reference, profile_from_sum
 from .distribution import (ROSE_COLUMNS, SPEED_COLUMNS, SUMMARY_COLUMNS, distribution_from_counts, distribution_tables,
                            level_distribution_reference)
 from .fss import EXCEEDANCE_COLUMNS, FSS_COLUMNS, fss_from_sums, fss_tables, level_fss_reference
+from .hub_height import COLUMNS as HUB_COLUMNS
+from .hub_height import hub_height_from_sums, hub_height_reference, hub_height_tables
 from .process_data import reverse_interpolate_z_axis
 from .ssim import SSIM_COLUMNS, columns_from_sums, level_ssim_reference, n_positions
 from .spectra import SPECTRUM_COLUMNS, grid_spacing, level_spectra_reference, mode_counts, spectrum_from_sums
@@ -455,6 +473,55 @@ class _Fss(_LevelSums):
                         f.write(f"{lvl}," + ",".join(str(rows[c][row]) for c in first + FSS_COLUMNS) + "\n")
 
 
+class _HubHeight(_LevelSums):
+    """[HUB_HEIGHT]: sums (B, NH, 18), with ``write_maps`` also the planes (B, NH, 7, X, Y); one row per height for the
+    test set, the rows of ``averages_hub_height<suffix>.csv``, with ``per_field`` the rows of every field and with
+    ``write_maps`` the per-column means.  ``xy``: the coordinates of the domain."""
+
+    stem = "hub_height"
+
+    def __init__(self, fn, tables, air_density, per_field, write_maps, xy, *where):
+        def sums(*batch):
+            if not write_maps:
+                return fn(*batch)
+            table, cols = fn(*batch)
+            m = cols.double().sum(dim=0)  # (NH, 7, X, Y), on the device of the sums
+            self.maps = m if self.maps is None else self.maps + m
+            return table
+
+        super().__init__(sums, *where)
+        self.tables, self.air_density, self.write_maps, self.xy, self.maps = tables, air_density, write_maps, xy, None
+        self.averages_path = os.path.join(self.folder, f"averages_hub_height{self.suffix}.csv")
+        _header(self.averages_path, "Name," + ",".join(HUB_COLUMNS))
+        if per_field:
+            self.open_fields("_fields", "field," + ",".join(HUB_COLUMNS))
+
+    def rows(self, table, nfields):
+        col = hub_height_from_sums(table, self.tables, self.air_density, self.shape[0] * self.shape[1] * nfields)
+        return [",".join(str(col[c][k]) for c in HUB_COLUMNS) for k in range(len(col["height_m"]))]
+
+    def write_field(self, name, table):
+        for row in self.rows(table, 1):
+            self.fields.write(f"{name},{row}\n")
+
+    def close(self):
+        super().close()
+        rows = [] if self.total is None else self.rows(self.total.cpu(), self.nfields)  # the ONE read
+        with open(self.path(), "w") as f:
+            f.write(",".join(HUB_COLUMNS) + "\n")
+            f.writelines(row + "\n" for row in rows)
+        with open(self.averages_path, "a") as f:
+            f.writelines(f"{self.name},{row}\n" for row in rows)
+        if self.write_maps and self.maps is not None:
+            m = self.maps.cpu()
+            n = m[:, 6]  # (NH, X, Y): the fields in which the column was valid
+            mean = torch.where(n[:, None] > 0, m[:, :6] / n[:, None].clamp(min=1), torch.full_like(m[:, :6], math.nan))
+            np.savez(os.path.join(self.folder, f"{self.name}____{self.stem}_maps{self.suffix}.npz"),
+                     heights=np.asarray(self.tables.heights_m), x=np.asarray(self.xy[0]), y=np.asarray(self.xy[1]),
+                     valid_fraction=(n / max(self.nfields, 1)).numpy(), speed=(mean[:, :3] * self.tables.UVW_MAX).numpy(),
+                     capacity_factor=mean[:, 3:6].numpy())
+
+
 def _outputs(cfg, gan, uvw, d, suffix, on_device, folder=OUT_DIR):
     """The extra outputs of one set of levels that ``cfg`` asks for, each yielded as soon as its files are open; the
     sums come from ``hip_ops`` with ``on_device`` (the device loop), else from the host references.  ``d``: the mean grid
@@ -488,6 +555,12 @@ def _outputs(cfg, gan, uvw, d, suffix, on_device, folder=OUT_DIR):
         score, thr = hip_ops.level_fss if on_device else level_fss_reference, fss_tables(uvw, fc.thresholds)
         yield _Fss(lambda HR, SR, TL, Z: score(HR, SR, TL, thr, fc.scales), fc.thresholds, fc.scales, d, fc.per_level,
                    *where)
+    if cfg.hub_height.on:
+        hc = cfg.hub_height
+        hub, terrain = (hip_ops.hub_height, gan.terrain) if on_device else (hub_height_reference, gan.terrain.cpu())
+        tab = hub_height_tables(uvw, hc.heights, hc.curve_speeds, hc.curve_power)
+        yield _HubHeight(lambda HR, SR, TL, Z: hub(HR, SR, TL, Z, terrain, tab, hc.interp, hc.write_maps), tab,
+                         hc.air_density, hc.per_field, hc.write_maps, gan.xy, *where)
 
 
 class _LevelSet:
@@ -613,6 +686,9 @@ def test(cfg, dataset_test, reverse_interpolate: bool = False):
     log.info("beginning test")
     if cfg.diagnostics.on:  # (the coordinates of the whole test domain)
         gan.x, gan.y = (torch.from_numpy(np.asarray(v)).float().contiguous().to(dev) for v in (dataset_test.x, dataset_test.y))
+    if cfg.hub_height.on:  # (the ground altitude and the coordinates of the whole test domain; one upload)
+        gan.terrain = torch.from_numpy(np.asarray(dataset_test.terrain)).float().contiguous().to(dev)
+        gan.xy = (np.asarray(dataset_test.x), np.asarray(dataset_test.y))
     d = grid_spacing(np.asarray(dataset_test.x), np.asarray(dataset_test.y)) if cfg.spectrum.on or cfg.fss.on else None
     on_device = cfg.eval.on and torch.device(dev).type == "cuda"
     with contextlib.ExitStack() as stack:  # (an exception in any batch closes every file)

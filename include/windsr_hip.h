@@ -849,6 +849,43 @@ int wsr_level_fss(const float* hr, int32_t hr_c, const float* sr, int32_t sr_c, 
                   const float* thr2, int32_t nt, const int32_t* scales, int32_t nn, int32_t B, int32_t X, int32_t Y,
                   int32_t NZ, double* out, void* workspace, void* stream);
 
+/* ---- hub-height wind resource ([HUB_HEIGHT]; csrc/hub_height.hip) ----------------------------------------------
+ * wsr_hub_height: out (B, nh, 18) doubles, written completely: per sample and height q = heights[k] (metres above
+ * ground) the sums over the VALID columns of the plane.  Sources 0 hr, 1 sr, 2 tl: fp32 planar (B, c, X, Y, NZ),
+ * channels 0 = u and 1 = v read; z: the raw altitude (B, 1, X, Y, NZ), taken as strictly increasing along z (not
+ * checked); terrain: the ground altitude (X, Y).  Per column:
+ *    h_k = z_k - terrain, ONE fp32 subtraction;  valid iff h_0 <= q <= h_{NZ-1} in fp32 (false for a NaN), no h_k is a
+ *    NaN and, with log_mode, h_0 > 0: no extrapolation, an invalid column enters no sum
+ *    j = the largest index with h_j <= q;  j = NZ - 1: the top level's value;  else the weight in double from the fp32
+ *    heights, w = (q - h_j) / (h_{j+1} - h_j), with log_mode ln(q / h_j) / ln(h_{j+1} / h_j), and every component
+ *    f_j + w (f_{j+1} - f_j) in double, rounded once to fp32 (w = 0: the knot's value bit for bit)
+ *    V = sqrtf(u u + v v), nothing contracted;  P = np.interp(V, curve_v, curve_p) (the end values outside) in double,
+ *    rounded once;  angle(a, b) = atan2f(|a_u b_v - a_v b_u|, a_u b_u + a_v b_v), 0 when both arguments are 0
+ *    [0] n_valid   [1..3] sum V of hr, sr, tl   [4, 5] sum |V_s - V_hr|, s = sr, tl   [6, 7] sum (V_s - V_hr)^2
+ *    [8..10] sum V^3   [11..13] sum P   [14, 15] sum |P_s - P_hr|   [16, 17] sum V_hr angle(hr, s)
+ * tl may be NULL: its sums are written as zeros.  cols may be NULL; else (B, nh, 7, X, Y) fp32, every element written
+ * exactly once: planes 0..2 V of hr, sr, tl, 3..5 P of hr, sr, tl (zeros for an invalid column and for an absent tl),
+ * 6 validity as 1.0 / 0.0.  heights (nh floats), curve_v and curve_p (nk floats, speeds in the fields' normalised
+ * units): HOST arrays, read during the call and passed to the kernel as arguments.  A workgroup stages runs of
+ * consecutive columns in LDS with coalesced loads, a thread owns (column, height) pairs, bisects once per pair and
+ * keeps fp32 partial sums; one partial row per workgroup, added in a fixed order in double: no atomics, the same bits
+ * on every call, n_valid an exact integer.
+ * workspace: wsr_hub_height_workspace_floats(B, X, Y, NZ, nh) floats (0 for arguments the entry refuses).  A null
+ * pointer (but tl and cols), a channel count < 3, nh outside 1 .. 8, nk outside 2 .. 32, heights not > 0 and strictly
+ * ascending, curve_v not >= 0 and strictly ascending, log_mode not 0 or 1, B, X or Y < 1, NZ < 2: WSR_EINVAL;
+ * NZ > 128, B > 65535, X or Y > 32768, X * Y * NZ >= 2^31: WSR_EUNSUPPORTED; nothing is written in either case. */
+#define WSR_HUB_HEIGHT_SUMS 18
+#define WSR_HUB_HEIGHT_PLANES 7
+#define WSR_HUB_HEIGHT_MAX_HEIGHTS 8
+#define WSR_HUB_HEIGHT_MAX_KNOTS 32
+#define WSR_HUB_HEIGHT_MAX_NZ 128
+#define WSR_HUB_HEIGHT_MAX_ROWS 2048
+int64_t wsr_hub_height_workspace_floats(int32_t B, int32_t X, int32_t Y, int32_t NZ, int32_t nh);
+int wsr_hub_height(const float* hr, int32_t hr_c, const float* sr, int32_t sr_c, const float* tl, int32_t tl_c,
+                   const float* z, const float* terrain, const float* heights, int32_t nh, const float* curve_v,
+                   const float* curve_p, int32_t nk, int32_t log_mode, int32_t B, int32_t X, int32_t Y, int32_t NZ,
+                   float* workspace, double* out, float* cols, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
