@@ -73,6 +73,10 @@ class wind_field_GAN_3D(BaseGAN):
         if self._ssim_loss_on():  # ([SSIM_LOSS]: likewise, behind ``spectral`` when both sections are present)
             self.train_G_loss_dict["ssim"] = torch.zeros(1)
             self.validation_G_loss_dict["ssim"] = torch.zeros(1)
+        if self._distribution_loss_on():  # ([DISTRIBUTION_LOSS]: likewise, the last of the three)
+            self.train_G_loss_dict["distribution"] = torch.zeros(1)
+            self.validation_G_loss_dict["distribution"] = torch.zeros(1)
+        self._wind_scale = None  # UVW_MAX of the training data (set_wind_scale): what [DISTRIBUTION_LOSS] needs
         self.D_loss_dict = _zeros_dict(("train_loss", "validation_loss"))
         self.hist_dict = {
             "val_grad_G_first_layer": torch.zeros(1), "val_grad_G_last_layer": torch.zeros(1),
@@ -339,6 +343,27 @@ class wind_field_GAN_3D(BaseGAN):
         """``[SSIM_LOSS]`` is in the configuration: the generator loss carries the SSIM term"""
         return bool(getattr(getattr(self.cfg, "ssim_loss", None), "on", False))
 
+    def _distribution_loss_on(self) -> bool:
+        """``[DISTRIBUTION_LOSS]`` is in the configuration: the generator loss carries the speed-distribution term"""
+        return bool(getattr(getattr(self.cfg, "distribution_loss", None), "on", False))
+
+    def set_wind_scale(self, UVW_MAX) -> None:
+        """The scale of the normalised wind components in m/s (``dataset_train.UVW_MAX``): ``[DISTRIBUTION_LOSS]`` bins
+        the speed in m/s.  Without the section the value is kept and never read."""
+        self._wind_scale = float(UVW_MAX)
+
+    def _distribution_tables(self):
+        """``distribution_loss.soft_tables`` of the section at the wind scale: built once per (device, scale)"""
+        if self._wind_scale is None:
+            raise ValueError("[DISTRIBUTION_LOSS] needs the scale of the wind components: call "
+                             "gan.set_wind_scale(dataset_train.UVW_MAX) before the first batch")
+        sec = self.cfg.distribution_loss
+        key = (str(self.device), self._wind_scale, sec.bin_width, sec.speed_bins)
+        if getattr(self, "_dist_tables", (None,))[0] != key:
+            from ..distribution_loss import soft_tables
+            self._dist_tables = (key, soft_tables(self._wind_scale, sec.bin_width, sec.speed_bins))
+        return self._dist_tables[1]
+
     def log_G_losses(self, fake_HR, losses: dict, training_iteration: bool):
         target = self.train_G_loss_dict if training_iteration else self.validation_G_loss_dict
         for k in _G_LOSS_KEYS:
@@ -347,6 +372,8 @@ class wind_field_GAN_3D(BaseGAN):
             target["spectral"] = losses["spectral"]
         if "ssim" in losses:
             target["ssim"] = losses["ssim"]
+        if "distribution" in losses:
+            target["distribution"] = losses["distribution"]
         if not training_iteration:
             self.metrics_dict["pix_loss_unscaled"] = losses["pix"] / self.cfg.training.pixel_loss_weight
             self.hist_dict["SR_pix_distribution"] = fake_HR.detach().cpu().numpy()
@@ -399,6 +426,13 @@ class wind_field_GAN_3D(BaseGAN):
             from ..ssim_loss import ssim_loss
             ssim_term = ssim_loss(HR, fake_HR, self.cfg.ssim_loss)
             wkey = wkey + (self.cfg.ssim_loss.weight,)
+        # [DISTRIBUTION_LOSS]: the speed-distribution term (distribution_loss.py), by the same rules: the next entry of the
+        # core vector, after ``ssim``; a non-finite SR makes it NaN on the device and the Adam step is skipped
+        dist_term = None
+        if self._distribution_loss_on():
+            from ..distribution_loss import distribution_loss
+            dist_term = distribution_loss(HR, fake_HR, self.cfg.distribution_loss, self._distribution_tables())
+            wkey = wkey + (self.cfg.distribution_loss.weight,)
         if getattr(self, "_loss_w", (None,))[0] != wkey:
             self._loss_w = (wkey, torch.tensor([float(v) for v in wkey[1:]], dtype=torch.float32).to(self.device))
         L = {}
@@ -411,7 +445,7 @@ class wind_field_GAN_3D(BaseGAN):
             Lp = torch.stack([v.reshape(()) for v in unweighted[3:]]) * wv[3:7]
             L.update(zip(keys, Lc.unbind() + Lp.unbind()))
             at = 7
-            for name, extra in (("spectral", spec), ("ssim", ssim_term)):
+            for name, extra in (("spectral", spec), ("ssim", ssim_term), ("distribution", dist_term)):
                 if extra is not None:
                     Ls = extra.reshape(1) * wv[at:at + 1]
                     L[name] = Ls.reshape(())

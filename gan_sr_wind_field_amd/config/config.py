@@ -57,6 +57,10 @@ Extension (optional keys, defaults keep reference behaviour):
             --test also writes the wind speed, the wind power density and a turbine's capacity factor at fixed heights
             above ground for the truth, the network and the baseline
             (hub_height.py, csrc/hub_height.hip)
+  [DISTRIBUTION_LOSS] weight / bin_width / speed_bins / pool
+            absent = off; present, the generator loss carries weight * the 1-D Wasserstein distance (m/s) between the
+            soft horizontal-speed histograms of SR and HR (distribution_loss.py, csrc/distribution_loss.hip), logged as
+            ``distribution``
 """
 from __future__ import annotations
 
@@ -824,6 +828,49 @@ class HubHeightConfig(OptionalSection):
         return bool(self.present)
 
 
+class DistributionLossConfig(OptionalSection):
+    """[DISTRIBUTION_LOSS] (extension): a wind-speed distribution term of the generator loss (distribution_loss.py,
+    csrc/distribution_loss.hip); absent section = off, and not printed by ``asINI``.  ``weight`` (required, > 0: there is
+    no reference default to inherit) multiplies ``L_dist``, the mean over the rows of the 1-D Wasserstein distance in m/s
+    between the soft (linearly binned) horizontal-speed histograms of SR and HR; ``bin_width`` > 0: the distance between
+    bin centres in m/s, required; ``speed_bins``: 2 .. 64, the last one open-ended; ``pool``: ``level`` (every sample and
+    z level is a distribution) or ``sample`` (the levels of a sample are summed first).  The keys are independent of
+    ``[DISTRIBUTION]``."""
+
+    weight: float = None
+    bin_width: float = None
+    speed_bins: int = 32
+    pool: str = "level"
+    _section = "DISTRIBUTION_LOSS"
+    _schema = (("weight", _F), ("bin_width", _F), ("speed_bins", _I), ("pool", _W))
+
+    setDistributionLossConfig = OptionalSection.load
+
+    def validate(self) -> None:
+        if not self.present:
+            return
+        from ..distribution import MAX_SPEED_BINS, MIN_SPEED_BINS
+        if self.weight is None:
+            raise ValueError("[DISTRIBUTION_LOSS] weight is required: the weight of the distribution term in the "
+                             "generator loss")
+        if not (self.weight > 0 and math.isfinite(self.weight)):
+            raise ValueError(f"[DISTRIBUTION_LOSS] weight must be a finite number > 0, not {self.weight}")
+        if self.bin_width is None:
+            raise ValueError("[DISTRIBUTION_LOSS] bin_width must be given (m/s, > 0): it has no default")
+        if not (self.bin_width > 0 and math.isfinite(self.bin_width)):
+            raise ValueError(f"[DISTRIBUTION_LOSS] bin_width must be a finite number > 0, not {self.bin_width}")
+        if not MIN_SPEED_BINS <= self.speed_bins <= MAX_SPEED_BINS:
+            raise ValueError(f"[DISTRIBUTION_LOSS] speed_bins must be {MIN_SPEED_BINS} .. {MAX_SPEED_BINS}, not "
+                             f"{self.speed_bins}")
+        if self.pool not in ("level", "sample"):
+            raise ValueError(f"[DISTRIBUTION_LOSS] pool must be level or sample, not {self.pool!r}")
+
+    @property
+    def on(self) -> bool:
+        """the generator loss carries the distribution term"""
+        return bool(self.present)
+
+
 class Config(IniConfig):
     name: str = "default_name"
     model: str = "default_model"
@@ -860,6 +907,7 @@ class Config(IniConfig):
     fss: FssConfig = FssConfig()
     hub_height: HubHeightConfig = HubHeightConfig()
     ssim_loss: SsimLossConfig = SsimLossConfig()
+    distribution_loss: DistributionLossConfig = DistributionLossConfig()
     compute_dtype: str = "fp32"
     is_train: bool
     is_use: bool
@@ -874,7 +922,8 @@ class Config(IniConfig):
                  ("diagnostics", None), ("spectrum", None), ("spectral_loss", None),
                  ("degradation", lambda c: c.scale), ("ssim", None))
     # (the sections above are a pinned list; later extensions load and print behind them, by the same rules)
-    _optional_later = (("distribution", None), ("ssim_loss", None), ("fss", None), ("hub_height", None))
+    _optional_later = (("distribution", None), ("ssim_loss", None), ("fss", None), ("hub_height", None),
+                       ("distribution_loss", None))
 
     def __init__(self, ini_path):
         parser = ConfigParser(allow_no_value=True)

@@ -1681,6 +1681,76 @@ def level_distribution(HR: Tensor, SR: Tensor, TL: Optional[Tensor], tables, out
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# wind-speed distribution loss of generator training ([DISTRIBUTION_LOSS]; csrc/distribution_loss.hip)
+# ---------------------------------------------------------------------------------------------------------------------
+DISTRIBUTION_LOSS_LDS_COUNTERS = 8320  # WSR_DISTRIBUTION_LOSS_LDS_COUNTERS
+
+
+class _SpeedSoftCounts(torch.autograd.Function):
+    """``wsr_speed_soft_counts`` with ``wsr_speed_soft_counts_bwd`` as backward: H (2, B, NZ, NS + 1), source 0 HR, 1 SR;
+    gradient flows only towards SR, from the NS bin columns of its table.  Nothing is saved but SR: the backward
+    recomputes."""
+
+    @staticmethod
+    def forward(ctx, hr: Tensor, sr: Tensor, c: float, ns: int):
+        B, _, X, Y, NZ = sr.shape
+        L = _lib.lib()
+        out = torch.empty((2, B, NZ, ns + 1), dtype=torch.float64, device=sr.device)
+        ws = _workspace(L.wsr_speed_soft_counts_workspace_floats(B, X, Y, NZ, ns), sr.device)
+        check(L.wsr_speed_soft_counts(_p(hr), hr.shape[1], _p(sr), sr.shape[1], c, ns, B, X, Y, NZ, _p(ws), _p(out),
+                                      _stream()), "speed_soft_counts")
+        ctx.meta = (c, ns)
+        ctx.save_for_backward(sr)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable  # (the kernel's result is no graph: a double backward is refused)
+    def backward(ctx, g: Tensor):
+        if not ctx.needs_input_grad[1]:
+            return None, None, None, None
+        (sr,) = ctx.saved_tensors
+        c, ns = ctx.meta
+        B, C_, X, Y, NZ = sr.shape
+        L = _lib.lib()
+        gtab = g[1, :, :, :ns].to(torch.float32).contiguous()
+        dsr = torch.empty((B, C_, X, Y, NZ), dtype=torch.float32, device=g.device)
+        check(L.wsr_speed_soft_counts_bwd(_p(sr), C_, _p(gtab), c, ns, B, X, Y, NZ, _p(dsr), _stream()),
+              "speed_soft_counts_bwd")
+        return None, dsr, None, None
+
+
+def speed_soft_counts_geometry(B: int, X: int, Y: int, NZ: int, speed_bins: int) -> Tuple[int, int, int, int]:
+    """(columns per workgroup of the counting launch, its column ranges per (sample, source), elements per workgroup of
+    the backward, its element ranges per sample) of ``wsr_speed_soft_counts`` at this shape"""
+    geom = (C.c_int32 * 4)()
+    check(_lib.lib().wsr_speed_soft_counts_geometry(int(B), int(X), int(Y), int(NZ), int(speed_bins), geom),
+          "speed_soft_counts_geometry")
+    return tuple(geom)
+
+
+def speed_soft_counts(HR: Tensor, SR: Tensor, tables) -> Tensor:
+    """The soft (linearly binned) histograms of the horizontal wind speed of ``HR`` and ``SR`` (B, C >= 2, X, Y, NZ;
+    channels 0 and 1 are read, surplus ones never) -> float64 (2, B, NZ, NS + 1), source 0 HR, 1 SR, per sample and z
+    level, under ``tables`` = ``distribution_loss.soft_tables(...)``: the definition of ``distribution_loss.py`` in fixed
+    point, column NS the voxels whose squared speed is not finite, every row summing to X * Y exactly
+    (``wsr_speed_soft_counts``).  Differentiable towards SR only (``wsr_speed_soft_counts_bwd``: one launch that
+    recomputes the positions).  Integer counting, no floating-point atomics: the same bits on every call, forward and
+    backward."""
+    from . import distribution_loss
+
+    _need_cuda(HR, SR)
+    distribution_loss._check_pair(HR, SR, "speed_soft_counts")
+    ns = int(tables.speed_bins)
+    distribution_loss.check_parameters(tables.bin_width, ns, "speed_soft_counts")
+    B, _, X, Y, NZ = HR.shape
+    if (ns + 1) * NZ > DISTRIBUTION_LOSS_LDS_COUNTERS or B > 65535 or X * Y * NZ >= 2 ** 31:
+        raise ValueError(f"speed_soft_counts: at most (speed_bins + 1) * NZ = {DISTRIBUTION_LOSS_LDS_COUNTERS}, 65535 "
+                         f"samples and 2^31 - 1 voxels per sample, not speed_bins = {ns}, B = {B}, X = {X}, Y = {Y}, "
+                         f"NZ = {NZ}")
+    return _SpeedSoftCounts.apply(HR.detach().contiguous().float(), SR.contiguous().float(), float(tables.c), ns)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # fractions skill score ([FSS]; csrc/fss.hip)
 # ---------------------------------------------------------------------------------------------------------------------
 FSS_TILE = 32  # FS_TILE of csrc/fss_kernels.h: the positions of a workgroup are FSS_TILE x FSS_TILE

@@ -106,6 +106,7 @@ def train(cfg, dataset_train, dataset_validation, x, y):
     if cfg.model.lower() != "wind_field_gan_3d":
         raise NotImplementedError(f"only wind_field_GAN_3D is supported - not {cfg.model}")
     gan = wind_field_GAN_3D(cfg)
+    gan.set_wind_scale(dataset_train.UVW_MAX)  # ([DISTRIBUTION_LOSS] bins the speed in m/s)
     status_logger.info(f"Making model wind_field_GAN_3D from config {cfg.name}")
     status_logger.debug(f"GAN:\n{gan}\n")
     for line in gan.get_new_status_logs():

@@ -821,6 +821,39 @@ int wsr_ssim_pair_sums_bwd(const float* hr, int32_t hr_c, const float* sr, int32
                            float* dsr, void* stream);
 int wsr_ssim_pair_sums_bwd_tile(int32_t X, int32_t Y, int32_t NZ, int32_t win, int32_t* tile);
 
+/* ---- wind-speed distribution loss of generator training ([DISTRIBUTION_LOSS]; csrc/distribution_loss.hip) -------
+ * wsr_speed_soft_counts: out (2, B, NZ, ns + 1) doubles, written completely: per source (0 hr, 1 sr; fp32 planar
+ * (B, c, X, Y, NZ), channels 0 = u and 1 = v read), sample and z level the soft (linearly binned) histogram of the
+ * horizontal speed of the plane.  In fp32, every product and sum rounded, nothing contracted, the square root correctly
+ * rounded, per voxel:
+ *    hs2 = u u + v v;   t = sqrt(hs2) c - 0.5;   t = min(max(t, 0), ns - 1);   k0 = min(floor(t), ns - 2);   f = t - k0
+ *    fi = rint(f 65536): bin k0 gets the integer 65536 - fi, bin k0 + 1 gets fi; a voxel whose hs2 is not finite enters
+ *    no bin and adds 65536 to column ns
+ * out = (double)count / 65536: every (source, b, z) row sums to X * Y exactly.  c = UVW_MAX / bin_width, finite and > 0.
+ * 32-bit integer counting in LDS (a workgroup holds all NZ levels of at most 65535 columns), 64-bit integer adds in the
+ * workspace, no floating-point atomics: the same bits on every call.  Nothing is saved for the backward.
+ * workspace: wsr_speed_soft_counts_workspace_floats(B, X, Y, NZ, ns) 4-byte words (0 for arguments the entry refuses),
+ * 8-byte aligned: the integer tables.
+ * wsr_speed_soft_counts_bwd: dsr (B, sr_c, X, Y, NZ) fp32, every element written exactly once: the vector-Jacobian
+ * product towards sr.  With gtab (B, NZ, ns) fp32 (device) = dL/dout[1][b, z, 0 .. ns) and t before the clamp, for a voxel
+ * with a finite hs2, r = sqrt(hs2) > 0 and 0 < t < ns - 1:
+ *    dsr[b, 0] = ((gtab[k0 + 1] - gtab[k0]) c) u / r,   dsr[b, 1] likewise with v;
+ * zero otherwise and in every channel from 2 on.  One launch that recomputes t with the forward's operations; gtab is
+ * staged in LDS; no atomics: the same bits on every call.
+ * wsr_speed_soft_counts_geometry: geom[0 .. 4) = (the columns a workgroup of the counting launch owns, its column ranges
+ * per (sample, source), the elements a workgroup of the backward owns, its element ranges per sample), a function of the
+ * shape alone (host only).
+ * A null pointer, a misaligned workspace, a channel count < 2, ns outside 2 .. 64, c not finite or not > 0, a
+ * non-positive size: WSR_EINVAL; (ns + 1) * NZ > WSR_DISTRIBUTION_LOSS_LDS_COUNTERS, B > 65535, X * Y >= 2^31 or
+ * X * Y * NZ >= 2^31: WSR_EUNSUPPORTED; nothing is launched and nothing is written in either case. */
+#define WSR_DISTRIBUTION_LOSS_LDS_COUNTERS 8320
+int64_t wsr_speed_soft_counts_workspace_floats(int32_t B, int32_t X, int32_t Y, int32_t NZ, int32_t ns);
+int wsr_speed_soft_counts(const float* hr, int32_t hr_c, const float* sr, int32_t sr_c, float c, int32_t ns, int32_t B,
+                          int32_t X, int32_t Y, int32_t NZ, void* workspace, double* out, void* stream);
+int wsr_speed_soft_counts_bwd(const float* sr, int32_t sr_c, const float* gtab, float c, int32_t ns, int32_t B, int32_t X,
+                              int32_t Y, int32_t NZ, float* dsr, void* stream);
+int wsr_speed_soft_counts_geometry(int32_t B, int32_t X, int32_t Y, int32_t NZ, int32_t ns, int32_t* geom);
+
 /* ---- fractions skill score ([FSS]; csrc/fss.hip) ---------------------------------------------------------------
  * wsr_level_fss: out (B, NZ, nt, nn, 5) doubles, written completely: per sample, z level, threshold t and
  * neighbourhood n = scales[k] five exact integers.  Sources 0 hr, 1 sr, 2 tl: fp32 planar (B, c, X, Y, NZ), channels

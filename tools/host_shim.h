@@ -29,6 +29,8 @@ static inline void __syncthreads() { pthread_barrier_wait(&g_barrier); }
 #define __forceinline__ inline
 #define __launch_bounds__(n)
 #define __shared__ static
+// the integer add behind a kernel header's *_LDS_ADD / *_GLOBAL_ADD macros, for 32-bit counters and 64-bit tables alike
+#define HOST_SHIM_ADD(p, v) __atomic_fetch_add((p), (v), __ATOMIC_RELAXED)
 
 namespace {
 
