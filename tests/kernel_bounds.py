@@ -57,6 +57,44 @@ and channel-scale factors are exact selections or single roundings inside the la
 back a value the kernel itself stored earlier pays rho for it through ``rho_mag``; one that reads a test operand (exact
 in bf16, like any residual) does not.
 
+BatchNorm (``ref_bn_*``; test_batchnorm_matrix.py).  Every stage is referenced from the fp32 tables the kernel itself
+receives - shift, mean, invstd, gamma, beta, sums, inv_n, scalars through ``_f32`` - so the stages are isolated and no
+error compounds; activations are bf16-exact in the bf16 rows.  The same bound with these K:
+
+* the reductions ``ref_bn_sums`` {sum d, sum d^2} and ``ref_bn_bwd_sums`` {sum g', sum g' xhat}: K = nvox + rows,
+  rho = 0 - nvox additions of terms plus the ``rows`` partial rows of the final kernel (the workgroups' atomics in the
+  scalar kernels).  A term costs at most three roundings of itself (x - shift, the product, (x - mean) * invstd), 3u of a
+  magnitude A already holds: inside the lambda term for every K >= 1.
+* the dy that ``bn_bwd_reduce`` writes back, ``ref_bn_bwd_dy``: one product, K = 1, rho of the stored type; bit-identical
+  to its input where the mask is 1.
+* ``ref_bn_finalize``: var = max(s2 / cnt - dm^2, 0) is three roundings with contraction off (two quotients' worth of
+  s2 / cnt and dm^2, one difference; max is 1-Lipschitz): ``bound(var, A_var, 3, 0)`` with A_var = s2 / cnt + dm^2.
+  invstd = (var + eps)^-1/2 turns an error e of var into invstd * e / (2 (var + eps)); var + eps and ``rsqrtf`` add
+  two relative roundings, the LAMBDA * 2^-24 term.  rm = (1 - m) rm0 + m mean: K = 3 (two products, one sum; 1 - m is a
+  rounding of a factor); rv the same with unb = var * (cnt / max(cnt - 1, 1)) in it, two more: K = 5, A with A_var.
+  After G ordered updates (``ref_bn_running``) K = 3G and 5G on the running sum of term magnitudes.  ``bn_mean``: one
+  quotient, K = 1.  ``bn_train_stats`` keeps its sums on the device: its mean is held to ``ref_bn_sums / cnt`` with
+  K = nvox + rows + 1 (the quotient), its invstd and running statistics to ``ref_bn_finalize`` / ``ref_bn_running`` of
+  the float64 sums of x shifted by the mean it wrote, with the SAME bounds as above (K = 3 inside invstd, 3G and 5G)
+  and nothing added for the fp32 sums in between: their error is a random walk over nvox terms of a sum that is
+  divided by cnt, far inside the lambda term (measured below), and a wider bound would let a ``cnt`` off by one
+  through at 25603 voxels.
+* ``ref_bn_apply``: x - mean, two products, one sum: K = 4, rho of the stored type.
+* ``ref_bn_bwd_apply``: the mask product, sums * inv_n, xhat (two), its product with sums * inv_n (two), two
+  differences and the product with gamma * invstd (two) - ten roundings at most in either kernel's order, of three
+  terms whose magnitudes A sums: K = 8 (10 u A < LAMBDA sqrt(8) u A) covers the one-element kernel and the 8-wide
+  one.
+
+Worst |err| / bound per label of test_batchnorm_matrix.py on the MI355X (its ``[bound]`` lines; bf16 rows / fp32 rows):
+bn_stats 0.037 / 0.029, shifted 0.009 / 0.025; bn_bwd_reduce sums 0.016 / 0.020 (act off 0.003 / 0.004), its
+written-back dy 0.79 / 0.059; bn_mean 0.061; bn_finalize invstd 0.067, running mean 0.078, running var 0.062;
+bn_train_stats mean 0.001 / 0.005, invstd 0.106 / 0.107, running mean 0.065 / 0.076, running var 0.063 / 0.057 (the
+largest at (2, 512, 16421); the fp32 emulation of the fused chain on the CPU reaches 0.08); bn_apply 0.995 / 0.077;
+bn_bwd_apply, one-element kernel, 0.995 / 0.088 over the four forms, 0.995 on the two one-element routes of the big
+data; bn_bwd_apply_v8 0.995 (sums), 0.994 (act_y), 0.995 (both).  As everywhere in this module: a bf16 store sits at
+the half-ulp limit, fp32 results at a few hundredths; the written-back bf16 dy at 0.79 because dy * 0.2 of an 8-bit
+significand seldom lands near a rounding tie.  No row exceeded its bound.
+
 A kernel bug that drops one tap at one voxel, loses one split or misplaces one channel chunk changes the elements it
 touches by a sizable fraction of A / sqrt(K), far above the bound; a whole-tensor relative L2 check averages such an
 error over every element and can miss it.
@@ -295,6 +333,142 @@ def ref_wgrad(x, gy, k, pad, *, ups=False, in_win=None):
 def _f32(v) -> float:
     """a scalar as the C side receives it (``float`` across the ABI)"""
     return float(torch.tensor(float(v), dtype=torch.float32))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# BatchNorm: every stage from the fp32 inputs the kernel itself receives, on (nvox, C) rows and (C,) / (2C,) tables
+# ---------------------------------------------------------------------------------------------------------------------
+
+def _row(t):
+    return _d(t).reshape(1, -1)
+
+
+def ref_bn_sums(x, shift=None):
+    """{sum_v d, sum_v d^2} per channel as one (2C,) table, d = x - shift[c] (``shift`` None: 0).  Returns (ref, A),
+    A = {sum |d|, sum d^2}; bound with K = nvox + rows."""
+    d = _d(x) if shift is None else _d(x) - _row(shift)
+    return torch.cat([d.sum(0), (d * d).sum(0)]), torch.cat([d.abs().sum(0), (d * d).sum(0)])
+
+
+def ref_bn_bwd_dy(dy, y, act, slope=0.2):
+    """the gradient in front of the folded LeakyReLU, g' = dy * (y > 0 ? 1 : slope) (``act`` false: dy itself), which
+    ``bn_bwd_reduce`` writes back over dy.  Returns (g', |g'|); bound with K = 1 and the stored type's rho, and where
+    the mask is 1 the stored element is the input, bit for bit."""
+    g = _d(dy)
+    if act:
+        g = g * _lrelu_mask(y, _f32(slope))
+    return g, g.abs()
+
+
+def ref_bn_bwd_sums(dy, y, x, mean, invstd, act, slope=0.2):
+    """{sum g', sum g' * xhat} per channel as one (2C,) table, g' of ``ref_bn_bwd_dy`` and xhat = (x - mean) * invstd.
+    Returns (ref, A), A = {sum |g'|, sum |g'| |xhat|}; bound with K = nvox + rows."""
+    g, _ = ref_bn_bwd_dy(dy, y, act, slope)
+    xh = (_d(x) - _row(mean)) * _row(invstd)
+    return (torch.cat([g.sum(0), (g * xh).sum(0)]),
+            torch.cat([g.abs().sum(0), (g.abs() * xh.abs()).sum(0)]))
+
+
+def ref_bn_mean(sums, cnt):
+    """sums[c] / cnt (``bn_mean``).  Returns (ref, |ref|); bound with K = 1."""
+    m = _d(sums) / _f32(cnt)
+    return m, m.abs()
+
+
+def ref_bn_finalize(s1, s2, cnt, mean, eps, momentum, rm0=None, rv0=None):
+    """``bn_finalize_channel`` from the shifted sums s1 = sum d, s2 = sum d^2 (d = x - mean): dm = s1 / cnt,
+    var = max(s2 / cnt - dm^2, 0), invstd = (var + eps)^-1/2, unb = var * cnt / max(cnt - 1, 1) and the running
+    statistics rm = (1 - m) rm0 + m mean, rv = (1 - m) rv0 + m unb (absent without rm0 / rv0).  Returns (ref, A), two
+    dicts: ref of ``var, invstd, unb, rm, rv``; A of ``var`` (= s2 / cnt + dm^2), ``rm`` and ``rv`` (the two terms'
+    magnitudes, rv's with A_var for var).  ``bn_finalize_bounds`` turns them into bounds."""
+    s1, s2, mean = _d(s1), _d(s2), _d(mean)
+    cnt, eps, m = _f32(cnt), _f32(eps), _f32(momentum)
+    dm = s1 / cnt
+    var = (s2 / cnt - dm * dm).clamp_min(0.0)
+    a_var = s2.abs() / cnt + dm * dm
+    ub = cnt / max(cnt - 1.0, 1.0)
+    ref = {"var": var, "invstd": (var + eps) ** -0.5, "unb": var * ub}
+    A = {"var": a_var}
+    if rm0 is not None:
+        rm0, rv0 = _d(rm0), _d(rv0)
+        ref["rm"] = (1.0 - m) * rm0 + m * mean
+        ref["rv"] = (1.0 - m) * rv0 + m * ref["unb"]
+        A["rm"] = abs(1.0 - m) * rm0.abs() + abs(m) * mean.abs()
+        A["rv"] = abs(1.0 - m) * rv0.abs() + abs(m) * a_var * ub
+    return ref, A
+
+
+def bn_finalize_bounds(ref, A, eps, steps=1):
+    """bounds of ``invstd``, ``rm``, ``rv`` from ``ref_bn_finalize`` / ``ref_bn_running`` with the same ``eps``
+    (``steps`` = G for running statistics after G ordered updates: K = 3G and 5G)"""
+    vb = bound(ref["var"], A["var"], 3, 0.0)
+    out = {"invstd": ref["invstd"] * (0.5 * vb / (ref["var"] + _f32(eps)) + LAMBDA * U_FP32)}
+    if "rm" in ref:
+        out["rm"] = bound(ref["rm"], A["rm"], 3 * steps, 0.0)
+        out["rv"] = bound(ref["rv"], A["rv"], 5 * steps, 0.0)
+    return out
+
+
+def ref_bn_running(groups, cnt, eps, momentum, rm0, rv0):
+    """the running statistics after ``ref_bn_finalize`` of each (s1, s2, mean) of ``groups`` in order, in float64 from
+    the fp32 initial values.  Returns (ref, A, per-group finalize results): A the running sum of term magnitudes.
+    Bound with ``steps=len(groups)``."""
+    rm, rv = _d(rm0), _d(rv0)
+    a_rm, a_rv = rm.abs(), rv.abs()
+    m = _f32(momentum)
+    cntf = _f32(cnt)
+    ub = cntf / max(cntf - 1.0, 1.0)
+    per = []
+    for s1, s2, mean in groups:
+        r, a = ref_bn_finalize(s1, s2, cnt, mean, eps, momentum, rm, rv)
+        a_rm = abs(1.0 - m) * a_rm + abs(m) * _d(mean).abs()
+        a_rv = abs(1.0 - m) * a_rv + abs(m) * a["var"] * ub
+        rm, rv = r["rm"], r["rv"]
+        per.append((r, a))
+    last = per[-1][0]
+    ref = {"rm": rm, "rv": rv, "var": last["var"], "invstd": last["invstd"]}
+    return ref, {"rm": a_rm, "rv": a_rv, "var": per[-1][1]["var"]}, per
+
+
+def bn_v4_geometry(C, nvox):
+    """(lanes, rows) of ``bn_reduce_v4_kernel`` as ``bn_v4_grid`` (elementwise.hip) launches it: lanes = 256 / (C / 4),
+    rows = min(512, ceil(nvox / (16 lanes))).  Widths the vectorised kernels do not take (C % 4, C > 512) go to the
+    scalar atomic kernels: lanes is None and rows the workgroup count of ``bn_grid``."""
+    if C % 4 or C > 512:
+        return None, max(1, min(1024, -(-nvox * C // (256 * 64))))
+    lanes = 256 // (C // 4)
+    return lanes, max(1, min(512, -(-nvox // (16 * lanes))))
+
+
+def ref_bn_apply(x, mean, invstd, gamma, beta, act, slope=0.2):
+    """y = lrelu?((x - mean) * invstd * gamma + beta).  Returns (ref, A), A = |x - mean| invstd |gamma| + |beta|;
+    bound with K = 4 and the stored type's rho."""
+    d = _d(x) - _row(mean)
+    sc = _row(invstd) * _row(gamma)
+    v = d * sc + _row(beta)
+    a = d.abs() * sc.abs() + _row(beta).abs()
+    if act:
+        v = F.leaky_relu(v, _f32(slope))
+    return v, a
+
+
+def ref_bn_bwd_apply(g, x, act_y, slope, mean, invstd, gamma, sums, inv_n):
+    """dx = (g' - sums[c] inv_n - xhat sums[C + c] inv_n) * gamma * invstd with g' = g * (act_y > 0 ? 1 : slope)
+    (``act_y`` None: g) and xhat = (x - mean) * invstd; both mean terms are absent when ``sums`` is None (the
+    eval-mode pass).  Returns (ref, A), A the three terms' magnitudes times |gamma invstd|; bound with K = 8 and the
+    stored type's rho - the one-element kernel and the 8-wide one, which orders the products differently."""
+    v = _d(g)
+    if act_y is not None:
+        v = v * _lrelu_mask(act_y, _f32(slope))
+    a = v.abs()
+    if sums is not None:
+        s, n = _d(sums), _f32(inv_n)
+        C = v.shape[1]
+        xh = (_d(x) - _row(mean)) * _row(invstd)
+        t1, t2 = s[:C].reshape(1, -1) * n, xh * s[C:].reshape(1, -1) * n
+        v, a = v - t1 - t2, a + t1.abs() + t2.abs()
+    sc = _row(gamma) * _row(invstd)
+    return v * sc, a * sc.abs()
 
 
 def ref_pointwise(x, w, *, bias=None, act=False, slope=0.2, alpha=1.0, res=None, beta=0.0, res_c1=None, res2=None,

@@ -745,3 +745,441 @@ def test_every_stride1_instantiation_has_a_matrix_row_or_a_reason():
     assert not missing, f"instantiations without a row in test_conv_tile_matrix.py: {missing}"
     assert not named - set(in_src), f"rows that name an instantiation the sources do not hold: {sorted(named - set(in_src))}"
     assert not rows & set(mx.UNREACHABLE)
+
+
+# ---- BatchNorm: references, fp32 emulations of every kernel in its own order, and the mistakes they must not hide ----------
+
+def test_bn_references_equal_float64_autograd():
+    """the chain sums -> mean -> shifted sums -> finalize -> apply -> backward sums -> dx of the BatchNorm references is
+    ``F.batch_norm`` (training) + ``F.leaky_relu`` under float64 autograd; two ordered running-statistics updates are
+    ``nn.BatchNorm3d`` called twice.  (Scalars exact in fp32: the references take them as the C side receives them.)"""
+    gen = torch.Generator().manual_seed(11)
+    B, C, xyz = 2, 6, (4, 4, 8)
+    eps, mom, slope = 2.0 ** -17, 0.125, 0.25
+    rows = lambda t: t.permute(0, 2, 3, 4, 1).reshape(-1, t.shape[1])
+    gamma = (1 + 0.1 * torch.randn(C, generator=gen, dtype=f64)).requires_grad_(True)
+    beta = (0.1 * torch.randn(C, generator=gen, dtype=f64)).requires_grad_(True)
+    bn = torch.nn.BatchNorm3d(C, eps=eps, momentum=mom).double()
+    rm0, rv0 = torch.randn(C, generator=gen, dtype=f64), torch.rand(C, generator=gen, dtype=f64) + 0.5
+    with torch.no_grad():
+        bn.running_mean.copy_(rm0)
+        bn.running_var.copy_(rv0)
+    groups = []
+    for call in range(2):
+        x = (0.3 + 1.5 * torch.randn((B, C) + xyz, generator=gen, dtype=f64)).requires_grad_(True)
+        gy = torch.randn((B, C) + xyz, generator=gen, dtype=f64)
+        n = x.numel() // C
+        bn(x.detach())
+        y = F.leaky_relu(F.batch_norm(x, None, None, gamma, beta, True, mom, eps), slope)
+        gx, gg, gb = torch.autograd.grad((y * gy).sum(), (x, gamma, beta))
+        xr, gr = rows(x.detach()), rows(gy)
+        s, _ = kb.ref_bn_sums(xr)
+        mean, _ = kb.ref_bn_mean(s[:C], n)
+        s2, _ = kb.ref_bn_sums(xr, mean)
+        fin, _ = kb.ref_bn_finalize(s2[:C], s2[C:], n, mean, eps, mom)
+        groups.append((s2[:C], s2[C:], mean))
+        close = lambda a, b: torch.testing.assert_close(a, b, rtol=1e-11, atol=1e-11)
+        close(mean, x.detach().mean(dim=(0, 2, 3, 4)))
+        close(fin["var"], x.detach().var(dim=(0, 2, 3, 4), unbiased=False))
+        yr, _ = kb.ref_bn_apply(xr, mean, fin["invstd"], gamma.detach(), beta.detach(), True, slope)
+        close(yr, rows(y.detach()))
+        bs, _ = kb.ref_bn_bwd_sums(gr, yr, xr, mean, fin["invstd"], True, slope)
+        close(bs[:C], gb)
+        close(bs[C:], gg)
+        gp, _ = kb.ref_bn_bwd_dy(gr, yr, True, slope)
+        for g_in, act_y in ((gp, None), (gr, yr)):  # the training form (g' written back) and the folded mask
+            dx, _ = kb.ref_bn_bwd_apply(g_in, xr, act_y, slope, mean, fin["invstd"], gamma.detach(), bs, 1.0 / n)
+            close(dx, rows(gx))
+        ev, _ = kb.ref_bn_bwd_apply(gr, xr, yr, slope, mean, fin["invstd"], gamma.detach(), None, 0.0)
+        close(ev, gp * (gamma.detach() * fin["invstd"]).view(1, -1))
+    run, _, _ = kb.ref_bn_running(groups, n, eps, mom, rm0, rv0)
+    close(run["rm"], bn.running_mean)
+    close(run["rv"], bn.running_var)
+
+
+def _emul_rows_sum(part):
+    """``chan_sum_final_kernel`` / ``bn_rows_sum``: the column sums of part (rows, C2) in fp32, thread = (row lane,
+    column), four accumulators over rows r, r + lanes, r + 2 lanes, r + 3 lanes, then the row lanes in order"""
+    rows, C2 = part.shape
+    fl = 1024 // C2
+    sh = []
+    for rl in range(fl):
+        a = [torch.zeros(C2) for _ in range(4)]
+        r = rl
+        while r + 3 * fl < rows:
+            for u in range(4):
+                a[u] = a[u] + part[r + u * fl]
+            r += 4 * fl
+        while r < rows:
+            a[0] = a[0] + part[r]
+            r += fl
+        sh.append((a[0] + a[1]) + (a[2] + a[3]))
+    out = sh[0]
+    for s in sh[1:]:
+        out = out + s
+    return out
+
+
+def _emul_v4_reduce(ta, tb, *, drop_lane_of=None, drop_trip=None):
+    """``bn_reduce_v4_kernel`` + the final kernel on the per-element fp32 terms ta, tb (nvox, C): every thread adds its
+    voxels trip by trip (step = rows * lanes), lane 0 adds the lanes in order, the final kernel adds the rows.
+    ``drop_lane_of`` = workgroup whose last voxel lane is left out, ``drop_trip`` = trip every thread skips."""
+    nvox, C = ta.shape
+    lanes, rows = kb.bn_v4_geometry(C, nvox)
+    step = rows * lanes
+    trips = -(-nvox // step)
+    parts = []
+    for t in (ta, tb):
+        pad = torch.zeros(trips * step, C)
+        pad[:nvox] = t
+        pad = pad.view(trips, rows, lanes, C)
+        acc = torch.zeros(rows, lanes, C)
+        for i in range(trips):
+            if i != drop_trip:
+                acc = acc + pad[i]
+        if drop_lane_of is not None:
+            acc[drop_lane_of, lanes - 1] = 0.0
+        a = acc[:, 0]
+        for l in range(1, lanes):
+            a = a + acc[:, l]
+        parts.append(a)
+    return _emul_rows_sum(torch.cat(parts, dim=1)), trips, rows
+
+
+def _f(v):
+    return torch.tensor(float(v), dtype=torch.float32)
+
+
+def _bn_rows(C, nvox, dt, seed):
+    """x (0.3 + 1.5 randn; in fp32 channel 1 at 1000 +- 1; channel 2 constant), dy, and a saved output with special
+    values, as the kernels' element type holds them (fp32 tensors, bf16-exact for bf16)"""
+    gen = torch.Generator().manual_seed(seed)
+    x = 0.3 + 1.5 * torch.randn(nvox, C, generator=gen)
+    if dt == torch.float32 and C > 1:
+        x[:, 1] = 1000.0 + torch.randn(nvox, generator=gen)
+    if C > 2:
+        x[:, 2] = 0.75
+    dy = torch.randn(nvox, C, generator=gen)
+    y = torch.randn(nvox, C, generator=gen).to(dt)
+    return (x.to(dt).float(), dy.to(dt).float(), y)
+
+
+def _emul_stats(x, shift, **kw):
+    d = x if shift is None else x - shift.view(1, -1)
+    return _emul_v4_reduce(d, d * d, **kw)
+
+
+def _emul_bwd_reduce(dy, y, x, mean, invstd, act, slope, flip=(), **kw):
+    g = dy
+    if act:
+        pos = y.float() > 0
+        for v, c in flip:
+            pos[v, c] = ~pos[v, c]
+        g = dy * torch.where(pos, torch.ones(()), _f(slope))
+    return _emul_v4_reduce(g, g * (x - mean.view(1, -1)) * invstd.view(1, -1), **kw) + (g,)
+
+
+BN_REDUCE_SHAPES = [(4, 1), (4, 257), (12, 1361), (48, 1000), (32, 630), (32, 512 * 50 + 3), (320, 333),
+                    (256, 32768 + 5)]
+
+
+def _bad(got, ref, bnd):
+    return kb.check_within(got, ref, bnd)[0]
+
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float32], ids=["bf16", "fp32"])
+@pytest.mark.parametrize("C,nvox", BN_REDUCE_SHAPES)
+def test_bn_reduce_emulation_is_within_the_bound(dt, C, nvox):
+    """both BatchNorm reductions in fp32 in the v4 kernel's order (threads, trips, lanes, rows) against
+    ``ref_bn_sums`` / ``ref_bn_bwd_sums`` with K = nvox + rows, and the written-back dy with K = 1"""
+    x, dy, y = _bn_rows(C, nvox, dt, 3 * C + nvox)
+    s0, _, rows = _emul_stats(x, None)
+    ref, A = kb.ref_bn_sums(x)
+    kb.assert_within(s0, ref, kb.bound(ref, A, nvox + rows, 0.0), f"emul bn_stats[{C}x{nvox}]")
+    mean = s0[:C] / _f(nvox)
+    s2, _, _ = _emul_stats(x, mean)
+    ref, A = kb.ref_bn_sums(x, mean)
+    kb.assert_within(s2, ref, kb.bound(ref, A, nvox + rows, 0.0), f"emul bn_stats shifted[{C}x{nvox}]")
+    invstd = torch.rsqrt((s2[C:] / _f(nvox) - (s2[:C] / _f(nvox)) ** 2).clamp_min(0) + _f(1e-5))
+    bs, _, _, g = _emul_bwd_reduce(dy, y, x, mean, invstd, True, 0.2)
+    ref, A = kb.ref_bn_bwd_sums(dy, y, x, mean, invstd, True, 0.2)
+    kb.assert_within(bs, ref, kb.bound(ref, A, nvox + rows, 0.0), f"emul bn_bwd_reduce[{C}x{nvox}]")
+    gref, ga = kb.ref_bn_bwd_dy(dy, y, True, 0.2)
+    kb.assert_within(g.to(dt), gref, kb.bound(gref, ga, 1, kb.rho_for(dt)), f"emul bn_bwd_reduce dy[{C}x{nvox}]")
+
+
+BN_REDUCE_MUTATIONS = {  # name -> ((C, nvox), emulation switches, which tables take the wrong channel)
+    "last_voxel_lane_of_a_workgroup_left_out": ((12, 1361), dict(drop_lane_of=1), False),
+    "last_voxel_lane_of_the_only_workgroup_left_out": ((4, 257), dict(drop_lane_of=0), False),
+    "second_trip_left_out": ((4, 257), dict(drop_trip=1), False),
+    "second_trip_of_a_capped_grid_left_out": ((256, 32768 + 5), dict(drop_trip=1), False),
+    "shift_or_mean_of_channel_c_plus_1": ((4, 1), dict(), True),
+    "shift_or_mean_of_channel_c_plus_1_two_rows": ((12, 1361), dict(), True),
+}
+
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float32], ids=["bf16", "fp32"])
+@pytest.mark.parametrize("name", list(BN_REDUCE_MUTATIONS))
+def test_bn_reduce_mutation_is_caught(dt, name):
+    (C, nvox), kw, roll = BN_REDUCE_MUTATIONS[name]
+    x, dy, y = _bn_rows(C, nvox, dt, 3 * C + nvox)
+    _, rows = kb.bn_v4_geometry(C, nvox)
+    if "drop_trip" in kw:
+        assert -(-nvox // (rows * kb.bn_v4_geometry(C, nvox)[0])) >= 2
+    mean = (x.double().mean(0) + 0.01).float()  # (a shift near the mean, as pass 2 gets it)
+    invstd = torch.rsqrt(x.double().var(0, unbiased=False).float() + _f(1e-5))
+    wrong = mean.roll(-1) if roll else mean
+    ref, A = kb.ref_bn_sums(x, mean)
+    bnd = kb.bound(ref, A, nvox + rows, 0.0)
+    assert not _bad(_emul_stats(x, mean)[0], ref, bnd)
+    assert _bad(_emul_stats(x, wrong, **kw)[0], ref, bnd) >= 1, name
+    ref, A = kb.ref_bn_bwd_sums(dy, y, x, mean, invstd, True, 0.2)
+    bnd = kb.bound(ref, A, nvox + rows, 0.0)
+    assert not _bad(_emul_bwd_reduce(dy, y, x, mean, invstd, True, 0.2)[0], ref, bnd)
+    assert _bad(_emul_bwd_reduce(dy, y, x, wrong, invstd, True, 0.2, **kw)[0], ref, bnd) >= 1, name
+
+
+def _emul_finalize(s1, s2, cnt, mean, eps, momentum, rm0=None, rv0=None, *, cnt_off=0.0, unbiased_invstd=False):
+    """``bn_finalize_channel`` in fp32, every product and sum rounded on its own"""
+    cnt, eps, m = _f(cnt) + _f(cnt_off), _f(eps), _f(momentum)
+    dm = s1 / cnt
+    var = (s2 / cnt - dm * dm).clamp_min(0.0)
+    ub = cnt / torch.maximum(cnt - 1.0, _f(1.0))
+    invstd = torch.rsqrt((var * ub if unbiased_invstd else var) + eps)
+    if rm0 is None:
+        return invstd, None, None
+    keep = _f(1.0) - m
+    return invstd, keep * rm0 + m * mean, keep * rv0 + m * (var * ub)
+
+
+def _finalize_case(C, cnt, seed=5):
+    gen = torch.Generator().manual_seed(seed)
+    d = 1.5 * torch.randn(max(cnt, 1), C, generator=gen, dtype=f64)
+    d[:, C // 2] = 0.0  # a constant channel: var = 0
+    s1 = (1e-3 * torch.randn(C, generator=gen)).float() * cnt  # (the shifted sum is near 0, not 0)
+    s2 = (d * d).sum(0).float()
+    mean = (0.3 + torch.randn(C, generator=gen)).float()
+    rm0, rv0 = torch.randn(C, generator=gen), torch.rand(C, generator=gen) + 0.5
+    return s1, s2, mean, rm0, rv0
+
+
+@pytest.mark.parametrize("cnt", [1, 630])
+@pytest.mark.parametrize("momentum", [0.1, 0.0])
+def test_bn_finalize_emulation_is_within_the_bound(cnt, momentum):
+    s1, s2, mean, rm0, rv0 = _finalize_case(300, cnt)
+    ref, A = kb.ref_bn_finalize(s1, s2, cnt, mean, 1e-5, momentum, rm0, rv0)
+    bnd = kb.bn_finalize_bounds(ref, A, 1e-5)
+    invstd, rm, rv = _emul_finalize(s1, s2, cnt, mean, 1e-5, momentum, rm0, rv0)
+    for k, got in (("invstd", invstd), ("rm", rm), ("rv", rv)):
+        kb.assert_within(got, ref[k], bnd[k], f"emul bn_finalize {k}[cnt {cnt}, m {momentum}]")
+    if momentum == 0.0:
+        assert torch.equal(rm, rm0) and torch.equal(rv, rv0)
+    m, _ = kb.ref_bn_mean(s1, cnt)
+    kb.assert_within(s1 / _f(cnt), m, kb.bound(m, m.abs(), 1, 0.0), "emul bn_mean")
+    # G ordered updates of the same running statistics (bn_train_stats)
+    groups, rmg, rvg = [], rm0, rv0
+    for g in range(3):
+        sg = _finalize_case(300, cnt, seed=6 + g)[:3]
+        groups.append(sg)
+        _, rmg, rvg = _emul_finalize(*sg[:2], cnt, sg[2], 1e-5, momentum, rmg, rvg)
+    run, ra, _ = kb.ref_bn_running(groups, cnt, 1e-5, momentum, rm0, rv0)
+    rb = kb.bn_finalize_bounds(run, ra, 1e-5, steps=3)
+    kb.assert_within(rmg, run["rm"], rb["rm"], f"emul bn running mean x3[cnt {cnt}, m {momentum}]")
+    kb.assert_within(rvg, run["rv"], rb["rv"], f"emul bn running var x3[cnt {cnt}, m {momentum}]")
+
+
+@pytest.mark.parametrize("name", ["cnt_off_by_one", "unbiased_factor_on_invstd_variance"])
+def test_bn_finalize_mutation_is_caught(name):
+    cnt = 630
+    s1, s2, mean, rm0, rv0 = _finalize_case(4, cnt)
+    ref, A = kb.ref_bn_finalize(s1, s2, cnt, mean, 1e-5, 0.1, rm0, rv0)
+    bnd = kb.bn_finalize_bounds(ref, A, 1e-5)
+    kw = dict(cnt_off=-1.0) if name.startswith("cnt") else dict(unbiased_invstd=True)
+    invstd, rm, rv = _emul_finalize(s1, s2, cnt, mean, 1e-5, 0.1, rm0, rv0, **kw)
+    assert _bad(invstd, ref["invstd"], bnd["invstd"]) >= 1, name
+    if name.startswith("cnt"):  # cnt / (cnt - 1) of 629 reaches the running variance too
+        assert _bad(rv, ref["rv"], bnd["rv"]) >= 1, name
+        assert _bad(_emul_finalize(s1, s2, cnt, mean, 1e-5, 0.1, rm0, rv0, cnt_off=1.0)[0], ref["invstd"],
+                    bnd["invstd"]) >= 1
+
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float32], ids=["bf16", "fp32"])
+@pytest.mark.parametrize("C,nvox", [(32, 630), (48, 1000), (32, 512 * 50 + 3)])
+def test_bn_train_stats_emulation_is_within_the_finalize_bounds(dt, C, nvox):
+    """the fused chain of ``bn_train_stats`` (v4 sums, mean, shifted v4 sums, finalize; two groups in order) in fp32
+    against ``ref_bn_finalize`` / ``ref_bn_running`` of the FLOAT64 sums of x shifted by the fp32 mean: the fp32 sums in
+    between need no allowance of their own, and ``cnt`` off by one in the fused finalize is caught at every size"""
+    gen = torch.Generator().manual_seed(C + nvox)
+    rm0, rv0 = torch.randn(C, generator=gen), torch.rand(C, generator=gen) + 0.5
+    for cnt_off in (0.0, -1.0):
+        rm, rv, groups, bad = rm0, rv0, [], 0
+        for g in range(2):
+            x = _bn_rows(C, nvox, dt, 5 * C + nvox + g)[0]
+            mean = _emul_stats(x, None)[0][:C] / _f(nvox)
+            s2 = _emul_stats(x, mean)[0]
+            invstd, rm, rv = _emul_finalize(s2[:C], s2[C:], nvox, mean, 1e-5, 0.1, rm, rv, cnt_off=cnt_off)
+            ref, _ = kb.ref_bn_sums(x, mean)
+            groups.append((ref[:C], ref[C:], mean))
+            fin, fa = kb.ref_bn_finalize(ref[:C], ref[C:], nvox, mean, 1e-5, 0.1)
+            bnd = kb.bn_finalize_bounds(fin, fa, 1e-5)["invstd"]
+            if cnt_off:
+                bad += _bad(invstd, fin["invstd"], bnd)
+            else:
+                kb.assert_within(invstd, fin["invstd"], bnd, f"emul bn_train_stats invstd[{C}x{nvox}]")
+        run, ra, _ = kb.ref_bn_running(groups, nvox, 1e-5, 0.1, rm0, rv0)
+        rb = kb.bn_finalize_bounds(run, ra, 1e-5, steps=2)
+        if cnt_off:
+            assert bad >= C // 2 and _bad(rv, run["rv"], rb["rv"]) >= 1
+        else:
+            kb.assert_within(rm, run["rm"], rb["rm"], f"emul bn_train_stats running mean[{C}x{nvox}]")
+            kb.assert_within(rv, run["rv"], rb["rv"], f"emul bn_train_stats running var[{C}x{nvox}]")
+
+
+def _bn_tables(x, C, seed):
+    gen = torch.Generator().manual_seed(seed)
+    mean = x.double().mean(0).float()
+    invstd = torch.rsqrt(x.double().var(0, unbiased=False).float() + _f(1e-5))
+    gamma = 1 + 0.1 * torch.randn(C, generator=gen)
+    beta = 0.1 * torch.randn(C, generator=gen)
+    sums = torch.cat([torch.randn(C, generator=gen), torch.randn(C, generator=gen)]) * 20.0
+    return mean, invstd, gamma, beta, sums
+
+
+def _emul_apply(x, mean, invstd, gamma, beta, act, slope, dt):
+    r = lambda t: t.view(1, -1)
+    v = (x - r(mean)) * r(invstd) * r(gamma) + r(beta)
+    if act:
+        v = torch.where(v > 0, v, v * _f(slope))
+    return v.to(dt)
+
+
+def _emul_bwd_apply(g, x, act_y, slope, mean, invstd, gamma, sums, inv_n, dt, *, v8=False, threads=None, flip=(),
+                    no_inv_n_on_xhat=False, reuse_trip0=False):
+    """``bn_bwd_apply_kernel`` (one element per thread: constants by i % C) or ``bn_bwd_apply_v8_kernel`` (``threads``
+    threads of 8 elements, constants by the FIRST vector of the thread when ``reuse_trip0``, as the kernel keeps them)
+    in fp32, each in its own order of products"""
+    nvox, C = g.shape
+    n = _f(inv_n)
+    v = g
+    if act_y is not None:
+        pos = act_y.float() > 0
+        for vv, c in flip:
+            pos[vv, c] = ~pos[vv, c]
+        v = g * torch.where(pos, torch.ones(()), _f(slope))
+    if not v8:
+        r = lambda t: t.view(1, -1)
+        if sums is not None:
+            xh = (x - r(mean)) * r(invstd)
+            t2 = xh * r(sums[C:]) if no_inv_n_on_xhat else xh * r(sums[C:]) * n
+            v = v - r(sums[:C]) * n - t2
+        return (v * r(gamma) * r(invstd)).to(dt)
+    i = torch.arange(nvox * C) // 8
+    k = torch.arange(nvox * C) % 8
+    true_c = (i * 8 + k) % C
+    c = ((i % threads) * 8 + k) % C if reuse_trip0 else true_c
+    sc = (gamma * invstd)[c]
+    v = v.reshape(-1)
+    if sums is not None:
+        a0 = (sums[:C] * n)[c]
+        a1 = (sums[C:] * invstd if no_inv_n_on_xhat else sums[C:] * n * invstd)[c]
+        v = v - a0 - (x.reshape(-1) - mean[c]) * a1
+    return (v * sc).view(nvox, C).to(dt)
+
+
+BN_APPLY_SHAPES = [(1, 630), (4, 630), (12, 630), (256, 630)]
+
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float32], ids=["bf16", "fp32"])
+@pytest.mark.parametrize("C,nvox", BN_APPLY_SHAPES)
+def test_bn_apply_emulations_are_within_the_bound(dt, C, nvox):
+    x, dy, y = _bn_rows(C, nvox, dt, 7 * C + nvox)
+    mean, invstd, gamma, beta, sums = _bn_tables(x, C, C)
+    for act in (True, False):
+        ref, A = kb.ref_bn_apply(x, mean, invstd, gamma, beta, act, 0.2)
+        kb.assert_within(_emul_apply(x, mean, invstd, gamma, beta, act, 0.2, dt), ref,
+                         kb.bound(ref, A, 4, kb.rho_for(dt)), f"emul bn_apply[{C}x{nvox} act {act}]")
+    for s in (sums, None):
+        for ay in (y, None):
+            ref, A = kb.ref_bn_bwd_apply(dy, x, ay, 0.2, mean, invstd, gamma, s, 1.0 / nvox)
+            bnd = kb.bound(ref, A, 8, kb.rho_for(dt))
+            tag = f"[{C}x{nvox} sums {s is not None} act_y {ay is not None}]"
+            kb.assert_within(_emul_bwd_apply(dy, x, ay, 0.2, mean, invstd, gamma, s, 1.0 / nvox, dt), ref, bnd,
+                             "emul bn_bwd_apply" + tag)
+            if dt == torch.bfloat16 and C % 8 == 0:  # the 8-wide order: 128 threads x 8 = 4 x C elements per trip
+                got = _emul_bwd_apply(dy, x, ay, 0.2, mean, invstd, gamma, s, 1.0 / nvox, dt, v8=True, threads=128,
+                                      reuse_trip0=True)
+                kb.assert_within(got, ref, bnd, "emul bn_bwd_apply v8" + tag)
+
+
+class _Apply:
+    """a bf16 C = 8 layer on 630 voxels with the special values of the saved output placed where g is largest"""
+    C, nvox, dt = 8, 630, torch.bfloat16
+
+    def __init__(self):
+        self.x, self.dy, self.y = _bn_rows(self.C, self.nvox, self.dt, 77)
+        self.mean, self.invstd, self.gamma, self.beta, self.sums = _bn_tables(self.x, self.C, 78)
+        self.inv_n = 1.0 / self.nvox
+        order = self.dy.abs().flatten().argsort(descending=True)
+        self.at = [(int(i) // self.C, int(i) % self.C) for i in order[:4]]
+        for (v, c), bits in zip(self.at, (NEG_ZERO, POS_SUB, NEG_SUB, 0x0000)):
+            self.y[v, c] = _bits(bits)
+
+    def ref(self, sums, act_y):
+        ref, A = kb.ref_bn_bwd_apply(self.dy, self.x, act_y, 0.2, self.mean, self.invstd, self.gamma, sums, self.inv_n)
+        return ref, kb.bound(ref, A, 8, kb.rho_for(self.dt))
+
+    def emul(self, sums, act_y, **kw):
+        return _emul_bwd_apply(self.dy, self.x, act_y, 0.2, self.mean, self.invstd, self.gamma, sums, self.inv_n,
+                               self.dt, **kw)
+
+
+@pytest.fixture(scope="module")
+def bn_apply_case():
+    return _Apply()
+
+
+@pytest.mark.parametrize("v8", [False, True], ids=["scalar", "v8"])
+def test_bn_bwd_apply_missing_inv_n_on_the_xhat_term_is_caught(bn_apply_case, v8):
+    s = bn_apply_case
+    ref, bnd = s.ref(s.sums, None)
+    assert not _bad(s.emul(s.sums, None, v8=v8, threads=128), ref, bnd)
+    assert _bad(s.emul(s.sums, None, v8=v8, threads=128, no_inv_n_on_xhat=True), ref, bnd) >= s.nvox
+
+
+def test_bn_bwd_apply_v8_constants_of_trip_0_on_other_channels_are_caught(bn_apply_case):
+    """the 8-wide kernel keeps the constants of its first vector: right while threads * 8 is a multiple of C (the host
+    checks that C divides 256), wrong on every trip whose first channel differs"""
+    s = bn_apply_case
+    x, dy, y = _bn_rows(32, s.nvox, s.dt, 79)
+    mean, invstd, gamma, beta, sums = _bn_tables(x, 32, 80)
+    ref, A = kb.ref_bn_bwd_apply(dy, x, None, 0.2, mean, invstd, gamma, sums, s.inv_n)
+    bnd = kb.bound(ref, A, 8, kb.RHO_BF16)
+    emul = lambda threads: _emul_bwd_apply(dy, x, None, 0.2, mean, invstd, gamma, sums, s.inv_n, s.dt, v8=True,
+                                           threads=threads, reuse_trip0=True)
+    assert not _bad(emul(128), ref, bnd)  # 128 * 8 elements per trip: a multiple of C
+    # 129 threads: trip t starts 8 t channels further on; only trips 0, 4, 8, .. keep their channels
+    assert _bad(emul(129), ref, bnd) >= x.numel() // 2
+
+
+@pytest.mark.parametrize("v8", [False, True], ids=["scalar", "v8"])
+@pytest.mark.parametrize("which", ["negative_zero_taken_as_positive", "positive_subnormal_taken_as_not_positive"])
+def test_bn_mask_sign_of_special_values_is_caught(bn_apply_case, which, v8):
+    """the folded LeakyReLU derivative at -0.0 and at a positive subnormal, in the eval form of bn_bwd_apply (both
+    kernels' orders) and in bn_bwd_reduce's written-back dy"""
+    s = bn_apply_case
+    v, c = s.at[0] if which.startswith("negative") else s.at[1]
+    assert bool(s.y[v, c].double() > 0) == which.startswith("positive")
+    ref, bnd = s.ref(None, s.y)
+    assert not _bad(s.emul(None, s.y, v8=v8, threads=128), ref, bnd)
+    got = s.emul(None, s.y, v8=v8, threads=128, flip=[(v, c)])
+    _, _, _, ratio = kb.check_within(got, ref, bnd)
+    assert [(int(a), int(b)) for a, b in (ratio > 1.0).nonzero().tolist()] == [(v, c)]
+    gref, ga = kb.ref_bn_bwd_dy(s.dy, s.y, True, 0.2)
+    gb = kb.bound(gref, ga, 1, kb.RHO_BF16)
+    g = _emul_bwd_reduce(s.dy, s.y, s.x, s.mean, s.invstd, True, 0.2)[3].to(s.dt)
+    assert not _bad(g, gref, gb)
+    keep = kb._lrelu_mask(s.y, 0.2) == 1.0
+    assert torch.equal(g[keep].view(torch.int16), s.dy.to(s.dt)[keep].view(torch.int16))
+    g = _emul_bwd_reduce(s.dy, s.y, s.x, s.mean, s.invstd, True, 0.2, flip=[(v, c)])[3].to(s.dt)
+    _, _, _, ratio = kb.check_within(g, gref, gb)
+    assert [(int(a), int(b)) for a, b in (ratio > 1.0).nonzero().tolist()] == [(v, c)]
