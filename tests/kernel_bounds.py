@@ -95,6 +95,45 @@ data; bn_bwd_apply_v8 0.995 (sums), 0.994 (act_y), 0.995 (both).  As everywhere 
 the half-ulp limit, fp32 results at a few hundredths; the written-back bf16 dy at 0.79 because dy * 0.2 of an 8-bit
 significand seldom lands near a rounding tie.  No row exceeded its bound.
 
+The network boundary (``ref_deriv`` .. ``ref_plane_sum``; test_boundary_matrix.py): the content loss of the generator,
+the wind gradient and the planar fp32 <-> NDHWC kernels, every stage from the fp32 operands the kernel receives, rho = 0
+throughout (fp32 stores; the copies are compared as bit patterns, bf16 copies with the host's round-to-nearest-even).
+
+* one derivative element (``ref_deriv``, ``ref_wind_gradient``): K_STENCIL = 12, the longest chain of roundings into
+  one term, counted in ``deriv_row`` (stencil.h :18-20) and ``jacobian``: hl and hr (two differences), hr * hr and
+  hl * hl (two products), their difference, hl * hr, hl + hr and their product (den, three), the quotient, the product
+  with f_i, two additions of the three terms - 2 + 2 + 1 + 3 + 1 + 1 + 2.  The chain through a or c is one shorter, the
+  one-sided rows have four.  A = |a| |f-| + bmag |f_i| + |c| |f+| with bmag = (hr^2 + hl^2) / |den|, the centre
+  weight's magnitude BEFORE hr^2 - hl^2 cancels: the roundings of the two squares are relative to the squares, not to
+  their difference.  With |b| |f_i| instead, the fp32 emulation of the same correct arithmetic leaves the bound 124-fold
+  on the grid 100.37 i + 1e-5 i^1.5 at a centre value of 1e6 (746-fold when the difference of the squares is contracted
+  into one fma, which then returns the rounding error of hl * hl where hr == hl) and stays at 0.04 of it with bmag
+  (test_kernel_bounds.py).  On 100 i + 1e-5 i^1.5 itself the fp32 spacings are 100 or 100 + 2^-13, whose squares are
+  exact, and both forms hold.
+* the adjoint (``ref_wind_gradient_bwd``): K_ADJOINT = 19 - the nine roundings of a centre weight, the product, and
+  the nine additions into ``acc`` over the three axes; A the same expression on magnitudes with bmag.
+* the residual (``ref_physics_residual``): K_RESIDUAL = 23 - a Jacobian entry (12), J_sr - J_hr and the product with
+  2 coef (2; the doubling is exact), and on channels 0, 4, 8 the divergence route: d2 (three), d3 (two), g2 * d3, g3 * d2
+  and their sum (three), the addition into o (one).  A = 2 |coef| (M_sr + M_hr) per route.
+* dsr (``ref_physics_adjoint``): K_DSR = 24 - the adjoint's 19, SR - HR, coef[4] * sign, 2 coef[5] * d, their sum and
+  the addition into ``acc``; referenced from the residual the first launch wrote.
+* the six sums of ``ref_physics_stats``: K = terms + rows + per-term roundings, terms = {6, 3, 1, 1, 3, 3} * voxels,
+  rows = ``physics_rows``, per-term = 27 for the Jacobian sums (two entries of 12, their difference, twice through
+  the square, the product), 31 and 29 for the divergences (+ 2, + 1 additions on either side), 1 and 3 for sum |d| and
+  sum d^2; A = sum (M_sr + M_hr)^2.  Where SR is close to HR that A is 10^4 times the sum, so the four Jacobian sums
+  are also held to a narrower bound that follows the element bounds through the square (``tight_sums``).  The eight
+  maxima: the largest element bound in the range (max is 1-Lipschitz); NaN where the range holds one.
+* ``ref_zfold``: K = KZ + 1, A = |bias| + sum |t|.  ``ref_plane_sum``: K = B V + rows, rows = ``plane_sum_rows``.
+
+Worst |err| / bound per label of test_boundary_matrix.py on the MI355X: wind_gradient 0.033, wind_gradient_bwd 0.048;
+physics_stats 0.019 over the main rows (0.022 with every z-derivative negative, 0.022 with a spike, 0.016 of the HR
+maxima beside a NaN), its four Jacobian sums against the narrower bound 0.005; physics_residual 0.011 (one-hot 0.011),
+physics_adjoint 0.032 (one-hot 0.050, coef[0..3] = 0 with equal levels 0.012); zfold 0.061; plane_sum 0.0019; through
+the wrappers wind_gradient 0.020 and 0.034 backward, physics_loss_stats 0.002 and 0.017 backward, zfold 0.041,
+plane_sum 4e-5.  Every copy row (planar_to_ndhwc, ndhwc_to_planar, zunfold, fp32 and bf16) and every pixel-term row
+matched bit for bit: 0.  The fp32 emulations on the CPU reach 0.038 (Jacobian), 0.040 (adjoint), 0.040 (residual),
+0.045 (dsr), 0.015 (statistics).  No row exceeded its bound.
+
 A kernel bug that drops one tap at one voxel, loses one split or misplaces one channel chunk changes the elements it
 touches by a sizable fraction of A / sqrt(K), far above the bound; a whole-tensor relative L2 check averages such an
 error over every element and can miss it.
@@ -500,6 +539,292 @@ def ref_pointwise(x, w, *, bias=None, act=False, slope=0.2, alpha=1.0, res=None,
         v[:, m0:m1] *= m
         a[:, m0:m1] *= m.abs()
     return v, a
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the network boundary: derivative stencils, the content loss, the planar layout kernels (test_boundary_matrix.py)
+# ---------------------------------------------------------------------------------------------------------------------
+
+K_STENCIL = 12   # one derivative element, see the module docstring
+K_ADJOINT = 19   # one element of the stencils' adjoint
+K_RESIDUAL = 23  # one element of the content loss's residual
+K_DSR = 24       # one element of d loss / d SR
+PL_BLOCK, PL_ROWS = 256, 1024  # physics_loss.hip :25-26
+
+
+def physics_rows(nvox) -> int:
+    """workgroups of ``physics_stats_kernel`` = partial rows of its final kernel (``pl_grid``, physics_loss.hip :223)"""
+    return max(1, min(PL_ROWS, -(-int(nvox) // PL_BLOCK)))
+
+
+def _stencil_rows(co):
+    """rows of the derivative operator along the LAST axis of the float64 coordinates ``co`` (..., n), as
+    ``deriv_row`` (stencil.h) builds them: (a, b, c, bmag), bmag the centre weight's magnitude BEFORE the cancellation
+    in hr^2 - hl^2.  n < 2: zeros."""
+    n = co.shape[-1]
+    a, b, c, bm = (torch.zeros_like(co) for _ in range(4))
+    if n < 2:
+        return a, b, c, bm
+    h = co[..., 1:] - co[..., :-1]
+    if n >= 3:
+        hl, hr = h[..., :-1], h[..., 1:]
+        den = hl * hr * (hl + hr)
+        a[..., 1:-1] = -(hr * hr) / den
+        b[..., 1:-1] = (hr * hr - hl * hl) / den
+        c[..., 1:-1] = (hl * hl) / den
+        bm[..., 1:-1] = (hr * hr + hl * hl) / den.abs()
+    b[..., 0], c[..., 0] = -1.0 / h[..., 0], 1.0 / h[..., 0]
+    a[..., -1], b[..., -1] = -1.0 / h[..., -1], 1.0 / h[..., -1]
+    bm[..., 0], bm[..., -1] = b[..., 0].abs(), b[..., -1].abs()
+    return a, b, c, bm
+
+
+def _shift(t, k):
+    """s[..., i] = t[..., i + k], zero where i + k falls outside"""
+    s = torch.zeros_like(t)
+    n = t.shape[-1]
+    if abs(k) < n:
+        if k > 0:
+            s[..., :n - k] = t[..., k:]
+        else:
+            s[..., -k:] = t[..., :n + k]
+    return s
+
+
+def _axis_coords(co, dim):
+    co = _d(co)
+    return co if co.dim() == 1 else co.movedim(dim, -1)
+
+
+def ref_deriv(f, co, dim):
+    """derivative of f (B, C, X, Y, Z) along ``dim``: three-point non-uniform rows inside, one-sided rows at the ends,
+    zero on an axis of length 1.  ``co``: a 1-D table of the axis (x, y) or a field (B, 1, X, Y, Z) whose columns
+    along ``dim`` are the coordinates (z).  Returns (d, M), M = |a| |f-| + bmag |f0| + |c| |f+| with bmag taken before
+    the cancellation of the centre weight; bound with K_STENCIL."""
+    f = _d(f).movedim(dim, -1)
+    a, b, c, bm = _stencil_rows(_axis_coords(co, dim))
+    fm, fp = _shift(f, -1), _shift(f, 1)
+    v = a * fm + b * f + c * fp
+    m = a.abs() * fm.abs() + bm * f.abs() + c.abs() * fp.abs()
+    return v.movedim(-1, dim), m.movedim(-1, dim)
+
+
+def ref_wind_gradient(f, x, y, zc):
+    """the 9-channel Jacobian stack (B, 9, X, Y, Z) of f (B, 3, X, Y, Z): d/dx, d/dy, d/dz of the three components, z
+    on the per-column heights ``zc`` (B, 1, X, Y, Z).  Returns (J, M); bound with K_STENCIL."""
+    parts = [ref_deriv(f, x, 2), ref_deriv(f, y, 3), ref_deriv(f, zc, 4)]
+    return torch.cat([p[0] for p in parts], 1), torch.cat([p[1] for p in parts], 1)
+
+
+def _adjoint_axis(g, co, dim):
+    g = g.movedim(dim, -1)
+    a, b, c, bm = _stencil_rows(_axis_coords(co, dim))
+    v = _shift(c * g, -1) + b * g + _shift(a * g, 1)
+    m = _shift(c.abs() * g.abs(), -1) + bm * g.abs() + _shift(a.abs() * g.abs(), 1)
+    return v.movedim(-1, dim), m.movedim(-1, dim)
+
+
+def ref_wind_gradient_bwd(g, x, y, zc):
+    """adjoint of ``ref_wind_gradient``: df_j = c_{j-1} g_{j-1} + b_j g_j + a_{j+1} g_{j+1} along each axis, summed
+    over the three axes; g (B, 9, X, Y, Z) -> (B, 3, X, Y, Z).  Returns (df, A), A the same expression on magnitudes
+    with the pre-cancellation centre weight; bound with K_ADJOINT."""
+    g = _d(g)
+    parts = [_adjoint_axis(g[:, 3 * k:3 * k + 3], co, 2 + k) for k, co in enumerate((x, y, zc))]
+    return sum(p[0] for p in parts), sum(p[1] for p in parts)
+
+
+def _nanmax(t):
+    return t.max()  # (torch.max propagates NaN)
+
+
+def ref_physics_stats(hr, sr, x, y, zc, rows=None, jac=None, tight_sums=False):
+    """the 14 statistics of ``wsr_physics_loss_stats``: sums {xy Jacobian, z Jacobian, div3, div2 squared differences,
+    sum |HR - SR|, sum (HR - SR)^2}, then the maxima {max |J[:6]|, max J[6:] (signed), max |div3|, max |div2|} of HR
+    and of SR.  Returns (ref, bnd), two (14,) tensors.  Sums: ``bound(ref, A, K, 0)`` with A = sum (M_sr + M_hr)^2
+    (the pixel sums: sum |d|, sum d^2) and K = terms + rows + the per-term roundings of the module docstring,
+    ``rows`` = ``physics_rows(voxels)``.  Maxima: the largest per-element bound over the elements the maximum ranges
+    over (max is 1-Lipschitz), rho = 0.  A NaN anywhere in a range makes that entry NaN.
+
+    ``tight_sums``: a third (6,) tensor, a second and narrower bound of the sums.  Where SR is close to HR on fields
+    with a large mean, (M_sr + M_hr)^2 is 10^4 times the term (J_sr - J_hr)^2 and the bound above several times the sum
+    itself.  The narrower one follows the error through the square: each Jacobian entry is within its own element
+    bound e_sr, e_hr (K_STENCIL; + 2, + 1 for the divergences), so a term is off by at most 2 |d| e + e^2 with
+    e = e_sr + e_hr, summed without any cancellation, plus ``bound(s, s, terms + rows + 2, 0)`` for the difference,
+    the square and the additions of the terms themselves.  The pixel sums keep their bound."""
+    hr_, sr_ = _d(hr), _d(sr)
+    nvox = hr_.numel() // 3
+    rows = physics_rows(nvox) if rows is None else rows
+    (jh, mh), (js, ms) = jac if jac is not None else (ref_wind_gradient(hr, x, y, zc), ref_wind_gradient(sr, x, y, zc))
+    d3 = lambda j: j[:, 0] + j[:, 4] + j[:, 8]  # noqa: E731
+    d2 = lambda j: j[:, 0] + j[:, 4]  # noqa: E731
+    d = hr_ - sr_
+    ref, bnd, tight = [], [], []
+    eb = lambda j, m, k: bound(j, m, k, 0.0)  # noqa: E731
+    for val, a, terms, per, e in (
+            ((js[:, :6] - jh[:, :6]) ** 2, (ms[:, :6] + mh[:, :6]) ** 2, 6, 27,
+             eb(js[:, :6], ms[:, :6], K_STENCIL) + eb(jh[:, :6], mh[:, :6], K_STENCIL)),
+            ((js[:, 6:] - jh[:, 6:]) ** 2, (ms[:, 6:] + mh[:, 6:]) ** 2, 3, 27,
+             eb(js[:, 6:], ms[:, 6:], K_STENCIL) + eb(jh[:, 6:], mh[:, 6:], K_STENCIL)),
+            ((d3(jh) - d3(js)) ** 2, (d3(mh) + d3(ms)) ** 2, 1, 31,
+             eb(d3(js), d3(ms), K_STENCIL + 2) + eb(d3(jh), d3(mh), K_STENCIL + 2)),
+            ((d2(jh) - d2(js)) ** 2, (d2(mh) + d2(ms)) ** 2, 1, 29,
+             eb(d2(js), d2(ms), K_STENCIL + 1) + eb(d2(jh), d2(mh), K_STENCIL + 1)),
+            (d.abs(), d.abs(), 3, 1, None), (d * d, d * d, 3, 3, None)):
+        s = val.sum()
+        ref.append(s)
+        bnd.append(bound(s, a.sum(), terms * nvox + rows + per, 0.0))
+        if e is not None:  # a term (d + t)^2 with |t| <= e is off by at most 2 |d| e + e^2; then the sum of the terms
+            tight.append((2.0 * val.sqrt() * e + e * e).sum() + bound(s, s, terms * nvox + rows + 2, 0.0))
+        else:
+            tight.append(bnd[-1])
+    for j, m in ((jh, mh), (js, ms)):
+        for val, b in ((j[:, :6].abs(), bound(j[:, :6], m[:, :6], K_STENCIL, 0.0)),
+                       (j[:, 6:], bound(j[:, 6:], m[:, 6:], K_STENCIL, 0.0)),
+                       (d3(j).abs(), bound(d3(j), d3(m), K_STENCIL + 2, 0.0)),
+                       (d2(j).abs(), bound(d2(j), d2(m), K_STENCIL + 1, 0.0))):
+            ref.append(_nanmax(val))
+            fin = b[torch.isfinite(b)]
+            bnd.append(fin.max() if fin.numel() else torch.tensor(TINY, dtype=torch.float64))
+    if tight_sums:
+        return torch.stack(ref), torch.stack(bnd), torch.stack(tight)
+    return torch.stack(ref), torch.stack(bnd)
+
+
+def ref_physics_residual(hr, sr, x, y, zc, coef, jac=None):
+    """the first launch of ``wsr_physics_loss_bwd``: r[k] = 2 coef_g (J_sr[k] - J_hr[k]) with g = 0 for k < 6, 1 for
+    k >= 6, plus 2 coef_2 (div3_sr - div3_hr) on channels 0, 4, 8 and 2 coef_3 (div2_sr - div2_hr) on channels 0, 4
+    (physics_loss.hip :160-167).  A coefficient that is exactly zero drops its term, whatever the Jacobians hold.
+    ``jac``: ((J_hr, M_hr), (J_sr, M_sr)) of ``ref_wind_gradient`` where the caller has them already.
+    Returns (r, A); bound with K_RESIDUAL."""
+    cf = [2.0 * float(v) for v in _d(coef)[:4]]
+    (jh, mh), (js, ms) = jac if jac is not None else (ref_wind_gradient(hr, x, y, zc), ref_wind_gradient(sr, x, y, zc))
+    r, a = torch.zeros_like(js), torch.zeros_like(js)
+    for g, sl in ((cf[0], slice(0, 6)), (cf[1], slice(6, 9))):
+        if g != 0.0:
+            r[:, sl] = g * (js[:, sl] - jh[:, sl])
+            a[:, sl] = abs(g) * (ms[:, sl] + mh[:, sl])
+    for g, chans in ((cf[2], (0, 4, 8)), (cf[3], (0, 4))):
+        if g != 0.0:
+            t = g * sum(js[:, k] - jh[:, k] for k in chans)
+            ta = abs(g) * sum(ms[:, k] + mh[:, k] for k in chans)
+            for k in chans:
+                r[:, k] += t
+                a[:, k] += ta
+    return r, a
+
+
+def ref_physics_adjoint(res, hr, sr, x, y, zc, coef):
+    """the second launch: dsr = adjoint of the stencils applied to ``res`` (skipped altogether when coef[0..3] are all
+    zero: 1 / dz of two equal levels must not meet the zeros) + coef[4] sign(d) + 2 coef[5] d, d = SR - HR, each pixel
+    term only where its coefficient is not zero.  Returns (dsr, A); bound with K_DSR."""
+    cf = [float(v) for v in _d(coef)]
+    d = _d(sr) - _d(hr)
+    if any(v != 0.0 for v in cf[:4]):
+        v, a = ref_wind_gradient_bwd(res, x, y, zc)
+    else:
+        v, a = torch.zeros_like(d), torch.zeros_like(d)
+    if cf[4] != 0.0:
+        v, a = v + cf[4] * torch.sign(d), a + abs(cf[4]) * torch.sign(d).abs()
+    if cf[5] != 0.0:
+        v, a = v + 2.0 * cf[5] * d, a + 2.0 * abs(cf[5]) * d.abs()
+    return v, a
+
+
+def ref_physics_bwd(hr, sr, x, y, zc, coef, residual=None, jac=None):
+    """``wsr_physics_loss_bwd``: ((residual, A), (dsr, A)).  ``residual``: the fp32 buffer the first launch wrote - dsr is
+    then referenced from it, as the BatchNorm stages are from their predecessor's tables - else the float64 one."""
+    r = ref_physics_residual(hr, sr, x, y, zc, coef, jac)
+    return r, ref_physics_adjoint(r[0] if residual is None else residual, hr, sr, x, y, zc, coef)
+
+
+def ref_zfold(t, bias, C, KZ, pz):
+    """y[b, c, ..., z] = bias[c] + sum_k t[b, c KZ + k, ..., z + k - pz] (taps outside [0, Z) absent); t (B, C KZ, ...,
+    Z).  Returns (y, A), A = |bias| + sum |t|; bound with K = KZ + 1."""
+    t = _d(t)
+    B, Z = t.shape[0], t.shape[-1]
+    t = t.reshape((B, C, KZ) + tuple(t.shape[2:]))
+    v = torch.zeros((B, C) + tuple(t.shape[3:]), dtype=torch.float64)
+    a = torch.zeros_like(v)
+    if bias is not None:
+        b = _d(bias).view((1, C) + (1,) * (v.dim() - 2))
+        v, a = v + b, a + b.abs()
+    for k in range(KZ):
+        s = _shift(t[:, :, k], k - pz)
+        v, a = v + s, a + s.abs()
+    return v, a
+
+
+def ref_zunfold(g, KZ, pz, c_fill):
+    """the adjoint of the fold as a copy: d[b, ..., z, c KZ + k] = g[b, c, ..., z - k + pz] or 0, channels from C KZ to
+    ``c_fill`` zero; g planar fp32 (B, C, X, Y, Z) -> fp32 (B, X, Y, Z, c_fill), every element a bit pattern of g or
+    +0.0 (no arithmetic: compared as bits)."""
+    B, C = g.shape[:2]
+    gi = g.detach().cpu().contiguous().view(torch.int32)
+    oi = torch.zeros((B,) + tuple(g.shape[2:]) + (c_fill,), dtype=torch.int32)
+    for c in range(C):
+        for k in range(KZ):
+            oi[..., c * KZ + k] = _shift(gi[:, c], pz - k)
+    return oi.view(torch.float32)
+
+
+def boundary_inputs(shape, coords="random", seed=0, descending=False):
+    """fp32 CPU operands (hr, sr, x, y, zc) of the content loss at ``shape`` = (B, X, Y, Z).  ``coords``: "random"
+    (non-uniform, spacings 50-150 in x and y, 6-36 in z), "uniform" (exactly), "near" (100 i + 1e-5 i^1.5: the centre
+    weight cancels almost completely; "near_odd": 100.37 i + 1e-5 i^1.5, whose spacings have low bits set, so that
+    their squares round) or "heights" (x, y random; columns start near 1000 m with spacings of 5-50 m
+    that vary per column, like the data's terrain-following levels).  The heights always differ between samples.
+    Fields: 10 + randn, SR = HR + 0.1 randn (the stencil cancels a mean of 10); ``descending``: both fall by about 2
+    per level, every z-derivative negative."""
+    B, X, Y, Z = shape
+    gen = torch.Generator().manual_seed(seed)
+    f64 = torch.float64
+
+    def axis(n, kind, step=100.0):
+        i = torch.arange(n, dtype=f64)
+        if kind == "uniform":
+            return 100.0 * i
+        if kind == "near":
+            return step * i + 1e-5 * i ** 1.5
+        return torch.cumsum(torch.rand(n, generator=gen, dtype=f64) + 0.5, 0) * 100.0
+
+    kind = coords if coords in ("uniform", "near") else "random"
+    if coords == "near_odd":
+        kind = "near"
+    step = 100.37 if coords == "near_odd" else 100.0
+    x, y = axis(X, kind, step), axis(Y, kind, step)
+    scale = (1.0 + torch.arange(B, dtype=f64)).view(B, 1, 1, 1, 1)
+    if coords == "uniform":
+        zc = (30.0 * torch.arange(Z, dtype=f64)).expand(B, 1, X, Y, Z) * scale
+    elif kind == "near":
+        zc = axis(Z, "near", step).expand(B, 1, X, Y, Z) * (0.5 + 0.5 * scale)
+    elif coords == "heights":
+        dz = 5.0 + 45.0 * torch.rand((B, 1, X, Y, Z), generator=gen, dtype=f64)
+        zc = 1000.0 + 50.0 * torch.rand((B, 1, X, Y, 1), generator=gen, dtype=f64) + torch.cumsum(dz, -1)
+    else:
+        zc = torch.cumsum(torch.rand((B, 1, X, Y, Z), generator=gen, dtype=f64) + 0.2, -1) * 30.0
+    hr = 10.0 + torch.randn((B, 3, X, Y, Z), generator=gen, dtype=f64)
+    if descending:
+        hr = 10.0 - 2.0 * torch.arange(Z, dtype=f64) + 0.1 * torch.randn((B, 3, X, Y, Z), generator=gen, dtype=f64)
+    sr = hr + (0.05 if descending else 0.1) * torch.randn((B, 3, X, Y, Z), generator=gen, dtype=f64)
+    return tuple(t.float().contiguous() for t in (hr, sr, x, y, zc))
+
+
+def plane_sum_rows(B, V, max_rows=512) -> tuple:
+    """(rv, bper, rows) of ``wsr_plane_sum`` (elementwise.hip :1783-1791): rv voxel slices per batch group of bper
+    samples, rows = rv * groups partial rows"""
+    rv = max(1, min(max_rows, (V + 16383) // 16384))
+    groups = max(1, min(B, max_rows // rv))
+    bper = -(-B // groups)
+    groups = -(-B // bper)
+    return rv, bper, rv * groups
+
+
+def ref_plane_sum(src):
+    """out[c] = sum over samples and voxels of a planar (B, C, ...) tensor.  Returns (ref, A), A the sum of magnitudes;
+    bound with K = B V + rows."""
+    s = _d(src)
+    s = s.reshape(s.shape[0], s.shape[1], -1)
+    return s.sum((0, 2)), s.abs().sum((0, 2))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

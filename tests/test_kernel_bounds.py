@@ -1183,3 +1183,510 @@ def test_bn_mask_sign_of_special_values_is_caught(bn_apply_case, which, v8):
     g = _emul_bwd_reduce(s.dy, s.y, s.x, s.mean, s.invstd, True, 0.2, flip=[(v, c)])[3].to(s.dt)
     _, _, _, ratio = kb.check_within(g, gref, gb)
     assert [(int(a), int(b)) for a, b in (ratio > 1.0).nonzero().tolist()] == [(v, c)]
+
+
+# ---- the network boundary: stencils, content loss, z-fold, plane sums - references, fp32 emulations, mutations ---------------
+
+BOUNDARY_SMALL = [(1, 1, 1, 1), (1, 1, 1, 2), (1, 2, 1, 1), (1, 1, 2, 1), (1, 2, 2, 2), (1, 3, 3, 3), (2, 1, 6, 5),
+                  (2, 5, 1, 6), (2, 5, 6, 1), (2, 5, 7, 9)]
+COEF = torch.tensor([0.31, -0.17, 0.23, 0.41, 0.136, 0.07])
+
+
+def _close(a, b, tol=1e-11):
+    torch.testing.assert_close(a, b, rtol=tol, atol=tol)
+
+
+@pytest.mark.parametrize("shape", [(1, 2, 2, 2), (1, 3, 3, 3), (2, 5, 7, 9), (2, 2, 6, 3)])
+@pytest.mark.parametrize("coords", ["random", "heights"])
+def test_boundary_references_equal_float64_autograd_of_the_oracle(shape, coords):
+    """``ref_wind_gradient``, its adjoint, the 14 statistics and d loss / d SR against ``oracle/physics.py`` and fp64
+    autograd of it (extents >= 2: the oracle has no axis of length 1)"""
+    from oracle import physics as ophys
+
+    hr, sr, x, y, zc = (t.double() for t in kb.boundary_inputs(shape, coords, seed=41))
+    srr = sr.clone().requires_grad_(True)
+    jh, js = ophys.wind_gradient(hr, x, y, zc), ophys.wind_gradient(srr, x, y, zc)
+    _close(kb.ref_wind_gradient(sr, x, y, zc)[0], js.detach())
+    gy = torch.randn(js.shape, generator=torch.Generator().manual_seed(3), dtype=f64)
+    (want,) = torch.autograd.grad((js * gy).sum(), srr, retain_graph=True)
+    _close(kb.ref_wind_gradient_bwd(gy, x, y, zc)[0], want)
+    d3 = lambda j: j[:, 0] + j[:, 4] + j[:, 8]  # noqa: E731
+    d2 = lambda j: j[:, 0] + j[:, 4]  # noqa: E731
+    sums = [((js[:, :6] - jh[:, :6]) ** 2).sum(), ((js[:, 6:] - jh[:, 6:]) ** 2).sum(), ((d3(jh) - d3(js)) ** 2).sum(),
+            ((d2(jh) - d2(js)) ** 2).sum(), (hr - srr).abs().sum(), ((hr - srr) ** 2).sum()]
+    mx = [f(j.detach()) for j in (jh, js) for f in (lambda j: j[:, :6].abs().max(), lambda j: j[:, 6:].max(),
+                                                    lambda j: d3(j).abs().max(), lambda j: d2(j).abs().max())]
+    ref, bnd = kb.ref_physics_stats(hr, sr, x, y, zc)
+    _close(ref, torch.stack([s.detach() for s in sums] + mx), 1e-10)
+    assert bool((bnd > 0).all())
+    coef = COEF.double()
+    (want,) = torch.autograd.grad(sum(c * s for c, s in zip(coef, sums)), srr)
+    (res, _), (dsr, _) = kb.ref_physics_bwd(hr, sr, x, y, zc, coef)
+    _close(dsr, want, 1e-10)
+    # the residual IS d loss / d J_sr
+    jl = js.detach().clone().requires_grad_(True)
+    loss = (coef[0] * ((jl[:, :6] - jh[:, :6]) ** 2).sum() + coef[1] * ((jl[:, 6:] - jh[:, 6:]) ** 2).sum()
+            + coef[2] * ((d3(jh) - d3(jl)) ** 2).sum() + coef[3] * ((d2(jh) - d2(jl)) ** 2).sum())
+    _close(res, torch.autograd.grad(loss, jl)[0], 1e-10)
+
+
+def test_boundary_reference_against_the_recorded_jacobians(golden):
+    """``ref_wind_gradient`` of the recorded HR / SR against the Jacobian stacks the reference project produced in fp32
+    (tests/golden/physics.npz), inside the stencil's own bound"""
+    g = golden("physics.npz")
+    T = lambda k: torch.from_numpy(g[k])  # noqa: E731
+    for src, want in (("HR", "grad_hr"), ("SR", "grad_sr")):
+        ref, M = kb.ref_wind_gradient(T(src), T("x"), T("y"), T("Z"))
+        kb.assert_within(T(want), ref, kb.bound(ref, M, kb.K_STENCIL, 0.0), f"recorded jacobian {src}")
+
+
+def test_boundary_references_on_an_axis_of_length_one():
+    for shape, dead in (((2, 1, 6, 5), 0), ((2, 5, 1, 6), 1), ((2, 5, 6, 1), 2), ((1, 1, 1, 1), None)):
+        hr, sr, x, y, zc = kb.boundary_inputs(shape, "random", seed=5)
+        J, M = kb.ref_wind_gradient(sr, x, y, zc)
+        for k in range(3):
+            if dead is None or k == dead:
+                assert not J[:, 3 * k:3 * k + 3].any() and not M[:, 3 * k:3 * k + 3].any()
+            else:
+                assert bool((M[:, 3 * k:3 * k + 3] > 0).all())
+        g = torch.randn(J.shape, dtype=f64)
+        if dead is not None:
+            g2 = g.clone()
+            g2[:, 3 * dead:3 * dead + 3] = 7.0  # the dead axis' gradient reaches nothing
+            assert torch.equal(kb.ref_wind_gradient_bwd(g, x, y, zc)[0], kb.ref_wind_gradient_bwd(g2, x, y, zc)[0])
+
+
+# -- the kernels' arithmetic in fp32, in their own order
+
+def _emul_rows(co, end_row_interior=False, contract=False):
+    """``deriv_row`` (stencil.h) along the last axis of fp32 coordinates, every operation rounded on its own;
+    ``contract``: hr * hr - hl * hl as the compiler may fuse it, fma(hr, hr, -(hl * hl)) - one rounding fewer, and a
+    centre weight that is the rounding error of hl * hl where hr == hl"""
+    n = co.shape[-1]
+    a, b, c = (torch.zeros_like(co) for _ in range(3))
+    if n < 2:
+        return a, b, c
+    if n >= 3:
+        hl, hr = co[..., 1:-1] - co[..., :-2], co[..., 2:] - co[..., 1:-1]
+        den = hl * hr * (hl + hr)
+        num = (hr.double() * hr.double() - (hl * hl).double()).float() if contract else hr * hr - hl * hl
+        a[..., 1:-1], b[..., 1:-1], c[..., 1:-1] = -(hr * hr) / den, num / den, (hl * hl) / den
+    h = co[..., 1] - co[..., 0]
+    b[..., 0], c[..., 0] = -1.0 / h, 1.0 / h
+    h = co[..., -1] - co[..., -2]
+    if end_row_interior:  # the last row takes the weights of the interior row below it
+        assert n >= 3
+        a[..., -1], b[..., -1], c[..., -1] = a[..., -2], b[..., -2], c[..., -2]
+    else:
+        a[..., -1], b[..., -1] = -1.0 / h, 1.0 / h
+    return a, b, c
+
+
+def _co(co, dim):
+    return co if co.dim() == 1 else co.movedim(dim, -1)
+
+
+def _emul_jacobian(f, x, y, zc, drop=None, end_row_interior=None, contract=False):
+    """``jacobian`` (physics_loss.hip :33) / ``wind_gradient_kernel``: (a f- + b f0) + c f+ per axis.  ``drop`` =
+    (channel 0..8, b, comp, x, y, z): the forward face tap (c f+) of that element is left out; ``end_row_interior``:
+    the axis (0..2) whose last row takes interior weights."""
+    out = []
+    for k, co in enumerate((x, y, zc)):
+        ff = f.movedim(2 + k, -1)
+        a, b, c = _emul_rows(_co(co, 2 + k), end_row_interior == k, contract)
+        ta, tb, tc = a * kb._shift(ff, -1), b * ff, c * kb._shift(ff, 1)
+        tc = tc.movedim(-1, 2 + k).clone()
+        if drop is not None and drop[0] // 3 == k:
+            assert drop[0] % 3 == drop[2]
+            tc[drop[1], drop[2], drop[3], drop[4], drop[5]] = 0.0
+        out.append((ta + tb).movedim(-1, 2 + k) + tc)
+    return torch.cat(out, 1)
+
+
+def _butterfly(v, op):
+    """the xor shuffles 32, 16, .., 1 over the last axis (64 lanes); every lane ends with the same value"""
+    idx = torch.arange(64)
+    for off in (32, 16, 8, 4, 2, 1):
+        v = op(v, v[..., idx ^ off])
+    return v[..., 0]
+
+
+def _emul_stats_kernel(hr, sr, x, y, zc, zmax_start=-math.inf, jac=_emul_jacobian):
+    """``physics_stats_kernel`` + ``physics_stats_final_kernel``: per-thread partials over its trips, the wave
+    butterflies, the four waves in order, then per statistic one wave over the rows (sums in double) -> (14,) fp32"""
+    jh, js = jac(hr, x, y, zc), jac(sr, x, y, zc)
+    B = hr.shape[0]
+    nvox = hr.numel() // 3
+    grid = kb.physics_rows(nvox)
+    nthr = grid * 256
+    trips = -(-nvox // nthr)
+    vox = lambda t: t.movedim(1, -1).reshape(nvox, t.shape[1])  # (voxel, channel)  # noqa: E731
+    jh, js = vox(jh), vox(js)
+    d = js - jh
+    h2, s2 = jh[:, 0] + jh[:, 4], js[:, 0] + js[:, 4]
+    h3, s3 = h2 + jh[:, 8], s2 + js[:, 8]
+    dp = vox(hr) - vox(sr)
+    sum_terms = [(d * d)[:, :6], (d * d)[:, 6:], ((h3 - s3) * (h3 - s3))[:, None], ((h2 - s2) * (h2 - s2))[:, None],
+                 dp.abs(), dp * dp]
+    max_terms = [jh[:, :6].abs(), jh[:, 6:], h3.abs()[:, None], h2.abs()[:, None],
+                 js[:, :6].abs(), js[:, 6:], s3.abs()[:, None], s2.abs()[:, None]]
+    starts = [0.0, zmax_start, 0.0, 0.0, 0.0, zmax_start, 0.0, 0.0]
+
+    def per_thread(t, start, op):
+        acc = torch.full((nthr,), start, dtype=torch.float32)
+        valid = torch.zeros(trips * nthr, dtype=torch.bool)
+        valid[:nvox] = True
+        pad = torch.zeros(trips * nthr, t.shape[1])
+        pad[:nvox] = t
+        for i in range(trips):
+            for c in range(t.shape[1]):
+                nxt = op(acc, pad[i * nthr:(i + 1) * nthr, c])
+                acc = torch.where(valid[i * nthr:(i + 1) * nthr], nxt, acc)
+        return acc.view(grid, 4, 64)
+
+    out = []
+    for t in sum_terms:
+        w = _butterfly(per_thread(t, 0.0, torch.add), torch.add)  # (grid, 4)
+        part = ((w[:, 0] + w[:, 1]) + w[:, 2]) + w[:, 3]
+        lanes = torch.zeros(64, dtype=f64)
+        for r in range(grid):
+            lanes[r % 64] = lanes[r % 64] + part[r].double()
+        out.append(_butterfly(lanes, torch.add).float())
+    for t, st in zip(max_terms, starts):
+        w = _butterfly(per_thread(t, st, torch.maximum), torch.maximum)
+        part = torch.maximum(torch.maximum(torch.maximum(w[:, 0], w[:, 1]), w[:, 2]), w[:, 3])
+        lanes = part[0].repeat(64)
+        for r in range(grid):
+            lanes[r % 64] = torch.maximum(lanes[r % 64], part[r])
+        out.append(_butterfly(lanes, torch.maximum))
+    return torch.stack(out)
+
+
+def _emul_residual(hr, sr, x, y, zc, coef, div2_on_8=False, jac=_emul_jacobian):
+    """``physics_residual_kernel`` (:139)"""
+    jh, js = jac(hr, x, y, zc), jac(sr, x, y, zc)
+    g = [2.0 * c for c in coef[:4]]
+    o = torch.zeros_like(js)
+    for k in range(9):
+        gg = g[0] if k < 6 else g[1]
+        if gg != 0:
+            o[:, k] = gg * (js[:, k] - jh[:, k])
+    d2 = (js[:, 0] + js[:, 4]) - (jh[:, 0] + jh[:, 4])
+    d3 = d2 + (js[:, 8] - jh[:, 8])
+    t3 = g[2] * d3 if g[2] != 0 else torch.zeros_like(d3)
+    t = t3 + (g[3] * d2 if g[3] != 0 else torch.zeros_like(d2))
+    o[:, 0] += t
+    o[:, 4] += t
+    o[:, 8] += t if div2_on_8 else t3
+    return o
+
+
+def _emul_adjoint(g, x, y, zc, weight_of_row_x=False):
+    """``wind_gradient_bwd_kernel`` (:1142): acc = 0, then per axis b_j g_j, c_{j-1} g_{j-1}, a_{j+1} g_{j+1} in that
+    order.  ``weight_of_row_x``: along x the lower neighbour's weight is taken from row x, not x - 1."""
+    acc = torch.zeros_like(g[:, :3])
+    for k, co in enumerate((x, y, zc)):
+        gg = g[:, 3 * k:3 * k + 3].movedim(2 + k, -1)
+        a, b, c = _emul_rows(_co(co, 2 + k))
+        lower = c * kb._shift(gg, -1) if (weight_of_row_x and k == 0) else kb._shift(c * gg, -1)
+        lower[..., 0] = 0.0
+        for term in (b * gg, lower, kb._shift(a * gg, 1)):
+            acc = acc + term.movedim(-1, 2 + k)
+    return acc
+
+
+def _emul_dsr(res, hr, sr, x, y, zc, coef, sign0=0.0, **kw):
+    """``physics_adjoint_kernel`` (:175)"""
+    phys = any(float(c) != 0 for c in coef[:4])
+    acc = _emul_adjoint(res, x, y, zc, **kw) if phys else torch.zeros_like(sr)
+    d = sr - hr
+    sgn = torch.where(d > 0, 1.0, torch.where(d < 0, -1.0, sign0)).float()
+    c1, c2 = coef[4], 2.0 * coef[5]
+    pix = (c1 * sgn if c1 != 0 else torch.zeros_like(d)) + (c2 * d if c2 != 0 else torch.zeros_like(d))
+    return acc + pix
+
+
+def _near_uniform_case():
+    """the nearly uniform grid with one large centre value: b = (hr^2 - hl^2) / den cancels almost completely there"""
+    hr, sr, x, y, zc = kb.boundary_inputs((1, 6, 7, 40), "near_odd", seed=9)
+    sr[0, :, 3, 3, 20] = 1.0e6
+    return hr, sr, x, y, zc
+
+
+def _boundary_cases():
+    for shape in BOUNDARY_SMALL:
+        for coords in ("random", "uniform", "near", "heights"):
+            yield f"{shape} {coords}", kb.boundary_inputs(shape, coords, seed=sum(shape))
+    yield "near uniform", _near_uniform_case()
+
+
+def test_stencil_emulations_are_within_the_bound():
+    """wind gradient forward and adjoint, residual and d loss / d SR in fp32 in the kernels' order, on the matrix's
+    small shapes and on the nearly uniform grid: K = 12, 19, 23, 24"""
+    worst = {}
+    for name, (hr, sr, x, y, zc) in _boundary_cases():
+        J, M = kb.ref_wind_gradient(sr, x, y, zc)
+        r = {"J": kb.assert_within(_emul_jacobian(sr, x, y, zc), J, kb.bound(J, M, kb.K_STENCIL, 0.0), f"emul wind_gradient[{name}]")}
+        g = torch.randn(J.shape, generator=torch.Generator().manual_seed(1))
+        ref, A = kb.ref_wind_gradient_bwd(g, x, y, zc)
+        r["adj"] = kb.assert_within(_emul_adjoint(g, x, y, zc), ref, kb.bound(ref, A, kb.K_ADJOINT, 0.0), f"emul wind_gradient_bwd[{name}]")
+        res = _emul_residual(hr, sr, x, y, zc, COEF)
+        (rr, ra), (dr, da) = kb.ref_physics_bwd(hr, sr, x, y, zc, COEF, residual=res)
+        r["res"] = kb.assert_within(res, rr, kb.bound(rr, ra, kb.K_RESIDUAL, 0.0), f"emul residual[{name}]")
+        r["dsr"] = kb.assert_within(_emul_dsr(res, hr, sr, x, y, zc, COEF), dr, kb.bound(dr, da, kb.K_DSR, 0.0), f"emul dsr[{name}]")
+        for k, v in r.items():
+            worst[k] = max(worst.get(k, 0.0), v)
+    print("[ratio] stencil emulations, worst |err|/bound:", {k: round(v, 4) for k, v in worst.items()})
+
+
+def test_pre_cancellation_magnitude_is_what_keeps_the_near_uniform_grid_inside():
+    """with |b| |f_i| in place of (hr^2 + hl^2) / |den| |f_i| the SAME correct emulation leaves the bound by orders of
+    magnitude at the large centre value: a hole in the bound, not an error of the arithmetic"""
+    hr, sr, x, y, zc = _near_uniform_case()
+    J, M = kb.ref_wind_gradient(sr, x, y, zc)
+    s = sr.double()
+    weak = []
+    for k, co in enumerate((x, y, zc)):
+        ff = s.movedim(2 + k, -1)
+        a, b, c, _ = kb._stencil_rows(_co(co.double(), 2 + k))
+        weak.append((a.abs() * kb._shift(ff, -1).abs() + b.abs() * ff.abs() + c.abs() * kb._shift(ff, 1).abs()).movedim(-1, 2 + k))
+    for contract in (False, True):
+        got = _emul_jacobian(sr, x, y, zc, contract=contract)
+        good = kb.assert_within(got, J, kb.bound(J, M, kb.K_STENCIL, 0.0), f"near-uniform grid, contract {contract}")
+        bad, worst, top, _ = kb.check_within(got, J, kb.bound(J, torch.cat(weak, 1), kb.K_STENCIL, 0.0))
+        print(f"[ratio] near-uniform grid, contract {contract}: {good:.3g} of the bound, {worst:.3g} of the one from |b|")
+        assert bad and worst > 10.0 and all(kb._coords(i, tuple(J.shape), "act").endswith("x=3, y=3, z=20)") for i in top[:bad])
+
+
+STATS_SHAPES = BOUNDARY_SMALL + [(1, 20, 41, 20)]
+
+
+@pytest.mark.parametrize("shape", STATS_SHAPES, ids=str)
+def test_stats_emulation_is_within_the_bound(shape):
+    worst = 0.0
+    for coords in (("random", "heights") if shape != (1, 20, 41, 20) else ("random",)):
+        hr, sr, x, y, zc = kb.boundary_inputs(shape, coords, seed=7 + sum(shape))
+        ref, bnd, tight = kb.ref_physics_stats(hr, sr, x, y, zc, tight_sums=True)
+        got = _emul_stats_kernel(hr, sr, x, y, zc)
+        kb.assert_within(got, ref, bnd, f"emul physics_stats[{shape} {coords}]")
+        worst = max(worst, kb.assert_within(got[:6], ref[:6], tight, f"emul physics_stats sums, propagated[{shape} {coords}]"))
+        assert bool((tight <= bnd[:6]).all())
+    hr, sr, x, y, zc = _near_uniform_case()
+    ref, bnd, tight = kb.ref_physics_stats(hr, sr, x, y, zc, tight_sums=True)
+    got = _emul_stats_kernel(hr, sr, x, y, zc)
+    kb.assert_within(got, ref, bnd, "emul physics_stats[near uniform]")
+    kb.assert_within(got[:6], ref[:6], tight, "emul physics_stats sums, propagated[near uniform]")
+    print(f"[ratio] physics_stats emulation {shape}: {worst:.3g} of the sums' narrower bound")
+
+
+def _violations(got, ref, bnd):
+    return [tuple(i) for i in (kb.check_within(got, ref, bnd)[3] > 1.0).nonzero().tolist()]
+
+
+def test_one_dropped_face_tap_at_one_voxel_is_caught():
+    hr, sr, x, y, zc = kb.boundary_inputs((2, 5, 7, 9), "random", seed=2)
+    J, M = kb.ref_wind_gradient(sr, x, y, zc)
+    bnd = kb.bound(J, M, kb.K_STENCIL, 0.0)
+    for ch, at in ((0, (1, 0, 3, 6, 8)), (4, (0, 1, 4, 5, 0)), (8, (1, 2, 0, 0, 7))):  # the last interior row of each axis
+        assert _violations(_emul_jacobian(sr, x, y, zc, drop=(ch,) + at), J, bnd) == [(at[0], ch, at[2], at[3], at[4])]
+    # the residual and the statistics see it too: channel 0 carries both divergence terms
+    drop = (0, 1, 0, 3, 6, 8)
+    jac = lambda f, *a: _emul_jacobian(f, *a, drop=drop if f is sr else None)  # noqa: E731
+    (rr, ra), _ = kb.ref_physics_bwd(hr, sr, x, y, zc, COEF)
+    rb = kb.bound(rr, ra, kb.K_RESIDUAL, 0.0)
+    assert not _violations(_emul_residual(hr, sr, x, y, zc, COEF), rr, rb)
+    assert _violations(_emul_residual(hr, sr, x, y, zc, COEF, jac=jac), rr, rb) == [(1, k, 3, 6, 8) for k in (0, 4, 8)]
+
+
+def test_interior_row_used_at_an_end_is_caught():
+    hr, sr, x, y, zc = kb.boundary_inputs((2, 5, 7, 9), "random", seed=2)
+    J, M = kb.ref_wind_gradient(sr, x, y, zc)
+    bnd = kb.bound(J, M, kb.K_STENCIL, 0.0)
+    for axis in range(3):
+        bad = _violations(_emul_jacobian(sr, x, y, zc, end_row_interior=axis), J, bnd)
+        last = sr.shape[2 + axis] - 1
+        assert bad and all(i[1] // 3 == axis and i[2 + axis] == last for i in bad)
+        assert len(bad) == sr.numel() // sr.shape[2 + axis], "every element of the end face"
+
+
+def test_adjoint_neighbour_weight_of_the_wrong_row_is_caught():
+    hr, sr, x, y, zc = kb.boundary_inputs((2, 5, 7, 9), "random", seed=2)
+    g = torch.randn((2, 9, 5, 7, 9), generator=torch.Generator().manual_seed(4))
+    g[:, 3:] = 0.0  # the x axis alone: no other axis' magnitude covers the error
+    ref, A = kb.ref_wind_gradient_bwd(g, x, y, zc)
+    bnd = kb.bound(ref, A, kb.K_ADJOINT, 0.0)
+    assert not _violations(_emul_adjoint(g, x, y, zc), ref, bnd)
+    bad = _violations(_emul_adjoint(g, x, y, zc, weight_of_row_x=True), ref, bnd)
+    assert bad and all(i[2] >= 1 for i in bad) and len(bad) == 2 * 3 * 4 * 7 * 9  # every element with a lower neighbour
+    # through the content loss, all axes live: still every such x-row is reported
+    res = _emul_residual(hr, sr, x, y, zc, COEF)
+    dr, da = kb.ref_physics_adjoint(res, hr, sr, x, y, zc, COEF)
+    db = kb.bound(dr, da, kb.K_DSR, 0.0)
+    assert not _violations(_emul_dsr(res, hr, sr, x, y, zc, COEF), dr, db)
+    bad = _violations(_emul_dsr(res, hr, sr, x, y, zc, COEF, weight_of_row_x=True), dr, db)
+    assert len(bad) > 0.5 * 2 * 3 * 4 * 7 * 9 and all(i[2] >= 1 for i in bad)
+
+
+def test_div2_term_on_channel_8_is_caught():
+    hr, sr, x, y, zc = kb.boundary_inputs((2, 5, 7, 9), "random", seed=2)
+    (rr, ra), _ = kb.ref_physics_bwd(hr, sr, x, y, zc, COEF)
+    bad = _violations(_emul_residual(hr, sr, x, y, zc, COEF, div2_on_8=True), rr, kb.bound(rr, ra, kb.K_RESIDUAL, 0.0))
+    assert bad and all(i[1] == 8 for i in bad) and len(bad) > 0.95 * 630
+    one_hot = torch.tensor([0.0, 0.0, 0.0, 0.41, 0.0, 0.0])  # the route on its own: channel 8 must stay +0.0
+    (rr, ra), _ = kb.ref_physics_bwd(hr, sr, x, y, zc, one_hot)
+    assert not rr[:, 8].any()
+    bad = _violations(_emul_residual(hr, sr, x, y, zc, one_hot, div2_on_8=True), rr, kb.bound(rr, ra, kb.K_RESIDUAL, 0.0))
+    assert bad and all(i[1] == 8 for i in bad)
+
+
+@pytest.mark.parametrize("shape", [(2, 5, 7, 9), (1, 1, 1, 2)], ids=str)
+def test_signed_maximum_started_at_zero_is_caught(shape):
+    """all z-derivatives negative: maxima 1 and 5 are negative, and a start value of 0 - which idle lanes and the first
+    comparison would keep - is reported at exactly those two entries"""
+    hr, sr, x, y, zc = kb.boundary_inputs(shape, "heights", seed=6, descending=True)
+    ref, bnd = kb.ref_physics_stats(hr, sr, x, y, zc)
+    assert float(ref[6 + 1]) < 0 and float(ref[6 + 5]) < 0
+    assert not _violations(_emul_stats_kernel(hr, sr, x, y, zc), ref, bnd)
+    assert _violations(_emul_stats_kernel(hr, sr, x, y, zc, zmax_start=0.0), ref, bnd) == [(7,), (11,)]
+
+
+def test_sign_of_zero_returned_as_one_is_caught():
+    hr, sr, x, y, zc = kb.boundary_inputs((2, 5, 7, 9), "random", seed=2)
+    at = [(0, 0, 0, 0, 0), (1, 2, 4, 6, 8), (0, 1, 2, 3, 4)]
+    for i in at:
+        sr[i] = hr[i]
+    for coef in (COEF, torch.tensor([0.0, 0.0, 0.0, 0.0, 0.136, 0.0])):
+        res = _emul_residual(hr, sr, x, y, zc, coef)
+        dr, da = kb.ref_physics_adjoint(res, hr, sr, x, y, zc, coef)
+        db = kb.bound(dr, da, kb.K_DSR, 0.0)
+        assert not _violations(_emul_dsr(res, hr, sr, x, y, zc, coef), dr, db)
+        assert sorted(_violations(_emul_dsr(res, hr, sr, x, y, zc, coef, sign0=1.0), dr, db)) == sorted(at)
+
+
+def test_nan_in_sr_reaches_the_sr_maxima_and_the_sums_only():
+    hr, sr, x, y, zc = kb.boundary_inputs((2, 5, 7, 9), "random", seed=2)
+    sr[-1, 0, -1, -1, -1] = float("nan")  # component u of the last voxel: it enters every SR statistic
+    ref, _ = kb.ref_physics_stats(hr, sr, x, y, zc)
+    got = _emul_stats_kernel(hr, sr, x, y, zc)
+    want = [True] * 6 + [False] * 4 + [True] * 4
+    assert torch.isnan(ref).tolist() == want and torch.isnan(got).tolist() == want
+
+
+# -- z-fold and plane sums
+
+def _emul_zfold(t, bias, C, KZ, pz, drop=None):
+    """``zfold_kernel`` (:1005): acc = bias, then the taps in order.  ``drop`` = (b, c, x, y, z): that output leaves out
+    its tap at z + kz - pz = Z - 1."""
+    B, Z = t.shape[0], t.shape[-1]
+    tt = t.reshape((B, C, KZ) + tuple(t.shape[2:]))
+    acc = torch.zeros((B, C) + tuple(t.shape[2:]))
+    if bias is not None:
+        acc = acc + bias.view(1, C, 1, 1, 1)
+    for k in range(KZ):
+        s = kb._shift(tt[:, :, k], k - pz)
+        if drop is not None and drop[4] + k - pz == Z - 1:
+            s[drop] = 0.0
+        acc = acc + s
+    return acc
+
+
+ZFOLD_SHAPES = [(2, 3, 5, 2, 4, 3, 7), (1, 1, 1, 0, 1, 1, 1), (2, 3, 5, 0, 3, 2, 6), (2, 3, 5, 4, 3, 2, 6),
+                (1, 2, 5, 2, 3, 3, 2), (1, 3, 3, 1, 2, 2, 1)]
+
+
+def _zfold_case(B, C, KZ, pz, X, Y, Z, seed=0):
+    gen = torch.Generator().manual_seed(seed)
+    return 10.0 + torch.randn((B, C * KZ, X, Y, Z), generator=gen), torch.randn(C, generator=gen)
+
+
+@pytest.mark.parametrize("row", ZFOLD_SHAPES, ids=str)
+def test_zfold_emulation_is_within_the_bound_and_equals_a_direct_sum(row):
+    B, C, KZ, pz, X, Y, Z = row
+    t, bias = _zfold_case(*row)
+    for bb in (bias, None):
+        ref, A = kb.ref_zfold(t, bb, C, KZ, pz)
+        direct = torch.zeros_like(ref)
+        for c in range(C):
+            for z in range(Z):
+                for k in range(KZ):
+                    if 0 <= z + k - pz < Z:
+                        direct[:, c, :, :, z] += t[:, c * KZ + k, :, :, z + k - pz].double()
+        _close(ref, direct + (0 if bb is None else bb.double().view(1, C, 1, 1, 1)))
+        kb.assert_within(_emul_zfold(t, bb, C, KZ, pz), ref, kb.bound(ref, A, KZ + 1, 0.0), f"emul zfold[{row}]")
+    # the adjoint as a copy: <zfold(t), g> = <t, zunfold(g)> exactly in float64
+    g = torch.randn((B, C, X, Y, Z), generator=torch.Generator().manual_seed(1))
+    d = kb.ref_zunfold(g, KZ, pz, C * KZ + 2)
+    assert not d[..., C * KZ:].any()
+    lhs = (kb.ref_zfold(t, None, C, KZ, pz)[0] * g.double()).sum()
+    rhs = (t.double().permute(0, 2, 3, 4, 1) * d[..., :C * KZ].double()).sum()
+    _close(lhs, rhs, 1e-10)
+
+
+def test_zfold_dropped_tap_at_the_last_level_is_caught():
+    row = (2, 3, 5, 2, 4, 3, 7)
+    B, C, KZ, pz, X, Y, Z = row
+    t, bias = _zfold_case(*row)
+    ref, A = kb.ref_zfold(t, bias, C, KZ, pz)
+    bnd = kb.bound(ref, A, KZ + 1, 0.0)
+    for at in ((1, 2, 3, 2, 6), (0, 0, 0, 0, 4)):  # z = Z - 1 (its centre tap) and z = 4 (its last tap)
+        assert _violations(_emul_zfold(t, bias, C, KZ, pz, drop=at), ref, bnd) == [at]
+
+
+def _emul_plane_sum(src, drop_last_of_group=None):
+    """``plane_sum_kernel`` (:1091) + ``chan_sum_final_kernel``: 256 threads per (channel, row) walk the samples of the
+    row's batch group and its voxel slice, butterfly, (sh0 + sh1) + (sh2 + sh3), then the rows.
+    ``drop_last_of_group``: that batch group stops one sample early."""
+    B, C = src.shape[:2]
+    s = src.reshape(B, C, -1)
+    V = s.shape[2]
+    rv, bper, rows = kb.plane_sum_rows(B, V)
+    per = -(-V // rv)
+    part = torch.zeros(rows, C)
+    for row in range(rows):
+        sl, bg = row % rv, row // rv
+        v0, v1 = sl * per, min(sl * per + per, V)
+        b0, b1 = bg * bper, min(bg * bper + bper, B)
+        if drop_last_of_group == bg:
+            b1 -= 1
+        n = max(v1 - v0, 0)
+        trips = max(-(-n // 256), 1)
+        pad = torch.zeros(max(b1 - b0, 0), C, trips * 256)
+        pad[:, :, :n] = s[b0:b1, :, v0:v1]
+        acc = torch.zeros(C, 256)
+        for b in range(pad.shape[0]):
+            for i in range(trips):
+                acc = acc + pad[b, :, i * 256:(i + 1) * 256]
+        w = _butterfly(acc.view(C, 4, 64), torch.add)
+        part[row] = (w[:, 0] + w[:, 1]) + (w[:, 2] + w[:, 3])
+    return _emul_rows_sum(part), rows, bper
+
+
+def _plane_case(B, C, V, seed=0):
+    x = torch.randn((B, C, V), generator=torch.Generator().manual_seed(seed))
+    x[:, C // 2] += 1000.0  # one channel at 1000 +- 1
+    return x
+
+
+@pytest.mark.parametrize("B,C,V", [(1, 1, 1), (1, 3, 16385), (5, 3, 1000), (600, 3, 64), (601, 3, 64), (3, 1024, 300)])
+def test_plane_sum_emulation_is_within_the_bound(B, C, V):
+    x = _plane_case(B, C, V)
+    got, rows, bper = _emul_plane_sum(x)
+    ref, A = kb.ref_plane_sum(x)
+    w = kb.assert_within(got, ref, kb.bound(ref, A, B * V + rows, 0.0), f"emul plane_sum[{B}x{C}x{V}]")
+    print(f"[ratio] plane_sum emulation ({B}, {C}, {V}): rows {rows} bper {bper} ratio {w:.3g}")
+
+
+def test_plane_sum_last_sample_of_a_ragged_group_left_out_is_caught():
+    B, C, V = 601, 3, 64
+    rv, bper, rows = kb.plane_sum_rows(B, V)
+    assert (rv, bper, rows) == (1, 2, 301) and B % bper == 1, "the last group holds one sample of two"
+    x = _plane_case(B, C, V)
+    ref, A = kb.ref_plane_sum(x)
+    bnd = kb.bound(ref, A, B * V + rows, 0.0)
+    assert not _violations(_emul_plane_sum(x)[0], ref, bnd)
+    # 64 ordinary values out of 38 464 are below what a sum's bound can see in the randn channels (their A is
+    # 30 000, the loss about 8): the channel at 1000 shows it, as does a planted sample of magnitude 1000
+    assert (1,) in _violations(_emul_plane_sum(x, drop_last_of_group=rows - 1)[0], ref, bnd)
+    x[B - 1] += 1000.0
+    ref, A = kb.ref_plane_sum(x)
+    assert _violations(_emul_plane_sum(x, drop_last_of_group=rows - 1)[0], ref, kb.bound(ref, A, B * V + rows, 0.0)) == [(0,), (1,), (2,)]
