@@ -134,6 +134,70 @@ plane_sum 4e-5.  Every copy row (planar_to_ndhwc, ndhwc_to_planar, zunfold, fp32
 matched bit for bit: 0.  The fp32 emulations on the CPU reach 0.038 (Jacobian), 0.040 (adjoint), 0.040 (residual),
 0.045 (dsr), 0.015 (statistics).  No row exceeded its bound.
 
+The table Adam family (``ref_adam`` .. ``clip_coef``; test_optimizer_matrix.py): ``torch.optim.Adam``'s definition - L2
+weight decay, both bias corrections, eps outside the root - in float64 from the fp32 p, g, m, v the kernel receives and
+the hyper-parameters as Python doubles, rho = 0.  The bounds are propagated through ``adam_one`` (elementwise.hip :618)
+the way ``bn_finalize_bounds`` does it, not one (A, K) term:
+
+* m' = beta1 m + (1 - beta1)(g + wd p): K = 5 - wd p, the sum with g, the product with 1 - beta1, beta1 m, the sum -
+  on A_m = beta1 |m| + (1 - beta1)(|g| + wd |p|).  The eight ``AdamK`` constants (``adam_k`` :608) are doubles rounded
+  once: relative perturbations of factors A already holds.  They are counted in K: three of them (wd, 1 - beta1, beta1)
+  enter m', so the worst case is 8 u A_m, against LAMBDA sqrt(5) u A_m = 35.8 u A_m.
+* v' = beta2 v + (1 - beta2)(g + wd p)^2: K = 6 (the same plus the second product with g) on A_v, the same expression
+  on magnitudes - every term is non-negative, and A_v = v' unless g and wd p cancel.  Constants: wd twice, 1 - beta2,
+  beta2; worst case 10 u A_v against 39.2 u A_v.
+* the denominator sqrt(v') / sqrt(bc2) + eps takes v's bound through the root, |sqrt(v' + e) - sqrt(v')| over |e| <=
+  bound_v evaluated exactly (bound_v / (2 sqrt v') to first order, sqrt(bound_v) at v' = 0, and no blow-up between the
+  two), divided by sqrt(bc2), plus three relative roundings - the root, the quotient, the sum with eps - as
+  LAMBDA sqrt(3) u denom (the rounded sqrt(bc2) and eps are two more relative perturbations inside that term).
+* the quotient m' / denom: (bound_m + (A_m / denom) bound_denom) / (denom - bound_denom) - the first-order
+  bound_m / denom + (A_m / denom) relerr(denom) with the exact divisor - plus one rounding, LAMBDA u A_m / denom.
+* p' = p - step_size * that: step_size times the quotient's bound, plus K = 3 (the product, the difference, the
+  rounded step_size) on |p| + step_size A_m / denom.
+* with clipping (``coef``) the gradient is coef * g, rounded three times on its way (``K_CLIP_G``: total + 1e-6, the
+  quotient, the product): the written-back g' has K = 3 on |coef g|, and m' and v' take 3 and 6 more in K.  coef itself
+  is ``clip_coef``: float64 from the fp32 total the kernel wrote.
+* ``ref_grad_sqnorm``: K = n + 10, A the sum.  ``ref_clip_total``: the float64 root of the sum of the fp32 partials the
+  first launch wrote, K = n_jobs + 2 (the kernel adds in double and rounds the root once).
+* |g| = 1e-25: g^2 is zero in fp32 and 1e-50 in the reference; 2^-100 = 8e-31 covers the difference in v', and
+  sqrt(2^-100) = 9e-16 is nothing beside eps = 1e-8 in the denominator (test_kernel_bounds.py asserts both).
+
+The single-tensor entry ``wsr_adam_step`` (``adam_kernel`` :590) receives its hyper-parameters as fp32 and takes
+``1.f - beta2`` in fp32 (:597) - exact for the float it holds, but 1 - float(0.999) is 1.3e-5 (relative) off
+1 - 0.999: against the double hyper-parameters its exp_avg_sq leaves the bound 5.6-fold (test_kernel_bounds.py,
+``one_minus_beta2_in_fp32``).  It is therefore referenced from the fp32 values it receives (``f32_hyper``), where it
+sits where the table kernels sit; the table entry points take doubles and round 1 - beta once.  INTEGRATION.md says
+the same in the entry's row.
+
+Worst |err| / bound per label of test_optimizer_matrix.py on the MI355X beside the fp32 emulation on the CPU
+(test_kernel_bounds.py, in brackets): adam_multi p 0.039 [0.037], exp_avg 0.070 [0.075], exp_avg_sq 0.116 [0.114];
+adam_multi_clip p 0.036 [0.035], exp_avg 0.065 [0.064], exp_avg_sq 0.099 [0.070 on one tensor of 1027 elements; the
+launches cover 170 000 elements per row], its written-back g 0.051, total 0.0087 (0.0092 over the job counts 1 .. 600);
+grad_sqnorm_multi partials 0.029 (small jobs 0.036, with a spike 0.033); adam_step p 0.038, exp_avg 0.067, exp_avg_sq
+0.103; TableAdam.step over three steps p 0.036, exp_avg 0.067, exp_avg_sq 0.102, g 0.069, norm 0.001.  The shadow of
+the moving average against test_ema.py's ``step_bound`` (3 u, a worst-case count, not a LAMBDA bound) 0.72, as
+test_ema_gpu.py measures it.  As expected for fp32 results: a few hundredths to a tenth of the bound, and no label's
+GPU ratio above one and a half times its emulation's.  No row exceeded its bound.
+
+The glue of the backward pass (``ref_lrelu_bwd`` .. ``ref_chan_sum_partials``; test_glue_matrix.py), operands exact in
+bf16, rho of the stored type:
+
+* ``ref_lrelu_bwd``: g * (y > 0 ? 1 : slope) * chan_scale: K = 2 - slope * scale, then the product with g; where the
+  whole factor is 1 the element is returned bit for bit, a keep factor of 0 gives a zero of g's sign.
+* ``ref_chan_axpby``: alpha * src + beta * dst: K = 3 (two products, one sum), rho once; beta == 0 does not read dst.
+* ``ref_upsample2_bwd``: three additions, K = 3, A the sum of the four magnitudes.
+* ``ref_chan_sum``: K = nvox + rows (``chan_sum_geometry``), rho = 0, A = |scale| sum |x|; a row of the partial table
+  (``ref_chan_sum_partials``) K = ceil(nvox / rows) + lanes.  The engine's form - the partial rows reduced by
+  ``wsr_unpack_wgrad_reduce_multi`` - the same K = nvox + rows.
+
+Worst |err| / bound per label of test_glue_matrix.py on the MI355X (bf16 rows / fp32 rows; the CPU emulation in
+brackets): lrelu_bwd 0.966 / 0.044; chan_axpby 0.79 / 0.034 with beta = 0 (alpha * s of an 8-bit significand seldom
+lands near a tie) and 0.996 / 0.036 with beta on; upsample2_bwd 0.996 / 0.097; chan_sum 0.037 / 0.024 [0.035] at scale
+0.2 - the one-voxel row, where the product with the scale is the only rounding - and 0.001 / 0.005 [0.004] at scale 1
+(bf16-exact operands add without rounding until the sum outgrows 24 bits), its partial rows 0.012 / 0.058, with a spike
+0.001 / 0.002, the engine's form 0.001 / 0.001.  bf16 stores at the half-ulp limit, fp32 results at a few hundredths.
+No row exceeded its bound.
+
 A kernel bug that drops one tap at one voxel, loses one split or misplaces one channel chunk changes the elements it
 touches by a sizable fraction of A / sqrt(K), far above the bound; a whole-tensor relative L2 check averages such an
 error over every element and can miss it.
@@ -807,6 +871,181 @@ def boundary_inputs(shape, coords="random", seed=0, descending=False):
         hr = 10.0 - 2.0 * torch.arange(Z, dtype=f64) + 0.1 * torch.randn((B, 3, X, Y, Z), generator=gen, dtype=f64)
     sr = hr + (0.05 if descending else 0.1) * torch.randn((B, 3, X, Y, Z), generator=gen, dtype=f64)
     return tuple(t.float().contiguous() for t in (hr, sr, x, y, zc))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the table Adam family (test_optimizer_matrix.py)
+# ---------------------------------------------------------------------------------------------------------------------
+
+ADAM_CHUNK = 32768        # elements per job of the table (hip_ops.ADAM_CHUNK)
+K_ADAM_M, K_ADAM_V, K_ADAM_P = 5, 6, 3
+K_CLIP_G = 3              # the written-back gradient coef * g
+
+
+def adam_hyper(lr, betas, eps, wd, step, f32_hyper=False):
+    """the eight factors of one Adam step in float64 - (beta1, 1 - beta1, beta2, 1 - beta2, step_size = lr / bc1,
+    sqrt(bc2), eps, wd) - from Python doubles, as ``torch.optim.Adam`` holds them.  ``f32_hyper``: from the fp32 values
+    the single-tensor entry ``wsr_adam_step`` receives across its ABI (then 1 - float(beta) is exact in fp32 for beta
+    in [0.5, 1], and the kernel's ``1.f - beta`` equals it)."""
+    b1, b2 = betas
+    if f32_hyper:
+        lr, b1, b2, eps, wd = (_f32(s) for s in (lr, b1, b2, eps, wd))
+    bc1 = 1.0 - b1 ** step
+    bc2 = 1.0 - b2 ** step
+    return b1, 1.0 - b1, b2, 1.0 - b2, lr / bc1, math.sqrt(bc2), float(eps), float(wd)
+
+
+def ref_adam(p, g, m, v, lr, betas, eps, wd, step, coef=None, *, f32_hyper=False):
+    """one step of ``torch.optim.Adam`` (L2 weight decay, both bias corrections, eps outside the square root) in float64
+    from the fp32 tensors the kernel receives; ``coef``: the clip coefficient, the gradient is coef * g.
+    Returns ((p', bound), (m', bound), (v', bound)), the bounds propagated as the module docstring derives them."""
+    b1, omb1, b2, omb2, ss, bc2s, eps, wd = adam_hyper(lr, betas, eps, wd, step, f32_hyper)
+    p, g, m, v = (_d(t) for t in (p, g, m, v))
+    km, kv = K_ADAM_M, K_ADAM_V
+    if coef is not None:  # three roundings into coef * g (K_CLIP_G), once in m', twice in v'
+        g = float(coef) * g
+        km, kv = km + K_CLIP_G, kv + 2 * K_CLIP_G
+    ge = g + wd * p
+    ga = g.abs() + wd * p.abs()
+    m1 = b1 * m + omb1 * ge
+    v1 = b2 * v + omb2 * ge * ge
+    a_m = b1 * m.abs() + omb1 * ga
+    a_v = b2 * v.abs() + omb2 * ga * ga
+    bm, bv = bound(m1, a_m, km, 0.0), bound(v1, a_v, kv, 0.0)
+    s = v1.clamp_min(0.0).sqrt()
+    # |sqrt(v' + e) - sqrt(v')| for |e| <= bv, exactly: bv / (2 sqrt v') to first order, sqrt(bv) at v' = 0
+    bs = torch.maximum((v1.clamp_min(0.0) + bv).sqrt() - s, s - (v1 - bv).clamp_min(0.0).sqrt())
+    den = s / bc2s + eps
+    bden = bs / bc2s + LAMBDA * math.sqrt(3.0) * U_FP32 * den
+    q_mag = a_m / den
+    lo = (den - bden).clamp_min(TINY)
+    bq = (bm + q_mag * bden) / lo + LAMBDA * U_FP32 * q_mag
+    p1 = p - ss * (m1 / den)
+    bp = abs(ss) * bq + bound(p1, p.abs() + abs(ss) * q_mag, K_ADAM_P, 0.0)
+    return (p1, bp), (m1, bm), (v1, bv)
+
+
+def adam_case(n, step, seed, plant=True):
+    """fp32 CPU (p, g, m, v) of one tensor of n elements: p, g = randn; state zero at step 1, else m = 0.3 randn,
+    v = (0.5 randn)^2.  ``plant``: the designed elements at 0, 4 (n >> 2) (the first tail element), n - 1 and the first
+    and last element of a second chunk, in turn (starting with ``seed`` % 4): g = m = v = 0; g = 0, v = 0, m = 0.25;
+    g = +-1e-25 with v = 0; g = 1e15."""
+    gen = torch.Generator().manual_seed(seed)
+    p, g = torch.randn(n, generator=gen), torch.randn(n, generator=gen)
+    m, v = 0.3 * torch.randn(n, generator=gen), (0.5 * torch.randn(n, generator=gen)) ** 2
+    if step == 1:
+        m, v = torch.zeros(n), torch.zeros(n)
+    if plant:
+        pos = sorted({i for i in (0, 4 * (n >> 2), n - 1, ADAM_CHUNK, 2 * ADAM_CHUNK - 1) if 0 <= i < n})
+        for j, i in enumerate(pos):
+            kind = (j + seed) % 4
+            if kind == 0:
+                g[i], m[i], v[i] = 0.0, 0.0, 0.0
+            elif kind == 1:
+                g[i], v[i], m[i] = 0.0, 0.0, 0.25
+            elif kind == 2:
+                g[i], v[i] = (1e-25 if j % 2 else -1e-25), 0.0
+            else:
+                g[i] = 1e15
+    return p, g, m, v
+
+
+def adam_jobs(sizes):
+    """[(tensor index, first element, elements)] of the job table ``hip_ops.adam_job_table`` builds for tensors of
+    ``sizes`` elements: chunks of ``ADAM_CHUNK``"""
+    return [(i, off, min(ADAM_CHUNK, n - off)) for i, n in enumerate(sizes) for off in range(0, n, ADAM_CHUNK)]
+
+
+def ref_grad_sqnorm(g):
+    """sum of g^2 of one job's chunk in float64.  Returns (ref, bound) with K = n + 10 - n squares and additions over
+    the 4 accumulators of a thread, its (a0 + a1) + (a2 + a3), six butterfly steps and the four wave sums - rho = 0,
+    A = the sum itself (every term is non-negative)."""
+    g = _d(g)
+    s = (g * g).sum()
+    return s, bound(s, s, g.numel() + 10, 0.0)
+
+
+def ref_clip_total(partials):
+    """sqrt of the sum of the fp32 partials in float64 (the kernel adds them in double and rounds the root once).
+    Returns (ref, bound) with K = n_jobs + 2, A = the root."""
+    t = _d(partials).sum().sqrt()
+    return t, bound(t, t, partials.numel() + 2, 0.0)
+
+
+def clip_coef(total, max_norm):
+    """min(1, max_norm / (total + 1e-6)) in float64 from the fp32 ``total`` the kernel wrote and the fp32 ``max_norm``
+    and 1e-6 it computes with; NaN stays NaN, as ``c > 1 ? 1 : c`` leaves it.  1.0 for an infinite bound (measure
+    only)."""
+    if math.isinf(max_norm):
+        return 1.0
+    c = _f32(max_norm) / (float(total) + _f32(1e-6))
+    return 1.0 if c > 1.0 else c
+
+
+def ema_step_bound(d, e_old, p_new):
+    """the shadow's bound of test_ema.py (``step_bound``): 3 u (|d e| + |(1 - d) p|)"""
+    return 3 * U_FP32 * ((d * _d(e_old)).abs() + ((1.0 - d) * _d(p_new)).abs())
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the activation-gradient and bias-gradient glue (test_glue_matrix.py)
+# ---------------------------------------------------------------------------------------------------------------------
+
+def ref_lrelu_bwd(g, y, slope, chan_scale=None, vox_per_b=None):
+    """g * (y > 0 ? 1 : slope) * chan_scale[b, c] on window rows (nvox, C); sample b = voxel // vox_per_b.
+    Returns (ref, |ref|, factor); bound with K = 2 (slope * scale, then the product with g) and the stored type's rho;
+    where ``factor`` is exactly 1 the stored element is the input, bit for bit."""
+    f = _lrelu_mask(y, _f32(slope))
+    if chan_scale is not None:
+        nvox = f.shape[0]
+        b = torch.arange(nvox) // int(vox_per_b)
+        f = f * _d(chan_scale)[b]
+    r = _d(g) * f
+    return r, r.abs(), f
+
+
+def ref_chan_axpby(src, dst, alpha, beta):
+    """alpha * src + beta * dst (``dst`` not read when beta == 0).  Returns (ref, A); K = 3, rho once."""
+    al, be = _f32(alpha), _f32(beta)
+    s = _d(src)
+    v, a = al * s, abs(al) * s.abs()
+    if be != 0.0:
+        d = _d(dst)
+        v, a = v + be * d, a + abs(be) * d.abs()
+    return v, a
+
+
+def ref_upsample2_bwd(dy):
+    """the 2 x 2 sum in x and y of an NDHWC gradient (B, 2 Xi, 2 Yi, Zi, C) -> (B, Xi, Yi, Zi, C).  Returns (ref, A);
+    K = 3 (three additions), A = the sum of the four magnitudes."""
+    d = _d(dy)
+    B, X2, Y2, Z, C = d.shape
+    r = d.reshape(B, X2 // 2, 2, Y2 // 2, 2, Z, C)
+    return r.sum(dim=(2, 4)), r.abs().sum(dim=(2, 4))
+
+
+def chan_sum_geometry(C, nvox, max_rows=512):
+    """(groups, lanes, rows) of ``chan_sum_kernel`` as ``wsr_chan_sum`` launches it: 4-channel groups, voxel lanes per
+    workgroup 256 / groups, rows = min(512, ceil(nvox / (16 lanes))) workgroups = partial rows"""
+    groups = C // 4
+    lanes = 256 // groups
+    return groups, lanes, max(1, min(max_rows, -(-nvox // (16 * lanes))))
+
+
+def ref_chan_sum(x, scale=1.0):
+    """scale * sum over voxels of window rows (nvox, C).  Returns (ref, A), A = |scale| sum |x|; K = nvox + rows."""
+    x, sc = _d(x), _f32(scale)
+    return sc * x.sum(0), abs(sc) * x.abs().sum(0)
+
+
+def ref_chan_sum_partials(x, C, nvox):
+    """the partial table (rows, C) of ``chan_sum_kernel``: row r sums the voxels v with (v // lanes) % rows == r.
+    Returns (ref, A); a row holds at most ceil(nvox / rows) terms and ``lanes`` lane sums: K = that + lanes."""
+    _, lanes, rows = chan_sum_geometry(C, nvox)
+    x = _d(x)
+    r = (torch.arange(nvox) // lanes) % rows
+    ref = torch.zeros(rows, C, dtype=torch.float64).index_add_(0, r, x)
+    return ref, torch.zeros(rows, C, dtype=torch.float64).index_add_(0, r, x.abs())
 
 
 def plane_sum_rows(B, V, max_rows=512) -> tuple:

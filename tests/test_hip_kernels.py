@@ -1562,6 +1562,10 @@ def test_ordered_reduce_row_form_is_bit_identical(hip, monkeypatch):
         (9, 48, 125, 144, 144, 1.0),    # 5x5x5: the [Cin][taps] image does not fit the row form's LDS -> chunk form
         (5, 8, 27, 8, 3, 1.0),          # 3 of 8 stored channels
         (3, 16, 12, 20, 18, 0.5),       # channel tail inside a float4
+        (1, 1, 1, 128, 128, 1.0),       # the bias form (a (1, 1, nf) packed row -> (1, nf, 1)): a single copy
+        (12, 1, 1, 128, 128, 0.2),      # ur_sum_parts: the 8 + 4 tails
+        (31, 1, 1, 128, 128, 1.0),      # 16 + 8 + 4 + 3
+        (512, 1, 1, 128, 128, 0.2),     # every partial row of a capped channel sum
     ]
     jobs, refs = [], []
     for n, cout, taps, kpad, cin, scale in shapes:

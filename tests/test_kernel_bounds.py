@@ -1690,3 +1690,495 @@ def test_plane_sum_last_sample_of_a_ragged_group_left_out_is_caught():
     x[B - 1] += 1000.0
     ref, A = kb.ref_plane_sum(x)
     assert _violations(_emul_plane_sum(x, drop_last_of_group=rows - 1)[0], ref, kb.bound(ref, A, B * V + rows, 0.0)) == [(0,), (1,), (2,)]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the table Adam family: reference against torch.optim.Adam, fp32 emulations of the kernels' arithmetic, mutants
+# ---------------------------------------------------------------------------------------------------------------------
+
+ADAM_HYPER = [(8e-5, 0.5, 0.999, 1e-8, 0.0, 1), (8e-5, 0.9, 0.999, 1e-8, 0.01, 2), (1e-2, 0.5, 0.999, 1e-8, 0.01, 1000),
+              (0.5, 0.9, 0.99, 1e-8, 0.0, 100000)]
+ADAM_SIZES = [1, 2, 3, 4, 5, 7, 8, 255, 256, 257, 1023, 1024, 1025, 1027, 32767, 32768, 32769, 65541]
+
+
+def _adam_k(lr, b1, b2, eps, wd, step, *, step_off=0, omb2_f32=False, f32_hyper=False):
+    """the eight ``AdamK`` constants as fp32 tensors (``adam_k``, elementwise.hip :608): double arithmetic, rounded once"""
+    h = list(kb.adam_hyper(lr, (b1, b2), eps, wd, step - step_off, f32_hyper))
+    if step_off:  # (the decay factors are not the mutant's business)
+        h[:4] = kb.adam_hyper(lr, (b1, b2), eps, wd, step)[:4]
+    k = [_f(x) for x in h]
+    if omb2_f32:
+        k[3] = _f(1.0) - _f(b2)
+    return k
+
+
+def _fma(a, b, c):
+    """fp32 a * b + c with one rounding (the product of two fp32 values is exact in float64)"""
+    return (a.double() * b.double() + c.double()).float()
+
+
+def _emul_adam(p, g, m, v, k, *, contract=False, eps_inside=False, no_wd=False, decoupled=False, lr=None, tail_of=None):
+    """``adam_one`` (elementwise.hip :618) in fp32, operation for operation; ``contract``: with the fused
+    multiply-adds a compiler may form.  The switches are the mutants of the tests below; ``tail_of`` = n leaves the
+    elements from 4 (n >> 2) on as they were."""
+    b1, omb1, b2, omb2, ss, bc2s, eps, wd = k
+    p0, m0, v0 = p, m, v
+    if decoupled:
+        p = p * (_f(1.0) - _f(lr) * wd)
+    elif not no_wd and float(wd) != 0.0:
+        g = _fma(wd, p, g) if contract else g + wd * p
+    if contract:
+        m = _fma(b1, m, omb1 * g)
+        v = _fma(b2, v, omb2 * g * g)
+    else:
+        m = b1 * m + omb1 * g
+        v = b2 * v + omb2 * g * g
+    den = torch.sqrt(v + eps) / bc2s if eps_inside else torch.sqrt(v) / bc2s + eps
+    q = m / den
+    p = _fma(-ss, q, p) if contract else p - ss * q
+    if tail_of is not None:
+        t = 4 * (tail_of >> 2)
+        p, m, v = (torch.cat([a[:t], a0[t:]]) for a, a0 in ((p, p0), (m, m0), (v, v0)))
+    return p, m, v
+
+
+def _adam_ratios(got, ref):
+    """per output: (elements outside the bound, worst |err| / bound)"""
+    return [kb.check_within(a, r, b)[:2] for a, (r, b) in zip(got, ref)]
+
+
+def test_ref_adam_equals_torch_adam_in_float64():
+    """``kb.ref_adam`` iterated over four steps against ``torch.optim.Adam`` on float64 CPU tensors (single-tensor
+    form), parameters and both moments, for every hyper-parameter set's lr, betas and weight decay"""
+    for lr, b1, b2, eps, wd, _ in ADAM_HYPER:
+        gen = torch.Generator().manual_seed(3)
+        p0 = torch.randn(257, generator=gen)
+        w = p0.double().clone().requires_grad_(True)
+        opt = torch.optim.Adam([w], lr=lr, betas=(b1, b2), eps=eps, weight_decay=wd, foreach=False, fused=False)
+        p, m, v = p0.double(), torch.zeros(257, dtype=torch.float64), torch.zeros(257, dtype=torch.float64)
+        for step in range(1, 5):
+            g = torch.randn(257, generator=gen)
+            w.grad = g.double()
+            opt.step()
+            (p, _), (m, _), (v, _) = kb.ref_adam(p, g, m, v, lr, (b1, b2), eps, wd, step)
+            st = opt.state[w]
+            for a, b in ((p, w.detach()), (m, st["exp_avg"]), (v, st["exp_avg_sq"])):
+                assert float((a - b).abs().max()) <= 1e-13 * (1.0 + float(b.abs().max())), (lr, step)
+    # the clip coefficient is a plain factor on the gradient
+    g = torch.randn(9, generator=gen)
+    z = torch.zeros(9)
+    a = kb.ref_adam(z, g, z, z, 1e-2, (0.5, 0.999), 1e-8, 0.0, 1, coef=0.25)
+    b = kb.ref_adam(z, (0.25 * g.double()), z, z, 1e-2, (0.5, 0.999), 1e-8, 0.0, 1)
+    assert all(torch.equal(x[0], y[0]) for x, y in zip(a, b))
+    assert all(bool((x[1] >= y[1]).all()) for x, y in zip(a, b))  # (its three roundings widen the bound)
+
+
+@pytest.mark.parametrize("contract", [False, True], ids=["plain", "fma"])
+@pytest.mark.parametrize("hyper", ADAM_HYPER, ids=lambda h: f"lr{h[0]}-b{h[1]}-wd{h[4]}-t{h[5]}")
+def test_adam_emulation_is_within_the_bound(hyper, contract):
+    """fp32 ``adam_one`` over every size of the matrix with its planted elements; the worst ratios are the CPU column of
+    the calibration in kernel_bounds.py"""
+    lr, b1, b2, eps, wd, step = hyper
+    worst = [0.0, 0.0, 0.0]
+    for n in ADAM_SIZES:
+        p, g, m, v = kb.adam_case(n, step, n)
+        got = _emul_adam(p, g, m, v, _adam_k(*hyper), contract=contract)
+        res = _adam_ratios(got, kb.ref_adam(p, g, m, v, lr, (b1, b2), eps, wd, step))
+        assert all(bad == 0 for bad, _ in res), (n, res)
+        worst = [max(w, r) for w, (_, r) in zip(worst, res)]
+        # the planted elements: |g| = 1e-25 squares to zero in fp32 and the 2^-100 floor covers the reference's 1e-53
+        tiny = g.abs() == 1e-25
+        if bool(tiny.any()) and step == 1 and wd == 0.0:
+            assert bool((got[2][tiny] == 0).all())
+            rv, bv = kb.ref_adam(p, g, m, v, lr, (b1, b2), eps, wd, step)[2]
+            assert bool((rv[tiny] > 0).all()) and bool((rv[tiny] < kb.TINY).all()) and bool((bv[tiny] >= kb.TINY).all())
+        still = (g == 0) & (m == 0) & (v == 0)
+        if wd == 0.0 and bool(still.any()):
+            assert torch.equal(got[0][still], p[still]) and not bool(got[1][still].any() or got[2][still].any())
+    print(f"[emul] adam p / m / v worst ratios {worst[0]:.3f} / {worst[1]:.3f} / {worst[2]:.3f}")
+    assert max(worst) < 0.5
+
+
+def test_adam_clip_emulation_is_within_the_bound():
+    """the clip launch's arithmetic: c = max_norm / (total + 1e-6f) in fp32, g' = fl(c g) written back (K = 3), then
+    ``adam_one`` on g' against ``ref_adam(coef=...)``"""
+    hyper = ADAM_HYPER[2]
+    lr, b1, b2, eps, wd, step = hyper
+    p, g, m, v = kb.adam_case(1027, step, 5, plant=False)
+    total = g.double().pow(2).sum().sqrt().float()
+    for factor in (1 - 2.0 ** -10, 0.25):
+        mx = _f(float(total) * factor)
+        c32 = mx / (total + _f(1e-6))
+        c64 = kb.clip_coef(total, float(mx))
+        assert c64 < 1.0
+        g1 = g * c32
+        ref = c64 * g.double()
+        assert kb.check_within(g1, ref, kb.bound(ref, ref.abs(), kb.K_CLIP_G, 0.0))[0] == 0
+        res = _adam_ratios(_emul_adam(p, g1, m, v, _adam_k(*hyper)),
+                           kb.ref_adam(p, g, m, v, lr, (b1, b2), eps, wd, step, coef=c64))
+        print(f"[emul] adam behind a clip of {factor:.4f}: p / m / v ratios " + " / ".join(f"{r:.3f}" for _, r in res))
+        assert all(bad == 0 and r < 0.5 for bad, r in res), res
+
+
+ADAM_MUTANTS = {  # name -> (emulation switches, constant switches, hyper rows it can show in, outputs it must leave)
+    "bias_corrections_at_step_minus_1": (dict(), dict(step_off=1), (1, 2), "p"),
+    "eps_inside_the_square_root": (dict(eps_inside=True), dict(), (0, 1, 2, 3), "p"),
+    "weight_decay_dropped": (dict(no_wd=True), dict(), (1, 2), "pmv"),
+    "decoupled_weight_decay": (dict(decoupled=True), dict(), (1, 2), "pmv"),
+    "one_minus_beta2_in_fp32": (dict(), dict(omb2_f32=True), (0, 1, 2), "v"),
+    "tail_left_as_it_was": (dict(tail=True), dict(), (0, 1, 2, 3), "pmv"),
+}
+
+
+@pytest.mark.parametrize("name", list(ADAM_MUTANTS))
+def test_adam_mutant_is_rejected(name):
+    """each mutant of ``adam_one`` leaves the bound of the outputs named for it, in every hyper-parameter row where it
+    differs from the kernel at all.  Measured at n = 1027 without planted elements (elements outside the bound, worst
+    |err| / bound):
+
+    * bias corrections at step - 1 (rows with 1 < step <= 1000; at step 100 000 both corrections are 1 either way): p',
+      821 of 1027 by up to 9000 at step 2, 717 by up to 38 at step 1000;
+    * eps inside the root: p', every element with v' = 0 - a fifth of the tensor, set up here with g = 0, m = 0.25 - by
+      1e5 (sqrt(eps) = 1e-4 in place of eps = 1e-8), and a few more where sqrt(v') is near sqrt(eps);
+    * weight decay dropped: m' on 1026-1027 elements by 4e4-2e5, v' on 940-950 by 2e4-1e5, p' on 14 (lr = 8e-5, ratio
+      20) to 1025 (lr = 1e-2, ratio 3e4); decoupled (AdamW) weight decay: the same m' and v', p' on 12 and 1004;
+    * 1 - beta2 in fp32: v' on all 1027 elements at step 1 and on the 80-90 where the new term dominates later, by 5.5
+      (the constant is out by 1.3e-5 relative) - THE FORM OF ``adam_kernel`` (elementwise.hip :597), the single-tensor
+      entry ``wsr_adam_step``: rejected against torch's double hyper-parameters, accepted against the fp32 ones that
+      entry receives, which is how test_optimizer_matrix.py references it.  The table kernels (``adam_k`` :608) take the
+      constant in double and round once;
+    * the n & 3 tail elements left as they were: m' and v' on all 3 by 3e3-5e5, p' on 1 to 3 of them by 9 (lr = 8e-5,
+      |p| large beside the update) to 5e4."""
+    emu, con, rows, outs = ADAM_MUTANTS[name]
+    n = 1027
+    for hi in rows:
+        hyper = ADAM_HYPER[hi]
+        lr, b1, b2, eps, wd, step = hyper
+        p, g, m, v = kb.adam_case(n, step, 17 + hi, plant=False)
+        if name == "eps_inside_the_square_root":
+            v[::5] = 0.0  # (with g = 0 the denominator is eps alone: sqrt(eps) instead is out by 1e4)
+            g[::5] = 0.0
+            m[::5] = 0.25
+        ref = kb.ref_adam(p, g, m, v, lr, (b1, b2), eps, wd, step)
+        good = _adam_ratios(_emul_adam(p, g, m, v, _adam_k(*hyper)), ref)
+        assert all(bad == 0 for bad, _ in good), (name, hi, good)
+        kw = dict(emu)
+        if kw.pop("tail", False):
+            kw["tail_of"] = n
+        res = _adam_ratios(_emul_adam(p, g, m, v, _adam_k(*hyper, **con), lr=lr, **kw), ref)
+        print(f"[mutant] {name} hyper {hi}: p {res[0]}, m {res[1]}, v {res[2]}")
+        for o in outs:
+            bad, worst = res["pmv".index(o)]
+            assert bad >= 1 and worst > 2.0, (name, hi, o, res)
+        if name == "tail_left_as_it_was":
+            assert res[1][0] >= (n & 3) - (1 if step == 1 else 0)
+        if name == "one_minus_beta2_in_fp32":  # accepted where the entry point is referenced from what it receives
+            ref32 = kb.ref_adam(p, g, m, v, lr, (b1, b2), eps, wd, step, f32_hyper=True)
+            k32 = _adam_k(*hyper, f32_hyper=True)
+            assert float(k32[3]) == float(_f(1.0) - _f(b2))  # 1 - float(beta2) is exact
+            assert all(bad == 0 for bad, _ in _adam_ratios(_emul_adam(p, g, m, v, k32), ref32))
+
+
+def _butterfly64(s):
+    """``wg256_sum`` (elementwise.hip :659): xor butterfly over each wave of 64, then (sh0 + sh1) + (sh2 + sh3)"""
+    s = s.view(4, 64)
+    idx = torch.arange(64)
+    for o in (32, 16, 8, 4, 2, 1):
+        s = s + s[:, idx ^ o]
+    return (s[0, 0] + s[1, 0]) + (s[2, 0] + s[3, 0])
+
+
+def _emul_grad_sqnorm(g, vec=True, skip_tail=False):
+    """``grad_sqnorm_multi_kernel`` (:668) in fp32: four accumulators per thread over its float4s (stride 256), the tail
+    into a0, (a0 + a1) + (a2 + a3), the butterfly and the four wave sums"""
+    n = g.numel()
+    acc = torch.zeros(256, 4)
+    done = 0
+    if vec:
+        n4 = n >> 2
+        trips = -(-n4 // 256)
+        pad = torch.zeros(trips * 256 * 4)
+        pad[:4 * n4] = g[:4 * n4]
+        for t in pad.view(trips, 256, 4):
+            acc = acc + t * t
+        done = 4 * n4
+    if not skip_tail:
+        rest = g[done:]
+        trips = -(-rest.numel() // 256)
+        pad = torch.zeros(trips * 256)
+        pad[:rest.numel()] = rest
+        for t in pad.view(trips, 256):
+            acc[:, 0] = acc[:, 0] + t * t
+    return _butterfly64((acc[:, 0] + acc[:, 1]) + (acc[:, 2] + acc[:, 3]))
+
+
+@pytest.mark.parametrize("vec", [True, False], ids=["float4", "scalar"])
+def test_grad_sqnorm_emulation_is_within_the_bound_and_the_spike_shows_a_dropped_element(vec):
+    """K = n + 10 holds for the kernel's order at every size; one ordinary element of 32 768 is below it (3e-5 of the
+    sum against a bound of 1.7e-4), so a spike of 1024 stands at each designed index: left out of the tail it moves the
+    partial by 6e3 (n = 32 767) to 3e5 (n = 5) bounds"""
+    for n in ADAM_SIZES:
+        if n > kb.ADAM_CHUNK:
+            continue
+        g = kb.adam_case(n, 2, n, plant=False)[1]
+        ref, bnd = kb.ref_grad_sqnorm(g)
+        assert kb.check_within(_emul_grad_sqnorm(g, vec), ref, bnd)[0] == 0, n
+        if n >= 32767:
+            assert float((g[5] ** 2).double() / bnd) < 1.0  # an ordinary element cannot be seen
+        for i in sorted({0, 4 * (n >> 2), n - 1, min(n - 1, 4 * 256 + 2)} & set(range(n))):
+            s = g.clone()
+            s[i] = 1024.0
+            ref, bnd = kb.ref_grad_sqnorm(s)
+            assert kb.check_within(_emul_grad_sqnorm(s, vec), ref, bnd)[0] == 0, (n, i)
+            if vec and n & 3 and i >= 4 * (n >> 2):
+                bad, worst, _, _ = kb.check_within(_emul_grad_sqnorm(s, vec, skip_tail=True), ref, bnd)
+                assert bad == 1 and worst > 1e3, (n, i, worst)
+
+
+def _emul_clip_total(partials, drop=None):
+    """the head of ``adam_multi_clip_kernel`` (:699-701): thread t adds partials[t], [t + 256], ... in double, the
+    butterfly in double, one square root, one rounding to fp32"""
+    n = partials.numel()
+    trips = -(-n // 256)
+    pad = torch.zeros(trips * 256, dtype=torch.float64)
+    pad[:n] = partials.double()
+    if drop is not None:
+        pad[drop] = 0.0
+    s = torch.zeros(256, dtype=torch.float64)
+    for t in pad.view(trips, 256):
+        s = s + t
+    return _butterfly64(s).sqrt().float()
+
+
+@pytest.mark.parametrize("n_jobs", [1, 2, 255, 256, 257, 512, 513, 600])
+def test_clip_total_emulation_is_within_the_bound_and_a_dropped_partial_is_rejected(n_jobs):
+    """K = n_jobs + 2.  With one partial dominating, dropping it (index 256: the second trip of thread 0) leaves the
+    bound by 4e4 (600 jobs) to 6e5 (one job); an ordinary partial at index 256 is rejected too, by 84 among 257 and 40
+    among 600 (the double sum is exact to 1e-16, the bound a few 1e-5 of the total)."""
+    gen = torch.Generator().manual_seed(n_jobs)
+    for big in sorted({0, 255, 256, 511, 512, n_jobs - 1} & set(range(n_jobs))):
+        part = torch.rand(n_jobs, generator=gen) + 0.5
+        part[big] = 1024.0 ** 2
+        ref, bnd = kb.ref_clip_total(part)
+        assert kb.check_within(_emul_clip_total(part), ref, bnd)[0] == 0
+        bad, worst, _, _ = kb.check_within(_emul_clip_total(part, drop=big), ref, bnd)
+        assert bad == 1 and worst > 1e4, (n_jobs, big, worst)
+    if n_jobs > 256:
+        part = torch.rand(n_jobs, generator=gen) + 0.5
+        ref, bnd = kb.ref_clip_total(part)
+        bad, worst, _, _ = kb.check_within(_emul_clip_total(part, drop=256), ref, bnd)
+        print(f"[mutant] partial 256 of {n_jobs} dropped: ratio {worst:.3g}")
+        assert bad == 1 and worst > 10.0
+
+
+def test_clip_coefficient_mutants_are_rejected():
+    """the coefficient left unclamped above 1 (max_norm = total (1 + 2^-10): every one of the 1027 g' out by
+    2^-10 / 1.65e-6 = 590 bounds instead of bit-identical) and ``total + 1e-6`` omitted at a norm of 1e-7 (coef 0.5 instead of 0.045: every g' out
+    by 6e6 bounds)"""
+    g = kb.adam_case(1027, 2, 9, plant=False)[1]
+    total = g.double().pow(2).sum().sqrt().float()
+    mx = _f(float(total) * (1 + 2.0 ** -10))
+    c64 = kb.clip_coef(total, float(mx))
+    assert c64 == 1.0
+    ref = c64 * g.double()
+    bnd = kb.bound(ref, ref.abs(), kb.K_CLIP_G, 0.0)
+    unclamped = g * (mx / (total + _f(1e-6)))
+    bad, worst, _, _ = kb.check_within(unclamped, ref, bnd)
+    assert bad >= 1000 and worst > 100, (bad, worst)
+    tiny = g * _f(1e-7 / float(total))
+    t = tiny.double().pow(2).sum().sqrt().float()
+    mx = _f(0.5e-7)
+    c64 = kb.clip_coef(t, float(mx))
+    assert 0.04 < c64 < 0.05
+    ref = c64 * tiny.double()
+    bnd = kb.bound(ref, ref.abs(), kb.K_CLIP_G, 0.0)
+    assert kb.check_within(tiny * (mx / (t + _f(1e-6))), ref, bnd)[0] == 0
+    bad, worst, _, _ = kb.check_within(tiny * (mx / t), ref, bnd)
+    assert bad >= 1000 and worst > 1e5, (bad, worst)
+    # non-finite totals: inf gives a zero coefficient, NaN stays NaN
+    assert kb.clip_coef(float("inf"), 1.0) == 0.0 and math.isnan(kb.clip_coef(float("nan"), 1.0))
+    assert kb.clip_coef(3.0, float("inf")) == 1.0
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the glue kernels: lrelu_bwd, chan_axpby, upsample2_bwd, chan_sum
+# ---------------------------------------------------------------------------------------------------------------------
+
+GLUE_SPECIALS = {torch.bfloat16: (0x0000, -0x8000, 0x0001, -0x7FFF), torch.float32: (0, -0x80000000, 1, -0x7FFFFFFF)}
+GLUE_INT = {torch.float32: torch.int32, torch.bfloat16: torch.int16}
+
+
+def _glue_case(nvox, C, B, dt, seed):
+    """(g, y, chan_scale): g bf16-exact, y with +0.0, -0.0 and both subnormals planted, keep factors {0, 1, 1.25}"""
+    gen = torch.Generator().manual_seed(seed)
+    g = torch.randn(nvox, C, generator=gen).to(dt)
+    y = torch.randn(nvox, C, generator=gen).to(dt)
+    vv = torch.arange(nvox)
+    yb = y.view(GLUE_INT[dt])
+    yb[vv, (vv * 5) % C] = torch.tensor(GLUE_SPECIALS[dt], dtype=GLUE_INT[dt])[vv % 4]
+    cs = torch.tensor([1.25, 1.0, 0.0, 1.25])[torch.randint(0, 4, (B, C), generator=gen)]
+    return g, y, cs
+
+
+def _emul_lrelu_bwd(g, y, slope, cs, vpb, dt, *, sample0=False, flip=None):
+    """``lrelu_bwd_kernel`` (:191) in fp32: m = (y > 0 ? 1 : slope) [* scale], g * m, one store"""
+    pos = y.float() > 0
+    if flip is not None:
+        pos = pos ^ flip
+    mm = torch.where(pos, torch.ones(()), _f(slope))
+    if cs is not None:
+        b = torch.arange(g.shape[0]) // vpb
+        mm = mm * cs[torch.zeros_like(b) if sample0 else b]
+    return (g.float() * mm).to(dt)
+
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float32], ids=["bf16", "fp32"])
+def test_lrelu_bwd_emulation_and_mutants(dt):
+    """inside K = 2 (worst ratio 0.97 bf16, 0.044 fp32).  ``chan_scale`` of sample 0 used for every sample: rejected on
+    6615 of the second sample's 10 080 elements - wherever the two samples' keep factors differ - by 50 and more, and by
+    1e30 where the right factor is 0 and the bound is the 2^-100 floor; no element of sample 0 moves.  -0.0 taken as
+    positive: all 118 planted elements on kept channels, by 1e3 (bf16) / 3e6 (fp32); a positive subnormal taken as not
+    positive: all 98, by 200 / 6e5 (0.8 |g| against rho |ref| or 23 u |ref|)."""
+    nvox, C, B = 630, 32, 2
+    g, y, cs = _glue_case(nvox, C, B, dt, 4)
+    ref, a, f = kb.ref_lrelu_bwd(g, y, 0.2, cs, nvox // B)
+    bnd = kb.bound(ref, a, 2, kb.rho_for(dt))
+    got = _emul_lrelu_bwd(g, y, 0.2, cs, nvox // B, dt)
+    assert kb.check_within(got, ref, bnd)[0] == 0
+    same = f == 1.0
+    assert bool(same.any()) and torch.equal(got.view(GLUE_INT[dt])[same], g.view(GLUE_INT[dt])[same])
+    bad, worst, _, ratio = kb.check_within(_emul_lrelu_bwd(g, y, 0.2, cs, nvox // B, dt, sample0=True), ref, bnd)
+    assert bad >= 100 and worst > 50 and not bool((ratio[:nvox // B] > 1).any()), (bad, worst)
+    bits = y.view(GLUE_INT[dt])
+    sp = GLUE_SPECIALS[dt]
+    kept = cs[torch.arange(nvox) // (nvox // B)] != 0
+    for pat in (sp[1], sp[2]):
+        flip = (bits == pat)
+        assert int(flip.sum()) >= nvox // 4 - 1
+        bad, worst, _, ratio = kb.check_within(_emul_lrelu_bwd(g, y, 0.2, cs, nvox // B, dt, flip=flip), ref, bnd)
+        hit = flip & kept & (g.float() != 0)
+        assert bool((ratio[hit] > 1).all()) and bad == int(hit.sum()) and worst > 50, (pat, bad, worst)
+
+
+def test_chan_axpby_reading_dst_at_beta_zero_is_rejected():
+    """beta * dst taken at beta == 0: 0 * NaN poisons every element (a non-finite result is an infinite ratio)"""
+    gen = torch.Generator().manual_seed(1)
+    s = torch.randn(77, 16, generator=gen).bfloat16()
+    d = torch.full((77, 16), float("nan"))
+    for al, be in ((1.0, 0.0), (0.2, 0.0), (1.0, 1.0), (1.0, 0.2), (-0.5, 2.0)):
+        d0 = d if be == 0.0 else torch.randn(77, 16, generator=gen).bfloat16().float()
+        ref, a = kb.ref_chan_axpby(s, d0, al, be)
+        for dt in (torch.bfloat16, torch.float32):
+            bnd = kb.bound(ref, a, 3, kb.rho_for(dt))
+            o = _f(al) * s.float()
+            got = o if be == 0.0 else o + _f(be) * d0
+            assert kb.check_within(got.to(dt), ref, bnd)[0] == 0, (al, be)
+            if be == 0.0:
+                assert kb.check_within((o + _f(be) * d0).to(dt), ref, bnd)[0] == ref.numel()
+
+
+def test_upsample2_bwd_reference_and_a_missing_fine_voxel():
+    """the reference is the adjoint of nearest up-sampling (float64 autograd); the kernel's order of the three additions
+    is inside K = 3; one of the four fine voxels left out is rejected on 477-480 of 480 elements, by 5e4 and more in
+    bf16 and 5e5 in fp32"""
+    gen = torch.Generator().manual_seed(2)
+    dy = torch.randn(2, 6, 4, 5, 8, generator=gen).bfloat16()
+    ref, a = kb.ref_upsample2_bwd(dy)
+    x = torch.zeros(2, 3, 2, 5, 8, dtype=torch.float64, requires_grad=True)
+    up = x.repeat_interleave(2, dim=1).repeat_interleave(2, dim=2)
+    (gx,) = torch.autograd.grad(up, x, dy.double())
+    assert torch.equal(gx, ref)
+    f = dy.float()
+    parts = [f[:, i::2, j::2] for i in (0, 1) for j in (0, 1)]
+    for dt in (torch.bfloat16, torch.float32):
+        bnd = kb.bound(ref, a, 3, kb.rho_for(dt))
+        assert kb.check_within((((parts[0] + parts[1]) + parts[2]) + parts[3]).to(dt), ref, bnd)[0] == 0
+        for k in range(4):
+            got = sum(q for i, q in enumerate(parts) if i != k)
+            bad, worst, _, _ = kb.check_within(got.to(dt), ref, bnd)
+            assert bad >= int((parts[k] != 0).sum()) * 0.9 and worst > 30, (k, bad, worst)
+
+
+def _emul_chan_sum(x, scale=1.0, *, drop_last_lane_of=None, twice_in_tail=False, group_shift=False):
+    """``chan_sum_kernel`` (:875) + ``chan_sum_final_kernel`` (:909) in fp32 on window rows (nvox, C): thread =
+    (voxel lane, 4-channel group) walks v = row lanes + lane + k step, eight voxels per trip of the unrolled loop -
+    added in index order, so the order is the plain one - then the tail loop; lane 0 adds the lanes in order; the final
+    kernel adds the rows.  Returns (out, partial table)."""
+    nvox, C = x.shape
+    _, lanes, rows = kb.chan_sum_geometry(C, nvox)
+    step = rows * lanes
+    if group_shift:
+        x = x.roll(-4, dims=1)
+    trips = -(-nvox // step)
+    pad = torch.zeros(trips * step, C)
+    pad[:nvox] = x
+    pad = pad.view(trips, rows, lanes, C)
+    acc = torch.zeros(rows, lanes, C)
+    for k in range(trips):
+        acc = acc + pad[k]
+    if twice_in_tail:  # thread (row 0, lane 0): its first voxel after the unrolled trips, once more
+        n0 = -(-nvox // step)  # voxels of that thread
+        k = 8 * (n0 // 8) if n0 % 8 else n0 - 1
+        acc[0, 0] = acc[0, 0] + pad[k, 0, 0]
+    if drop_last_lane_of is not None:
+        acc[drop_last_lane_of, lanes - 1] = 0.0
+    part = acc[:, 0]
+    for l in range(1, lanes):
+        part = part + acc[:, l]
+    return _f(scale) * _emul_rows_sum(part), part
+
+
+CHAN_SUM_ROWS = [(4, 1), (4, 4097), (12, 1361), (48, 1000), (128, 8 * 16 + 1), (144, 3000), (1020, 300), (1024, 8197),
+                 (128, 65541)]
+
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float32], ids=["bf16", "fp32"])
+@pytest.mark.parametrize("C,nvox", CHAN_SUM_ROWS)
+def test_chan_sum_emulation_is_within_the_bound(dt, C, nvox):
+    gen = torch.Generator().manual_seed(C + nvox)
+    x = (0.2 + torch.randn(nvox, C, generator=gen)).to(dt).float()
+    _, lanes, rows = kb.chan_sum_geometry(C, nvox)
+    for scale in (1.0, 0.2):
+        out, part = _emul_chan_sum(x, scale)
+        ref, a = kb.ref_chan_sum(x, scale)
+        r = kb.check_within(out, ref, kb.bound(ref, a, nvox + rows, 0.0))
+        print(f"[emul] chan_sum ({C}, {nvox}) scale {scale}: ratio {r[1]:.4f}")
+        assert r[0] == 0 and r[1] < 0.5, r[:2]
+    pref, pa = kb.ref_chan_sum_partials(x, C, nvox)
+    assert kb.check_within(part, pref, kb.bound(pref, pa, -(-nvox // rows) + lanes, 0.0))[0] == 0
+    assert torch.equal(pref.sum(0), kb.ref_chan_sum(x)[0]) or float((pref.sum(0) - x.double().sum(0)).abs().max()) < 1e-9
+
+
+CHAN_SUM_MUTANTS = {  # name -> ((C, nvox), emulation switch, spike voxel or None)
+    "last_lane_of_a_workgroup_dropped": ((12, 1361), dict(drop_last_lane_of=1), None),
+    "last_lane_of_a_capped_grid_dropped": ((128, 65541), dict(drop_last_lane_of=511), "last_lane"),
+    "tail_voxel_taken_twice": ((128, 65541), dict(twice_in_tail=True), "tail"),
+    "tail_voxel_taken_twice_one_lane": ((1024, 8197), dict(twice_in_tail=True), "tail"),
+    "channel_group_g_read_at_g_plus_1": ((48, 1000), dict(group_shift=True), None),
+}
+
+
+@pytest.mark.parametrize("name", list(CHAN_SUM_MUTANTS))
+def test_chan_sum_mutant_is_rejected(name):
+    """measured (channels outside the bound, worst |err| / bound): the last lane's voxels of workgroup 1 dropped at
+    (12, 1361): 12 of 12, 190; on the capped rows one voxel in 65 541 is below the bound, which is why those rows carry
+    a spike of 1024: the last lane of workgroup 511 dropped at (128, 65 541): 128 of 128, 79; the tail voxel of thread 0
+    taken twice: 128 of 128, 79, and at (1024, 8197) 1024 of 1024, 1600; the channel group of thread g read at
+    4 (g + 1) at (48, 1000): 48 of 48, 8e4 (the channels' means differ by 0.5)"""
+    (C, nvox), kw, spike = CHAN_SUM_MUTANTS[name]
+    gen = torch.Generator().manual_seed(7)
+    x = (torch.randn(nvox, C, generator=gen) + torch.arange(C) % 7 * 0.5).bfloat16().float()
+    _, lanes, rows = kb.chan_sum_geometry(C, nvox)
+    step = rows * lanes
+    if spike == "tail":
+        n0 = -(-nvox // step)
+        assert n0 % 8 == 1 and n0 > 8  # unrolled trips, then one tail voxel
+        x[8 * (n0 // 8) * step] = 1024.0
+    elif spike == "last_lane":
+        x[511 * lanes + lanes - 1] = 1024.0
+    ref, a = kb.ref_chan_sum(x)
+    bnd = kb.bound(ref, a, nvox + rows, 0.0)
+    assert kb.check_within(_emul_chan_sum(x)[0], ref, bnd)[0] == 0
+    bad, worst, _, _ = kb.check_within(_emul_chan_sum(x, **kw)[0], ref, bnd)
+    print(f"[mutant] chan_sum {name}: {bad} of {C} channels outside, worst ratio {worst:.3g}")
+    assert bad >= C // 2 and worst > 10.0, (name, bad, worst)
