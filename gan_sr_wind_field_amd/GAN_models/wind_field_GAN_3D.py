@@ -849,6 +849,19 @@ class wind_field_GAN_3D(BaseGAN):
         return _level_sums("hub_height", hub_height_reference, self.cfg.scale, HR, SR, LR,
                            (Z, terrain.to(HR.device)), (tables, hc.interp, with_columns))
 
+    # ------------------------------------------------------------------ structure functions ([INCREMENTS])
+    def level_increments(self, HR, SR, LR):
+        """The sums of ``increments.py`` per sample, z level, source, separation, direction, kind and order of a batch ->
+        float64 (B, NZ, 3, R, 2, 3, 3) on the tensors' device, with the separations of ``[INCREMENTS]`` (without the
+        section: 1, 2, 4, 8, 16): the trilinear baseline of ``LR`` is built here (``wsr_trilinear_xy`` on a GPU,
+        ``F.interpolate`` on a CPU), the sums come from ``hip_ops.level_increments`` on a GPU and from
+        ``increments.level_increments_reference`` on a CPU.  Reads no weights: the same inside ``ema_scope()``."""
+        from ..increments import DEFAULT_SEPARATIONS, level_increments_reference
+
+        ic = getattr(self.cfg, "increments", None)
+        sp = ic.separations if ic is not None and ic.separations is not None else DEFAULT_SEPARATIONS
+        return _level_sums("level_increments", level_increments_reference, self.cfg.scale, HR, SR, LR, (), (tuple(sp),))
+
     def make_new_labels(self, it):
         """Real / fake label vectors of this iteration (reference :627-678)."""
         t = self.cfg.training

@@ -36,6 +36,7 @@ EXPORTS = [
     "wsr_ssim_pair_sums_workspace_floats", "wsr_ssim_pair_sums", "wsr_ssim_pair_sums_bwd", "wsr_ssim_pair_sums_bwd_tile",
     "wsr_level_fss_workspace_floats", "wsr_level_fss",
     "wsr_hub_height_workspace_floats", "wsr_hub_height",
+    "wsr_level_increments_workspace_floats", "wsr_level_increments",
     "wsr_speed_soft_counts_workspace_floats", "wsr_speed_soft_counts", "wsr_speed_soft_counts_bwd",
     "wsr_speed_soft_counts_geometry",
     "wsr_last_tile_plan", "wsr_last_tile_instantiation",
@@ -191,6 +192,8 @@ def lib() -> C.CDLL:
                           vp],   # additive export
         "wsr_hub_height": [vp, i32, vp, i32, vp, i32, vp, vp, C.POINTER(C.c_float), i32, C.POINTER(C.c_float),
                            C.POINTER(C.c_float), i32, i32, i32, i32, i32, i32, vp, vp, vp, vp],   # additive export
+        "wsr_level_increments": [vp, i32, vp, i32, vp, i32, C.POINTER(C.c_int32), i32, i32, i32, i32, i32, vp, vp,
+                                 vp],   # additive export
         "wsr_speed_soft_counts": [vp, i32, vp, i32, C.c_float, i32, i32, i32, i32, i32, vp, vp, vp],   # additive export
         "wsr_speed_soft_counts_bwd": [vp, i32, vp, C.c_float, i32, i32, i32, i32, i32, vp, vp],   # additive export
         "wsr_speed_soft_counts_geometry": [i32, i32, i32, i32, i32, C.POINTER(C.c_int32)],   # additive export
@@ -224,6 +227,8 @@ def lib() -> C.CDLL:
     L.wsr_level_fss_workspace_floats.restype = C.c_int64
     L.wsr_hub_height_workspace_floats.argtypes = [i32, i32, i32, i32, i32]
     L.wsr_hub_height_workspace_floats.restype = C.c_int64
+    L.wsr_level_increments_workspace_floats.argtypes = [i32, i32, i32, i32, C.POINTER(C.c_int32), i32]
+    L.wsr_level_increments_workspace_floats.restype = C.c_int64
     L.wsr_speed_soft_counts_workspace_floats.argtypes = [i32, i32, i32, i32, i32]
     L.wsr_speed_soft_counts_workspace_floats.restype = C.c_int64
     if L.wsr_abi_version() != 9:

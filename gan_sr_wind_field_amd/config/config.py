@@ -57,6 +57,10 @@ Extension (optional keys, defaults keep reference behaviour):
             --test also writes the wind speed, the wind power density and a turbine's capacity factor at fixed heights
             above ground for the truth, the network and the baseline
             (hub_height.py, csrc/hub_height.hip)
+  [INCREMENTS] separations / per_level
+            --test also writes the structure functions of truth, network and baseline: second-order structure function
+            (twice the semivariogram), skewness and flatness of the velocity increments per separation
+            (increments.py, csrc/increments.hip)
   [DISTRIBUTION_LOSS] weight / bin_width / speed_bins / pool
             absent = off; present, the generator loss carries weight * the 1-D Wasserstein distance (m/s) between the
             soft horizontal-speed histograms of SR and HR (distribution_loss.py, csrc/distribution_loss.hip), logged as
@@ -828,6 +832,34 @@ class HubHeightConfig(OptionalSection):
         return bool(self.present)
 
 
+class IncrementsConfig(OptionalSection):
+    """[INCREMENTS] (extension): the structure functions of HR, SR and the trilinear baseline in ``run.py --test``
+    (increments.py, csrc/increments.hip); absent section = off, and never printed by ``asINI``.  ``separations``: 1 .. 8
+    integers in HR grid cells, strictly ascending, each 1 .. 32, required; ``per_level``: ``--test`` also writes
+    ``<name>____structure_functions_levels.csv``."""
+
+    separations: Optional[list] = None
+    per_level: bool = False
+    _section, _printed = "INCREMENTS", False
+    _schema = (("separations", _L), ("per_level", _B))
+
+    setIncrementsConfig = OptionalSection.load
+
+    def validate(self) -> None:
+        if not self.present:
+            return
+        from ..increments import check_separations
+        if self.separations is None:
+            raise ValueError("[INCREMENTS] separations must be given (a list of integers in HR grid cells): it has no "
+                             "default")
+        self.separations = check_separations(self.separations, "[INCREMENTS]")
+
+    @property
+    def on(self) -> bool:
+        """``--test`` takes the increment sums and writes the structure-function files"""
+        return bool(self.present)
+
+
 class DistributionLossConfig(OptionalSection):
     """[DISTRIBUTION_LOSS] (extension): a wind-speed distribution term of the generator loss (distribution_loss.py,
     csrc/distribution_loss.hip); absent section = off, and not printed by ``asINI``.  ``weight`` (required, > 0: there is
@@ -906,6 +938,7 @@ class Config(IniConfig):
     distribution: DistributionConfig = DistributionConfig()
     fss: FssConfig = FssConfig()
     hub_height: HubHeightConfig = HubHeightConfig()
+    increments: IncrementsConfig = IncrementsConfig()
     ssim_loss: SsimLossConfig = SsimLossConfig()
     distribution_loss: DistributionLossConfig = DistributionLossConfig()
     compute_dtype: str = "fp32"
@@ -923,7 +956,7 @@ class Config(IniConfig):
                  ("degradation", lambda c: c.scale), ("ssim", None))
     # (the sections above are a pinned list; later extensions load and print behind them, by the same rules)
     _optional_later = (("distribution", None), ("ssim_loss", None), ("fss", None), ("hub_height", None),
-                       ("distribution_loss", None))
+                       ("increments", None), ("distribution_loss", None))
 
     def __init__(self, ini_path):
         parser = ConfigParser(allow_no_value=True)

@@ -1877,3 +1877,43 @@ def hub_height(HR: Tensor, SR: Tensor, TL: Optional[Tensor], Z: Tensor, terrain:
                            _p(terrain), heights, nh, curve_v, curve_p, nk, int(interp == "log"), B, X, Y, NZ, _p(ws),
                            _p(out), _p(cols), _stream()), "hub_height")
     return (out, cols) if with_columns else out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# structure functions ([INCREMENTS]; csrc/increments.hip)
+# ---------------------------------------------------------------------------------------------------------------------
+INCREMENTS_TILE = 32  # INC_TILE of csrc/increments_kernels.h: the positions of a workgroup are INCREMENTS_TILE squared
+
+
+def increments_level_chunk(NZ: int, separations) -> int:
+    """The consecutive levels one workgroup of ``wsr_level_increments`` stages (``inc_geom`` of
+    csrc/increments_kernels.h)"""
+    S = INCREMENTS_TILE + int(separations[-1])
+    zc = min(12288 // (S * S), 16, int(NZ))
+    return -(-int(NZ) // -(-int(NZ) // zc))
+
+
+def level_increments(HR: Tensor, SR: Tensor, TL: Optional[Tensor], separations=(1, 2, 4, 8, 16),
+                     out: Optional[Tensor] = None) -> Tensor:
+    """The sums of ``increments.py`` per sample, z level, source, separation, direction, kind and order -> float64
+    (B, NZ, 3, R, 2, 3, 3): over every horizontal plane of ``HR``, ``SR`` and the baseline ``TL`` (B, C >= 3, X, Y, NZ;
+    channels 0, 1 and 2 are read) the sums of the second, third and fourth powers of the increments of u, v and w over
+    ``separations`` grid cells along x and along y.  ``TL`` None: zeros in its slices.  One pass, fp32 partial sums in a
+    fixed order added in double, no atomics: the same bits on every call.  ``out``: a float64 (B, NZ, 3, R, 2, 3, 3)
+    slice to write into (``wsr_level_increments``)."""
+    from . import increments
+
+    _need_cuda(HR, SR, TL, out)
+    B, X, Y, NZ = _same_grid("level_increments", HR, SR=SR, **({} if TL is None else {"TL": TL}))
+    sp = increments.check_separations(separations, "level_increments")
+    nr = len(sp)
+    if B > 65535 or X * Y >= 2 ** 31 or X * Y * NZ >= 2 ** 31:
+        raise ValueError(f"level_increments: at most 65535 samples, 2^31 - 1 columns and 2^31 - 1 voxels per sample, not "
+                         f"B = {B}, X = {X}, Y = {Y}, NZ = {NZ}")
+    out = _sums_out("level_increments", out, (B, NZ, 3, nr, 2, 3, 3), HR.device)
+    L = _lib.lib()
+    arr = (C.c_int32 * nr)(*sp)
+    ws = _workspace(L.wsr_level_increments_workspace_floats(B, X, Y, NZ, arr, nr), HR.device)
+    check(L.wsr_level_increments(_p(HR), HR.shape[1], _p(SR), SR.shape[1], _p(TL), 0 if TL is None else TL.shape[1], arr,
+                                 nr, B, X, Y, NZ, _p(ws), _p(out), _stream()), "level_increments")
+    return out

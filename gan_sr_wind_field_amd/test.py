@@ -110,6 +110,20 @@ write
     ./test_output/<cfg.name>____hub_height_reverse_interpolate.csv   (+ ``..._fields_reverse_interpolate.csv``,
         ``averages_hub_height_reverse_interpolate.csv``, ``..._maps_reverse_interpolate.npz``) with
         ``reverse_interpolate``: the same on the raw truth, the re-levelled SR and baseline and the raw altitudes
+
+With an ``[INCREMENTS]`` section both loops also add the sums of the powers of the increments per level, source,
+separation, direction, kind and order of every batch (``increments.py``) into one (NZ, 3, R, 2, 3, 3) table - the device
+loop with ONE ``hip_ops.level_increments`` launch per batch on the stored baseline, its table a device tensor read once
+after the last batch; the host loop with ``increments.level_increments_reference`` on the host tensors - and write
+    ./test_output/<cfg.name>____structure_functions.csv           one row of ``INCREMENT_COLUMNS`` per separation, pooled
+                                                                   over fields and levels
+    ./test_output/<cfg.name>____structure_functions_levels.csv    (``per_level``) one row ``level,`` + ``INCREMENT_COLUMNS``
+                                                                   per z level and separation
+    ./test_output/averages_structure_functions.csv                one appended row ``Name,`` + ``INCREMENT_COLUMNS`` per
+                                                                   separation
+    ./test_output/<cfg.name>____structure_functions_reverse_interpolate.csv   (+ ``..._levels_reverse_interpolate.csv``,
+        ``averages_structure_functions_reverse_interpolate.csv``) with ``reverse_interpolate``: the same on the raw truth
+        and the re-levelled SR and baseline
 """
 from __future__ import annotations
 
@@ -131,6 +145,7 @@ from .distribution import (ROSE_COLUMNS, SPEED_COLUMNS, SUMMARY_COLUMNS, distrib
 from .fss import EXCEEDANCE_COLUMNS, FSS_COLUMNS, fss_from_sums, fss_tables, level_fss_reference
 from .hub_height import COLUMNS as HUB_COLUMNS
 from .hub_height import hub_height_from_sums, hub_height_reference, hub_height_tables
+from .increments import INCREMENT_COLUMNS, increments_from_sums, level_increments_reference
 from .process_data import reverse_interpolate_z_axis
 from .ssim import SSIM_COLUMNS, columns_from_sums, level_ssim_reference, n_positions
 from .spectra import SPECTRUM_COLUMNS, grid_spacing, level_spectra_reference, mode_counts, spectrum_from_sums
@@ -522,6 +537,39 @@ class _HubHeight(_LevelSums):
                      capacity_factor=mean[:, 3:6].numpy())
 
 
+class _Increments(_LevelSums):
+    """[INCREMENTS]: sums (B, NZ, 3, R, 2, 3, 3); one row per separation for the test set, pooled over fields and levels,
+    the rows of ``averages_structure_functions<suffix>.csv`` and, with ``per_level``, the rows of every level.  No
+    per-field file.  ``d``: the mean grid spacing in metres."""
+
+    stem = "structure_functions"
+
+    def __init__(self, fn, separations, uvw, d, per_level, *where):
+        super().__init__(fn, *where)
+        self.separations, self.uvw, self.d, self.per_level = separations, uvw, d, per_level
+        self.averages_path = os.path.join(self.folder, f"averages_structure_functions{self.suffix}.csv")
+        _header(self.averages_path, "Name," + ",".join(INCREMENT_COLUMNS))
+
+    def rows(self, table, levels):
+        col = increments_from_sums(table, self.separations, self.nfields * levels, *self.shape, self.uvw, self.d)
+        return [",".join(str(col[c][k]) for c in INCREMENT_COLUMNS) for k in range(len(self.separations))]
+
+    def close(self):
+        super().close()
+        table = None if self.total is None else self.total.cpu()  # the ONE read
+        rows = [] if table is None else self.rows(table.sum(dim=0), table.shape[0])
+        with open(self.path(), "w") as f:
+            f.write(",".join(INCREMENT_COLUMNS) + "\n")
+            f.writelines(row + "\n" for row in rows)
+        with open(self.averages_path, "a") as f:
+            f.writelines(f"{self.name},{row}\n" for row in rows)
+        if self.per_level:
+            with open(self.path("_levels"), "w") as f:
+                f.write("level," + ",".join(INCREMENT_COLUMNS) + "\n")
+                for lvl in range(0 if table is None else table.shape[0]):
+                    f.writelines(f"{lvl},{row}\n" for row in self.rows(table[lvl], 1))
+
+
 def _outputs(cfg, gan, uvw, d, suffix, on_device, folder=OUT_DIR):
     """The extra outputs of one set of levels that ``cfg`` asks for, each yielded as soon as its files are open; the
     sums come from ``hip_ops`` with ``on_device`` (the device loop), else from the host references.  ``d``: the mean grid
@@ -561,6 +609,9 @@ def _outputs(cfg, gan, uvw, d, suffix, on_device, folder=OUT_DIR):
         tab = hub_height_tables(uvw, hc.heights, hc.curve_speeds, hc.curve_power)
         yield _HubHeight(lambda HR, SR, TL, Z: hub(HR, SR, TL, Z, terrain, tab, hc.interp, hc.write_maps), tab,
                          hc.air_density, hc.per_field, hc.write_maps, gan.xy, *where)
+    if cfg.increments.on:
+        inc, sp = hip_ops.level_increments if on_device else level_increments_reference, tuple(cfg.increments.separations)
+        yield _Increments(lambda HR, SR, TL, Z: inc(HR, SR, TL, sp), sp, uvw, d, cfg.increments.per_level, *where)
 
 
 class _LevelSet:
@@ -689,7 +740,7 @@ def test(cfg, dataset_test, reverse_interpolate: bool = False):
     if cfg.hub_height.on:  # (the ground altitude and the coordinates of the whole test domain; one upload)
         gan.terrain = torch.from_numpy(np.asarray(dataset_test.terrain)).float().contiguous().to(dev)
         gan.xy = (np.asarray(dataset_test.x), np.asarray(dataset_test.y))
-    d = grid_spacing(np.asarray(dataset_test.x), np.asarray(dataset_test.y)) if cfg.spectrum.on or cfg.fss.on else None
+    d = grid_spacing(np.asarray(dataset_test.x), np.asarray(dataset_test.y)) if cfg.spectrum.on or cfg.fss.on or cfg.increments.on else None
     on_device = cfg.eval.on and torch.device(dev).type == "cuda"
     with contextlib.ExitStack() as stack:  # (an exception in any batch closes every file)
         sets = []

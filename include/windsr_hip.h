@@ -919,6 +919,31 @@ int wsr_hub_height(const float* hr, int32_t hr_c, const float* sr, int32_t sr_c,
                    const float* curve_p, int32_t nk, int32_t log_mode, int32_t B, int32_t X, int32_t Y, int32_t NZ,
                    float* workspace, double* out, float* cols, void* stream);
 
+/* ---- structure functions ([INCREMENTS]; csrc/increments.hip) ---------------------------------------------------
+ * wsr_level_increments: out (B, NZ, 3, nr, 2, 3, 3) doubles, written completely: per sample, z level, source (0 hr,
+ * 1 sr, 2 tl), separation r = separations[k], direction a (0 x, 1 y), kind (0 L: the component along a - u for x, v for
+ * y; 1 T: the horizontal component across a; 2 W: w) and order (2, 3, 4) the sum over every pair (p, p + r e_a) with
+ * both ends inside the level's plane - no padding, max(X - r, 0) * Y pairs along x and X * max(Y - r, 0) along y - of
+ *    delta = f(p + r e_a) - f(p), ONE fp32 subtraction;   q = delta delta;   [0] q   [1] q delta   [2] q q
+ * every product rounded to fp32, nothing contracted.  Sources: fp32 planar (B, c, X, Y, NZ), channels 0 = u, 1 = v and
+ * 2 = w read.  z is never paired.  An entry without pairs is 0; a NaN or Inf operand makes exactly the entries whose
+ * pairs contain it non-finite.  tl may be NULL: its slices are written as zeros.  separations (nr int32): HOST, read
+ * during the call: 1 .. 8 entries, strictly ascending, each 1 .. 32.  A workgroup stages a 32 x 32 tile of one component
+ * with a forward halo of the largest separation in LDS, keeps fp32 partial sums in a fixed order (a chain of at most 96
+ * additions) and writes one partial row; the rows are added in a fixed order in double: no atomics, the same bits on
+ * every call, the three sources through the same code.
+ * workspace: wsr_level_increments_workspace_floats(B, X, Y, NZ, separations, nr) floats (0 for arguments the entry
+ * refuses).  A null pointer (but tl), a channel count < 3, a non-positive size, nr outside 1 .. 8, a separation outside
+ * 1 .. 32 or not ascending: WSR_EINVAL; B > 65535, X * Y >= 2^31 or X * Y * NZ >= 2^31: WSR_EUNSUPPORTED; nothing is
+ * written in either case. */
+#define WSR_INCREMENTS_MAX_SEPARATIONS 8
+#define WSR_INCREMENTS_MAX_SEPARATION 32
+int64_t wsr_level_increments_workspace_floats(int32_t B, int32_t X, int32_t Y, int32_t NZ, const int32_t* separations,
+                                              int32_t nr);
+int wsr_level_increments(const float* hr, int32_t hr_c, const float* sr, int32_t sr_c, const float* tl, int32_t tl_c,
+                         const int32_t* separations, int32_t nr, int32_t B, int32_t X, int32_t Y, int32_t NZ,
+                         float* workspace, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
