@@ -76,6 +76,9 @@ class wind_field_GAN_3D(BaseGAN):
         if self._distribution_loss_on():  # ([DISTRIBUTION_LOSS]: likewise, the last of the three)
             self.train_G_loss_dict["distribution"] = torch.zeros(1)
             self.validation_G_loss_dict["distribution"] = torch.zeros(1)
+        if self._consistency_loss_on():  # ([CONSISTENCY_LOSS]: likewise, behind ``distribution``)
+            self.train_G_loss_dict["consistency"] = torch.zeros(1)
+            self.validation_G_loss_dict["consistency"] = torch.zeros(1)
         self._wind_scale = None  # UVW_MAX of the training data (set_wind_scale): what [DISTRIBUTION_LOSS] needs
         self.D_loss_dict = _zeros_dict(("train_loss", "validation_loss"))
         self.hist_dict = {
@@ -347,6 +350,18 @@ class wind_field_GAN_3D(BaseGAN):
         """``[DISTRIBUTION_LOSS]`` is in the configuration: the generator loss carries the speed-distribution term"""
         return bool(getattr(getattr(self.cfg, "distribution_loss", None), "on", False))
 
+    def _consistency_loss_on(self) -> bool:
+        """``[CONSISTENCY_LOSS]`` is in the configuration: the generator loss carries the coarse-grained consistency term"""
+        return bool(getattr(getattr(self.cfg, "consistency_loss", None), "on", False))
+
+    def coarse_residual(self, HR, SR):
+        """``r = D(SR - HR)`` (consistency_loss.py) of a batch under the keys of ``[CONSISTENCY_LOSS]``: the coarse-grained
+        difference of the wind components, (B, 3, XL, YL, NZ)"""
+        if not self._consistency_loss_on():
+            raise ValueError("coarse_residual needs a [CONSISTENCY_LOSS] section in the configuration")
+        from ..consistency_loss import coarse_residual, section_tables
+        return coarse_residual(HR, SR, section_tables(HR, self.cfg.consistency_loss, self.cfg.scale))
+
     def set_wind_scale(self, UVW_MAX) -> None:
         """The scale of the normalised wind components in m/s (``dataset_train.UVW_MAX``): ``[DISTRIBUTION_LOSS]`` bins
         the speed in m/s.  Without the section the value is kept and never read."""
@@ -374,6 +389,8 @@ class wind_field_GAN_3D(BaseGAN):
             target["ssim"] = losses["ssim"]
         if "distribution" in losses:
             target["distribution"] = losses["distribution"]
+        if "consistency" in losses:
+            target["consistency"] = losses["consistency"]
         if not training_iteration:
             self.metrics_dict["pix_loss_unscaled"] = losses["pix"] / self.cfg.training.pixel_loss_weight
             self.hist_dict["SR_pix_distribution"] = fake_HR.detach().cpu().numpy()
@@ -433,6 +450,13 @@ class wind_field_GAN_3D(BaseGAN):
             from ..distribution_loss import distribution_loss
             dist_term = distribution_loss(HR, fake_HR, self.cfg.distribution_loss, self._distribution_tables())
             wkey = wkey + (self.cfg.distribution_loss.weight,)
+        # [CONSISTENCY_LOSS]: the coarse-grained consistency term (consistency_loss.py), by the same rules: the next entry
+        # of the core vector, after ``distribution``; a non-finite SR makes it non-finite and the Adam step is skipped
+        cons_term = None
+        if self._consistency_loss_on():
+            from ..consistency_loss import consistency_loss
+            cons_term = consistency_loss(HR, fake_HR, self.cfg.consistency_loss, self.cfg.scale)
+            wkey = wkey + (self.cfg.consistency_loss.weight,)
         if getattr(self, "_loss_w", (None,))[0] != wkey:
             self._loss_w = (wkey, torch.tensor([float(v) for v in wkey[1:]], dtype=torch.float32).to(self.device))
         L = {}
@@ -445,7 +469,8 @@ class wind_field_GAN_3D(BaseGAN):
             Lp = torch.stack([v.reshape(()) for v in unweighted[3:]]) * wv[3:7]
             L.update(zip(keys, Lc.unbind() + Lp.unbind()))
             at = 7
-            for name, extra in (("spectral", spec), ("ssim", ssim_term), ("distribution", dist_term)):
+            for name, extra in (("spectral", spec), ("ssim", ssim_term), ("distribution", dist_term),
+                                ("consistency", cons_term)):
                 if extra is not None:
                     Ls = extra.reshape(1) * wv[at:at + 1]
                     L[name] = Ls.reshape(())

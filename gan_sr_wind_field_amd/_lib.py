@@ -39,6 +39,7 @@ EXPORTS = [
     "wsr_level_increments_workspace_floats", "wsr_level_increments",
     "wsr_speed_soft_counts_workspace_floats", "wsr_speed_soft_counts", "wsr_speed_soft_counts_bwd",
     "wsr_speed_soft_counts_geometry",
+    "wsr_coarse_residual", "wsr_coarse_residual_bwd", "wsr_coarse_residual_geometry",
     "wsr_last_tile_plan", "wsr_last_tile_instantiation",
 ]
 
@@ -197,6 +198,9 @@ def lib() -> C.CDLL:
         "wsr_speed_soft_counts": [vp, i32, vp, i32, C.c_float, i32, i32, i32, i32, i32, vp, vp, vp],   # additive export
         "wsr_speed_soft_counts_bwd": [vp, i32, vp, C.c_float, i32, i32, i32, i32, i32, vp, vp],   # additive export
         "wsr_speed_soft_counts_geometry": [i32, i32, i32, i32, i32, C.POINTER(C.c_int32)],   # additive export
+        "wsr_coarse_residual": [vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp],   # additive export
+        "wsr_coarse_residual_bwd": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp],   # additive export
+        "wsr_coarse_residual_geometry": [i32, i32, i32, i32, i32, i32, C.POINTER(C.c_int32)],   # additive export
         "wsr_last_tile_plan": [C.POINTER(C.c_int32)],   # additive export (diagnostic)
         "wsr_last_tile_instantiation": [C.POINTER(C.c_int32)],   # additive export (diagnostic)
     }

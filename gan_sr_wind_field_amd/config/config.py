@@ -65,6 +65,10 @@ Extension (optional keys, defaults keep reference behaviour):
             absent = off; present, the generator loss carries weight * the 1-D Wasserstein distance (m/s) between the
             soft horizontal-speed histograms of SR and HR (distribution_loss.py, csrc/distribution_loss.hip), logged as
             ``distribution``
+  [CONSISTENCY_LOSS] weight / kernel / sigma / factor / norm
+            absent = off; present, the generator loss carries weight * the mean |r| (l1) or r^2 (l2) of the
+            coarse-grained difference r = D(SR - HR), D the anti-aliased coarse-graining of [DEGRADATION]
+            (consistency_loss.py, csrc/consistency_loss.hip), logged as ``consistency``
 """
 from __future__ import annotations
 
@@ -903,6 +907,72 @@ class DistributionLossConfig(OptionalSection):
         return bool(self.present)
 
 
+class ConsistencyLossConfig(OptionalSection):
+    """[CONSISTENCY_LOSS] (extension): a coarse-grained consistency term of the generator loss (consistency_loss.py,
+    csrc/consistency_loss.hip); absent section = off, and not printed by ``asINI``.  ``weight`` (required, > 0: there is
+    no reference default to inherit) multiplies ``L_cons``, the mean over samples, wind components, coarse cells and
+    levels of ``|r|`` (``norm = l1``) or ``r^2`` (``norm = l2``) of ``r = D(SR - HR)``; ``kernel`` (required): ``box`` or
+    ``gaussian``, the taps of ``degradation.taps``; ``sigma`` (gaussian only, required there): in HR grid cells,
+    0 < sigma <= 10; ``factor``: the coarse-graining factor in x and y, 0 = ``[DEFAULT] scale`` (the LR grid), else
+    2 .. 32.  The keys are independent of ``[DEGRADATION]``."""
+
+    weight: float = None
+    kernel: str = None
+    sigma: float = None
+    factor: int = 0
+    norm: str = "l1"
+    _section = "CONSISTENCY_LOSS"
+    _schema = (("weight", _F), ("kernel", _W), ("sigma", _F), ("factor", _I), ("norm", _W))
+
+    setConsistencyLossConfig = OptionalSection.load
+
+    def validate(self, scale) -> None:
+        if not self.present:
+            return
+        from ..degradation import KERNELS, MAX_RADIUS, taps
+        if self.weight is None:
+            raise ValueError("[CONSISTENCY_LOSS] weight is required: the weight of the consistency term in the "
+                             "generator loss")
+        if not (self.weight > 0 and math.isfinite(self.weight)):
+            raise ValueError(f"[CONSISTENCY_LOSS] weight must be a finite number > 0, not {self.weight}")
+        if self.kernel is None:
+            raise ValueError("[CONSISTENCY_LOSS] kernel is required: box or gaussian")
+        if self.kernel not in KERNELS:
+            raise ValueError(f"[CONSISTENCY_LOSS] kernel must be box or gaussian, not {self.kernel!r}")
+        if self.kernel == "gaussian":
+            if self.sigma is None:
+                raise ValueError("[CONSISTENCY_LOSS] sigma is required with kernel = gaussian: the width in HR grid "
+                                 "cells")
+            if not 0.0 < self.sigma <= 10.0:  # (NaN fails both)
+                raise ValueError(f"[CONSISTENCY_LOSS] sigma must be > 0 and <= 10, not {self.sigma}")
+        if self.norm not in ("l1", "l2"):
+            raise ValueError(f"[CONSISTENCY_LOSS] norm must be l1 or l2, not {self.norm!r}")
+        if self.factor != 0 and not 2 <= self.factor <= 32:
+            raise ValueError(f"[CONSISTENCY_LOSS] factor must be 0 ([DEFAULT] scale) or 2 .. 32, not {self.factor}")
+        s = self.resolved_factor(scale)
+        if s is None or not 2 <= s <= 32:
+            raise ValueError(f"[CONSISTENCY_LOSS] factor = 0 needs [DEFAULT] scale in 2 .. 32, not {scale}")
+        try:
+            taps(self.kernel, s, self.sigma)
+        except ValueError:
+            raise ValueError(f"[CONSISTENCY_LOSS] kernel = {self.kernel} at factor {s} needs a tap radius above "
+                             f"{MAX_RADIUS}") from None
+
+    def __str__(self) -> str:
+        # (``sigma`` has no value with kernel = box: a key printed as None would not load again)
+        return f"[{self._section}]\n" + "".join(f"{k} = {getattr(self, k)}\n" for k, _ in self._schema
+                                                if getattr(self, k) is not None)
+
+    def resolved_factor(self, scale):
+        """the coarse-graining factor: ``factor``, or ``scale`` when it is 0"""
+        return int(self.factor) if self.factor else (None if scale is None else int(scale))
+
+    @property
+    def on(self) -> bool:
+        """the generator loss carries the consistency term"""
+        return bool(self.present)
+
+
 class Config(IniConfig):
     name: str = "default_name"
     model: str = "default_model"
@@ -941,6 +1011,7 @@ class Config(IniConfig):
     increments: IncrementsConfig = IncrementsConfig()
     ssim_loss: SsimLossConfig = SsimLossConfig()
     distribution_loss: DistributionLossConfig = DistributionLossConfig()
+    consistency_loss: ConsistencyLossConfig = ConsistencyLossConfig()
     compute_dtype: str = "fp32"
     is_train: bool
     is_use: bool
@@ -957,6 +1028,8 @@ class Config(IniConfig):
     # (the sections above are a pinned list; later extensions load and print behind them, by the same rules)
     _optional_later = (("distribution", None), ("ssim_loss", None), ("fss", None), ("hub_height", None),
                        ("increments", None), ("distribution_loss", None))
+    # ([CONSISTENCY_LOSS] loads and prints behind every other section; it needs [DEFAULT] scale, like [DEGRADATION])
+    _optional_last = (("consistency_loss", lambda c: c.scale),)
 
     def __init__(self, ini_path):
         parser = ConfigParser(allow_no_value=True)
@@ -975,7 +1048,7 @@ class Config(IniConfig):
                 setattr(self, attr, None)
         if parser.has_section("DIST"):
             self.dist.setDistConfig(parser["DIST"])
-        for attr, given in self._optional + self._optional_later:
+        for attr, given in self._optional + self._optional_later + self._optional_last:
             sec = getattr(self, attr)
             sec.load(parser[sec._section] if parser.has_section(sec._section) else None)
             sec.validate(*(() if given is None else (given(self),)))
@@ -1006,7 +1079,7 @@ class Config(IniConfig):
         for sec in sections:
             if sec is not None:
                 out += "\n" + str(sec)
-        for attr, _ in self._optional + self._optional_later:  # (absent: the text of a file without the extension, unchanged)
+        for attr, _ in self._optional + self._optional_later + self._optional_last:  # (absent: the text of a file without the extension, unchanged)
             sec = getattr(self, attr)
             if sec.present and sec._printed:
                 out += "\n" + str(sec)

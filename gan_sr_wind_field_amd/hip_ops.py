@@ -1751,6 +1751,79 @@ def speed_soft_counts(HR: Tensor, SR: Tensor, tables) -> Tensor:
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# coarse-grained consistency loss of generator training ([CONSISTENCY_LOSS]; csrc/consistency_loss.hip)
+# ---------------------------------------------------------------------------------------------------------------------
+CONSISTENCY_LOSS_LDS_FLOATS = 16384  # WSR_CONSISTENCY_LOSS_LDS_FLOATS
+
+
+class _CoarseResidual(torch.autograd.Function):
+    """``wsr_coarse_residual`` with ``wsr_coarse_residual_bwd`` as backward: r (B, 3, XL, YL, NZ) = D(fl(SR - HR));
+    gradient flows only towards SR.  The operator is linear: nothing is saved but the shape and the two weight
+    tables."""
+
+    @staticmethod
+    def forward(ctx, hr: Tensor, sr: Tensor, wx: Tensor, wy: Tensor, s: int, R: int):
+        B, C_, X, Y, NZ = sr.shape
+        L = _lib.lib()
+        out = torch.empty((B, 3, wx.shape[0], wy.shape[0], NZ), dtype=torch.float32, device=sr.device)
+        check(L.wsr_coarse_residual(_p(hr), hr.shape[1], _p(sr), C_, _p(wx), _p(wy), s, R, B, X, Y, NZ, _p(out),
+                                    _stream()), "coarse_residual")
+        ctx.meta = (s, R, (B, C_, X, Y, NZ), wx, wy)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable  # (the kernel's result is no graph: a double backward is refused)
+    def backward(ctx, g: Tensor):
+        if not ctx.needs_input_grad[1]:
+            return None, None, None, None, None, None
+        s, R, (B, C_, X, Y, NZ), wx, wy = ctx.meta
+        L = _lib.lib()
+        gout = g.contiguous().float()
+        dsr = torch.empty((B, C_, X, Y, NZ), dtype=torch.float32, device=g.device)
+        check(L.wsr_coarse_residual_bwd(_p(gout), _p(wx), _p(wy), s, R, C_, B, X, Y, NZ, _p(dsr), _stream()),
+              "coarse_residual_bwd")
+        return None, dsr, None, None, None, None
+
+
+def coarse_residual_geometry(s: int, R: int, B: int, X: int, Y: int, NZ: int) -> Tuple[int, ...]:
+    """(XL, YL, coarse rows per forward workgroup, its runs, rows per backward workgroup, its runs, floats of LDS of a
+    forward and of a backward workgroup) of ``wsr_coarse_residual`` at this shape"""
+    geom = (C.c_int32 * 8)()
+    check(_lib.lib().wsr_coarse_residual_geometry(int(s), int(R), int(B), int(X), int(Y), int(NZ), geom),
+          "coarse_residual_geometry")
+    return tuple(geom)
+
+
+def coarse_residual(HR: Tensor, SR: Tensor, wx: Tensor, wy: Tensor, s: int) -> Tensor:
+    """``r = D(fl(SR - HR))`` of ``HR`` and ``SR`` (B, C >= 3, X, Y, NZ; channels 0..2 are read, surplus ones never) ->
+    fp32 (B, 3, ceil(X / s), ceil(Y / s), NZ): the coarse-graining of ``degradation.py`` with the fp32 device tables
+    ``wx`` (XL, 2 R + 1) and ``wy`` (YL, 2 R + 1) of ``degradation.axis_weights``, as ``consistency_loss.py`` defines it
+    (``wsr_coarse_residual``).  Differentiable towards SR only (``wsr_coarse_residual_bwd``: the adjoint, from the
+    upstream gradient and the tables alone; zero in surplus channels).  No atomics: the same bits on every call, forward
+    and backward."""
+    from . import consistency_loss
+
+    _need_cuda(HR, SR)
+    consistency_loss._check_pair(HR, SR, "coarse_residual")
+    B, _, X, Y, NZ = HR.shape
+    s = int(s)
+    for name, w, n in (("wx", wx, X), ("wy", wy, Y)):
+        if (w.dim() != 2 or w.dtype != torch.float32 or w.device != HR.device or not w.is_contiguous()
+                or w.shape[0] != -(-n // s) or w.shape[1] % 2 != 1 or w.shape[1] != wx.shape[1]):
+            raise ValueError(f"coarse_residual wants {name} as a contiguous float32 ({-(-n // s)}, 2 R + 1) tensor on "
+                             f"{HR.device}, got {w.dtype} {tuple(w.shape)} on {w.device}")
+    R = (wx.shape[1] - 1) // 2
+    geom = (C.c_int32 * 8)()
+    rc = _lib.lib().wsr_coarse_residual_geometry(s, R, B, X, Y, NZ, geom)
+    if rc != 0 or B * SR.shape[1] > 65535:
+        raise ValueError(f"coarse_residual: a factor of 2 .. 32, a tap radius of at most 32, an LDS strip of at most "
+                         f"{CONSISTENCY_LOSS_LDS_FLOATS} floats (about (2 R + s) NZ), B * C <= 65535, X <= 65535 and "
+                         f"2^31 - 1 voxels per sample, not s = {s}, R = {R}, B = {B}, C = {SR.shape[1]}, X = {X}, "
+                         f"Y = {Y}, NZ = {NZ}")
+    return _CoarseResidual.apply(HR.detach().contiguous().float(), SR.contiguous().float(), wx, wy, s, R)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # fractions skill score ([FSS]; csrc/fss.hip)
 # ---------------------------------------------------------------------------------------------------------------------
 FSS_TILE = 32  # FS_TILE of csrc/fss_kernels.h: the positions of a workgroup are FSS_TILE x FSS_TILE

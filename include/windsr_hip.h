@@ -854,6 +854,36 @@ int wsr_speed_soft_counts_bwd(const float* sr, int32_t sr_c, const float* gtab, 
                               int32_t Y, int32_t NZ, float* dsr, void* stream);
 int wsr_speed_soft_counts_geometry(int32_t B, int32_t X, int32_t Y, int32_t NZ, int32_t ns, int32_t* geom);
 
+/* ---- coarse-grained consistency loss of generator training ([CONSISTENCY_LOSS]; csrc/consistency_loss.hip) ------
+ * wsr_coarse_residual: r (B, 3, XL, YL, NZ) fp32, XL = ceil(X / s), YL = ceil(Y / s), every element written exactly
+ * once: the anti-aliased coarse-graining of [DEGRADATION] applied to the difference of the wind components of sr and hr
+ * (fp32 planar (B, c, X, Y, NZ), channels 0..2 read).  wx (XL, 2 R + 1) and wy (YL, 2 R + 1) fp32 (device) are the
+ * tables of degradation.axis_weights.  In fp32, every product and sum rounded, nothing contracted, accumulators from
+ * +0.0f, taps ascending, a tap outside [0, n) skipped and never read:
+ *    e[x, y, z] = sr - hr
+ *    g[i, y, z] = sum_d wx[i, d] e[s i + d - R, y, z]
+ *    r[i, j, z] = sum_d wy[j, d] g[i, s j + d - R, z]
+ * One launch, no workspace, no atomics; nothing is saved for the backward.
+ * wsr_coarse_residual_bwd: dsr (B, sr_c, X, Y, NZ) fp32, every element written exactly once: the vector-Jacobian product
+ * towards sr.  With G (B, 3, XL, YL, NZ) fp32 (device) = dL/dr, indices ascending:
+ *    t[x; j, z]   = sum_i wx[i, x - s i + R] G[i, j, z]          over the i with 0 <= x - s i + R <= 2 R
+ *    dsr[x, y, z] = sum_j wy[j, y - s j + R] t[x; j, z]          over the j with 0 <= y - s j + R <= 2 R
+ * zero in every channel from 3 on.  One launch, no atomics.  Both entries give the same bits on every call.
+ * wsr_coarse_residual_geometry: geom[0 .. 8) = (XL, YL, the coarse rows a forward workgroup owns, its runs of them per
+ * (sample, channel, coarse column), the rows a backward workgroup owns, its runs of them per (sample, channel, column),
+ * the floats of LDS of a forward and of a backward workgroup), a function of the arguments alone (host only).
+ * A null pointer, a channel count < 3, s outside 2 .. 32, R outside 0 .. WSR_DEGRADE_MAX_R, a non-positive size:
+ * WSR_EINVAL; an LDS strip above WSR_CONSISTENCY_LOSS_LDS_FLOATS floats (the forward holds the
+ * min(Y, s (TJ - 1) + 2 R + 1) NZ x-pass values of its run, the backward the t of the coarse rows its run reaches; R = 32
+ * with NZ = 128 fits), 3 B or sr_c B > 65535, X > 65535 or X * Y * NZ >= 2^31: WSR_EUNSUPPORTED; nothing is launched and
+ * nothing is written in either case. */
+#define WSR_CONSISTENCY_LOSS_LDS_FLOATS 16384
+int wsr_coarse_residual(const float* hr, int32_t hr_c, const float* sr, int32_t sr_c, const float* wx, const float* wy,
+                        int32_t s, int32_t R, int32_t B, int32_t X, int32_t Y, int32_t NZ, float* r, void* stream);
+int wsr_coarse_residual_bwd(const float* G, const float* wx, const float* wy, int32_t s, int32_t R, int32_t sr_c,
+                            int32_t B, int32_t X, int32_t Y, int32_t NZ, float* dsr, void* stream);
+int wsr_coarse_residual_geometry(int32_t s, int32_t R, int32_t B, int32_t X, int32_t Y, int32_t NZ, int32_t* geom);
+
 /* ---- fractions skill score ([FSS]; csrc/fss.hip) ---------------------------------------------------------------
  * wsr_level_fss: out (B, NZ, nt, nn, 5) doubles, written completely: per sample, z level, threshold t and
  * neighbourhood n = scales[k] five exact integers.  Sources 0 hr, 1 sr, 2 tl: fp32 planar (B, c, X, Y, NZ), channels
